@@ -114,7 +114,12 @@ def parse():
     ap.add_argument("--no-concurrent", action="store_true", help="run ED and VAE back to back on one stream (A/B switch)")
     ap.add_argument("--swin", action="store_true",
                     help="also time the Swin-T embedder (row A6: constructed but never executed by the reference forward)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (per-frame logits, vote) as DIR/<name>.npy (fp32)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def build_models(net, dtype, batch, device):
@@ -211,7 +216,7 @@ def main():
         logits = model(x, eps=eps)
         if dist_on:
             logits = gdist.gather_logits(logits, n_global, nets)
-        return _lib.vote(logits)
+        return logits, _lib.vote(logits)
 
     def fence():
         torch.cuda.synchronize()
@@ -225,9 +230,12 @@ def main():
     log("warm-up done")
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        out = step()
+        logits, out = step()
     fence()
     dt = time.perf_counter() - t0
+    # what a caller of the timed path receives from its last step: every step allocates fresh output tensors, so these
+    # are the last timed step's results (copied to the host outside the timed region)
+    dump = {"logits": logits.float().cpu().numpy(), "vote": out.float().cpu().numpy()} if a.dump_outputs else None
     if dist_on:
         t = torch.tensor([dt], dtype=torch.float64, device=device)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -239,7 +247,7 @@ def main():
     # step's launches are queued before the GPU reaches them; here the enqueue time of a step is exposed.
     t1 = time.perf_counter()
     for _ in range(a.steps):
-        out = step()
+        step()
         torch.cuda.synchronize()
     synced_ms = (time.perf_counter() - t1) / a.steps * 1e3
     log(f"synchronised after every step: {synced_ms:.3f} ms per step")
@@ -357,6 +365,13 @@ def main():
         torch.distributed.all_gather_object(names, f"{torch.cuda.get_device_name(device)} (cuda:{local_rank})")
         info = gdist.comm_info()
         comm = {"backend": "nccl (RCCL)", "allgather_path": info["path"], "rccl_ranks": info["ranks"], "devices": names}
+    if rank == 0 and a.dump_outputs:
+        import numpy as np
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in dump.items():
+            np.save(os.path.join(a.dump_outputs, f"{name}.npy"), np.ascontiguousarray(arr, dtype=np.float32))
+        log(f"outputs of the last timed step written to {a.dump_outputs}: " +
+            ", ".join(f"{k}{tuple(v.shape)}" for k, v in dump.items()))
     if rank == 0:
         fps = n_global * a.steps / dt
         line = {

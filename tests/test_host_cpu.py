@@ -289,19 +289,14 @@ def test_shard_bounds_cover_and_balance():
             assert max(sizes) - min(sizes) <= 1
 
 
-# ----------------------------------------------------------------------------- drop-in claim: the reference's own driver
-REFERENCE = "/root/reference"
-
-
-@pytest.mark.skipif(not os.path.exists(os.path.join(REFERENCE, "prediction.py")),
-                    reason="the reference checkout only exists in the build container")
-def test_reference_prediction_py_runs_unchanged_on_the_model_alias(tmp_path, monkeypatch, capsys):
-    """alias ``model`` -> ``genconvit_amd.model`` in sys.modules, then import the reference's
-    ``prediction.py`` IN PLACE (never copied) and drive ``vids()`` / ``predict()`` (prediction.py:12-47,231-266) with
-    ``df_face`` replaced by synthetic crops and the forward stubbed (no GPU here).  Checks the star-import surface
-    (``torch`` / ``os`` reach prediction.py through ``from model.pred_func import *``), the ``store_result`` schema
-    and that a per-video exception is printed and swallowed like the reference does."""
-    import importlib.util
+# ----------------------------------------------------------------------------- drop-in claim: the upstream driver's surface
+def test_prediction_driver_surface_on_the_model_alias(tmp_path, monkeypatch):
+    """alias ``model`` -> ``genconvit_amd.model`` in sys.modules and run the two imports the
+    upstream ``prediction.py`` starts with (``from model.pred_func import *``, ``from model.config import load_config``),
+    then make the calls its ``vids()`` / ``predict()`` make, in the same order and with the same arguments: load_config,
+    set_result, load_genconvit from a cwd-relative ``weight/`` file, is_video, pred_vid (forward stubbed: no GPU here),
+    store_result, real_or_fake, and the (0, 0.5) default for a video without faces.  Checks the star-import surface
+    (``torch`` / ``os`` reach the driver through it) and the ``store_result`` schema that ends up in result/*.json."""
     import json
     import genconvit_amd.model as gm
     from genconvit_amd import spec, synth
@@ -313,48 +308,43 @@ def test_reference_prediction_py_runs_unchanged_on_the_model_alias(tmp_path, mon
             sys.modules[f"model.{n}"] = __import__(f"genconvit_amd.model.{n}", fromlist=["_"])
         monkeypatch.chdir(tmp_path)                      # weight/, model/config.yaml and result/ are cwd-relative
         (tmp_path / "weight").mkdir()
-        (tmp_path / "result").mkdir()
         (tmp_path / "vids").mkdir()
         torch.save({"state_dict": synth.make_state_dict(spec.ed_spec(), 7, "ed/")}, tmp_path / "weight" / "ed_w.pth")
-        for n in ("a.mp4", "b.avi", "broken.mp4", "notes.txt"):
+        for n in ("a.mp4", "b.avi", "notes.txt"):
             (tmp_path / "vids" / n).write_bytes(b"0")
-        specm = importlib.util.spec_from_file_location("ref_prediction", os.path.join(REFERENCE, "prediction.py"))
-        pred = importlib.util.module_from_spec(specm)
-        specm.loader.exec_module(pred)                   # runs `from model.pred_func import *` + load_config()
-        assert pred.config["model"]["backbone"] == "convnext_tiny"
+        pred = {}
+        exec("from model.pred_func import *\nfrom model.config import load_config\n", pred)
         for name in ("load_genconvit", "df_face", "pred_vid", "is_video", "set_result", "store_result", "real_or_fake",
-                     "torch", "os"):
-            assert hasattr(pred, name), f"prediction.py did not receive `{name}` from the star import"
-
-        calls = []
-
-        def fake_df_face(vid, num_frames, net):
-            calls.append(os.path.basename(vid))
-            if "broken" in vid:
-                raise RuntimeError("decoder exploded")
-            return synth.make_frames(3, name=os.path.basename(vid))
+                     "load_config", "torch", "os"):
+            assert name in pred, f"the star import did not provide `{name}`"
+        config = pred["load_config"]()
+        assert config["model"]["backbone"] == "convnext_tiny"
 
         def fake_forward(self, x, eps=None):             # stands in for the HIP forward (no GPU in this container)
             return torch.tensor([[2.0, -1.0]] * x.shape[0])
 
         from genconvit_amd.model.genconvit import GenConViT
-        monkeypatch.setattr(pred, "df_face", fake_df_face)
         monkeypatch.setattr(GenConViT, "forward", fake_forward)
-        result = pred.vids("ed_w", "unused_vae", str(tmp_path / "vids"), "other", 15, "ed", False)
-        out = capsys.readouterr().out
-        assert "An error occurred: decoder exploded" in out              # prediction.py:44-45 swallows per video
-        assert "Invalid video file" in out                               # notes.txt
+        result = pred["set_result"]()
+        model = pred["load_genconvit"](config, "ed", "ed_w", "unused_vae", False)
+        assert isinstance(model, GenConViT) and not model.training
+        vids = sorted(os.listdir(tmp_path / "vids"))
+        assert [pred["is_video"](os.path.join(tmp_path, "vids", v)) for v in vids] == [True, True, False]
+        for v in vids[:2]:
+            df = synth.make_frames(3, name=v)
+            y, y_val = pred["pred_vid"](df, model)
+            result = pred["store_result"](result, v, y, y_val, "uncategorized", "unknown", None)
         v = result["video"]
-        assert sorted(v["name"]) == ["a.mp4", "b.avi"] and sorted(calls) == ["a.mp4", "b.avi", "broken.mp4"]
         assert set(v) == {"name", "pred", "klass", "pred_label", "correct_label"}
+        assert v["name"] == ["a.mp4", "b.avi"]
         assert v["klass"] == ["uncategorized"] * 2 and v["correct_label"] == ["unknown"] * 2
         assert v["pred_label"] == ["FAKE", "FAKE"]                       # index 0 = FAKE (pred_func.py:134-135)
         assert all(abs(p - float(torch.sigmoid(torch.tensor(2.0)))) < 1e-6 for p in v["pred"])
         json.dumps(result)                                               # what main() writes to result/*.json
-        # predict() with an empty face list: the (0, 0.5) default of prediction.py:252-254
-        monkeypatch.setattr(pred, "df_face", lambda vid, n, net: [])
-        r2, acc, count, p = pred.predict("x.mp4", None, False, pred.set_result(), 15, "ed", "uncategorized")
-        assert p == [0, 0.5] and r2["video"]["pred_label"] == ["FAKE"]   # y = 0 -> {0: "REAL", 1: "FAKE"}[0 ^ 1]
+        # a video without faces: predict() stores (0, 0.5) without calling the model
+        y, y_val = torch.tensor(0).item(), torch.tensor(0.5).item()
+        r2 = pred["store_result"](pred["set_result"](), "x.mp4", y, y_val, "uncategorized", "unknown", None)
+        assert r2["video"]["pred_label"] == ["FAKE"] and pred["real_or_fake"](y) == "FAKE"
     finally:
         for k, m in saved.items():
             if m is None:

@@ -210,7 +210,11 @@ def test_oracle_architecture_constants_are_its_own_and_agree_with_the_product():
 
 
 def test_committed_huggingface_fixture_is_what_the_script_produces(tmp_path):
-    """tests/golden/hf_backbones.npz must be reproducible from tests/golden/make_hf_golden.py in this container."""
+    """tests/golden/hf_backbones.npz must be reproducible from tests/golden/make_hf_golden.py.  The float32 reductions of
+    the CPU kernels run in an order that depends on the host's vector ISA and thread count, so a rerun on another host
+    (or with another torch.set_num_threads) moves the logits by a few ulps (<= 2e-6 seen at |logit| <= 4); the bound below
+    is ten times that, under the 5e-5 / 1e-4 the script itself allows between Hugging Face and the oracle, and orders of
+    magnitude under what any change of weights, frames or architecture produces."""
     import importlib.util
     import numpy as np
     here = os.path.dirname(os.path.abspath(__file__))
@@ -222,7 +226,8 @@ def test_committed_huggingface_fixture_is_what_the_script_produces(tmp_path):
     new, old = dict(np.load(out)), dict(np.load(os.path.join(here, "golden", "hf_backbones.npz")))
     assert set(new) == set(old)
     for k in old:
-        assert np.array_equal(new[k], old[k]), k
+        assert new[k].shape == old[k].shape and new[k].dtype == old[k].dtype, k
+        assert np.abs(new[k] - old[k]).max() <= 2e-5, (k, float(np.abs(new[k] - old[k]).max()))
 
 
 # ----------------------------------------------------------------------------- row N4: cv2.INTER_AREA restatement
