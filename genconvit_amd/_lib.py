@@ -64,6 +64,9 @@ SIGNATURES = {
     "gcv_preprocess": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "gcv_face_crop_resize": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "gcv_vote_segments": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "gcv_tap_set": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t]),
+    "gcv_tap_clear": (c_int, [c_void_p]),
+    "gcv_tap_written": (c_int, [c_void_p, c_char_p]),
     "gcv_profile_enable": (c_int, [c_void_p, c_int]),
     "gcv_profile_report": (c_char_p, [c_void_p]),
     "gcv_k_gemm": (c_int, [c_int, c_int, c_int, ctypes.POINTER(GemmArgs), c_void_p]),
@@ -235,6 +238,32 @@ class Handle:
         self._settle()
         arr, keep, _ = self._descs(state_dict)
         check(self.lib.gcv_load_swin(self._h, arr, len(keep), prefix.encode()), "gcv_load_swin")
+
+    # -- taps (tests: include/genconvit_hip.h, gcv_tap_set) ------------------------------------
+    def set_tap(self, name, tensor):
+        """Copy intermediate ``name`` into ``tensor`` (a contiguous device tensor of its exact size) at every following
+        forward of this handle; ``tensor=None`` removes the tap.  The handle keeps a reference to the tensor."""
+        taps = self.__dict__.setdefault("_taps", {})
+        if tensor is None:
+            check(self.lib.gcv_tap_set(self._h, name.encode(), None, 0), "gcv_tap_set")
+            taps.pop(name, None)
+            return
+        if not (tensor.is_cuda and tensor.is_contiguous()):
+            raise GenConViTHipError("a tap buffer must be a contiguous device tensor")
+        check(self.lib.gcv_tap_set(self._h, name.encode(), tensor.data_ptr(), tensor.numel() * tensor.element_size()),
+              "gcv_tap_set")
+        taps[name] = tensor
+
+    def clear_taps(self):
+        check(self.lib.gcv_tap_clear(self._h), "gcv_tap_clear")
+        self.__dict__.pop("_taps", None)
+
+    def tap_written(self, name) -> bool:
+        """True if the last forward stored all of tap ``name``; False if its dispatch never stores that tensor."""
+        rc = self.lib.gcv_tap_written(self._h, name.encode())
+        if rc < 0:
+            check(rc, "gcv_tap_written")
+        return rc == 1
 
     # -- forwards --------------------------------------------------------------------------
     def _check_x(self, x, res=224):

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <set>
 #include <sstream>
 #include <vector>
 
@@ -65,6 +66,27 @@ struct Roctx {
 };
 Roctx& roctx() { static Roctx r; return r; }
 }  // namespace
+bool tap_name_known(const std::string& name) {
+  static const std::set<std::string> names = [] {
+    std::set<std::string> n;
+    for (const char* t : {"ed.e1", "ed.e2", "ed.e3", "ed.e4", "ed.e5", "ed.d1", "ed.d2", "ed.d3", "ed.d4", "ed.rec", "ed.feat",
+                          "vae.v1", "vae.v2", "vae.v3", "vae.v4", "vae.mu", "vae.z", "vae.d1", "vae.d2", "vae.d3", "vae.xhat",
+                          "vae.feat"})
+      n.insert(t);
+    static const int depths[4] = {3, 3, 9, 3};
+    for (const char* net : {"ed", "vae"}) {
+      const std::string p = std::string(net) + ".bb.";
+      n.insert(p + "stem");
+      n.insert(p + "pool");
+      for (int i = 0; i < 4; ++i) {
+        if (i > 0) n.insert(p + "s" + std::to_string(i) + ".down_in");
+        for (int j = 0; j < depths[i]; ++j) n.insert(p + "s" + std::to_string(i) + ".b" + std::to_string(j));
+      }
+    }
+    return n;
+  }();
+  return names.count(name) != 0;
+}
 void roctx_push(const char* tag) { if (roctx().push) (void)roctx().push(tag); }
 void roctx_pop() { if (roctx().pop) (void)roctx().pop(); }
 }  // namespace gcv
@@ -440,6 +462,31 @@ int gcv_vote(const float* logits, int rows, float* mean2, gcv_stream stream) {
 int gcv_vote_segments(const float* logits, int batch, int nets, const int* offsets, int n_videos, float* mean2,
                       gcv_stream stream) {
   return launch_vote_segments(logits, batch, nets, offsets, n_videos, mean2, (hipStream_t)stream);
+}
+
+int gcv_tap_set(gcv_handle* h, const char* name, void* dst, size_t bytes) {
+  GCV_REQUIRE(h && name, "null handle / tap name");
+  GCV_REQUIRE(tap_name_known(name), std::string("unknown tap '") + name + "'");
+  if (!dst) { h->net->taps.erase(name); return 0; }
+  GCV_REQUIRE(bytes > 0, "tap buffer of 0 bytes");
+  Tap t;
+  t.dst = dst;
+  t.bytes = bytes;
+  h->net->taps[name] = t;
+  return 0;
+}
+
+int gcv_tap_clear(gcv_handle* h) {
+  GCV_REQUIRE(h, "null handle");
+  h->net->taps.clear();
+  return 0;
+}
+
+int gcv_tap_written(gcv_handle* h, const char* name) {
+  GCV_REQUIRE(h && name, "null handle / tap name");
+  auto it = h->net->taps.find(name);
+  GCV_REQUIRE(it != h->net->taps.end(), std::string("no tap '") + name + "' is set");
+  return it->second.need != 0 && it->second.mask == it->second.need ? 1 : 0;
 }
 
 size_t gcv_workspace_bytes(const gcv_handle* h) { return h ? h->net->workspace_bytes() : 0; }

@@ -43,6 +43,17 @@ struct Profiler {
   ~Profiler();
 };
 
+// ---- test taps (gcv_tap_set, include/genconvit_hip.h) -------------------------
+// A caller-owned device buffer that the forwards copy one named intermediate into.  A backbone tap covers every segment of
+// the network's token stream; `mask` collects the segments whose copy was enqueued by the current forward and `need` is
+// the set it takes to fill the buffer, so a tensor that some launch of the dispatch never stores reads as "not written".
+struct Tap {
+  void* dst = nullptr;
+  size_t bytes = 0;
+  unsigned mask = 0, need = 0;
+};
+bool tap_name_known(const std::string& name);
+
 // ---- abstract network (dtype erased) ----------------------------------------
 struct NetBase {
   int device = 0;
@@ -53,6 +64,7 @@ struct NetBase {
   // host-side enqueue order of the ensemble (gcv_genconvit_forward): called by vae_forward once its encoder -> mu ->
   // decoder chain is enqueued and before its backbone pass, to enqueue the ED network on its own stream in between
   std::function<int()> after_chain;
+  std::map<std::string, Tap> taps;   // empty unless a test registered one: then no forward looks at it
   virtual ~NetBase() {}
   virtual int init() = 0;
   virtual int load_ed(const TensorMap& w) = 0;

@@ -78,6 +78,13 @@ struct Arena {
   }
   template <typename U> U* get(int64_t n) { return (U*)alloc((size_t)n * sizeof(U)); }
 };
+// releases an arena mark on every exit path of a forward (an error return included)
+struct ArenaScope {
+  Arena& a;
+  const size_t m;
+  explicit ArenaScope(Arena& a_) : a(a_), m(a_.mark()) {}
+  ~ArenaScope() { a.release(m); }
+};
 
 // device-side permute+cast for the 25088x12544 mu/var matrices: columns c*196+hw -> hw*128+c so the
 // NHWC encoder output (B,14,14,128) can be used as the GEMM A operand without a transpose.
@@ -182,8 +189,15 @@ template <typename T> struct NetImpl : NetBase {
     void now() { if (ev) { (void)hipStreamWaitEvent(s, ev, 0); ev = nullptr; } }
     ~Join() { now(); }
   };
+  // (test taps) the segments of one network's backbone token stream in the library's concatenation order; a run_convnext call
+  // covers segments [first, first + nseg of the call).
+  struct TapPass {
+    const char* net;      // "ed" / "vae"
+    int nall, first;
+    int n[4], H[4], W[4];
+  };
   // run one backbone pass on the side stream, forked from `s` here
-  int side_pass(const CnxW<T>& w, const Seg<T>* seg, hipStream_t s, Join& join) {
+  int side_pass(const CnxW<T>& w, const Seg<T>* seg, hipStream_t s, Join& join, const TapPass* tp) {
     if (!arena.dry) {
       if (!vae_side) {
         GCV_CHECK_HIP(hipStreamCreateWithFlags(&vae_side, hipStreamNonBlocking));
@@ -194,7 +208,7 @@ template <typename T> struct NetImpl : NetBase {
       GCV_CHECK_HIP(hipStreamWaitEvent(vae_side, vae_fork, 0));
       cur = vae_side;
     }
-    const int rc = run_convnext(w, seg, 1, true);
+    const int rc = run_convnext(w, seg, 1, true, tp);
     cur = s;
     if (!arena.dry && hipEventRecord(vae_join, vae_side) == hipSuccess) join.arm(s, vae_join);
     return rc;
@@ -238,6 +252,62 @@ template <typename T> struct NetImpl : NetBase {
     double bytes = sizeof(T) * (a_bytes + (double)g.N * g.K + c_bytes);
     if (epi == EPI_SPLITK) bytes = sizeof(T) * (a_bytes + (double)g.N * g.K) + 4.0 * g.splitk * (double)g.M * g.N;
     return run(tag, flops, bytes, [&] { return launch_gemm<T>(g, a_mode, epi, cur); });
+  }
+
+  // ------------------------------------------------------------ test taps (Tap in net.h, gcv_tap_set)
+  // Nothing below runs unless a tap is registered: the forwards pass a null TapPass and skip every tap call when `taps` is
+  // empty.  Copies are enqueued on `cur`, the stream that produced the tensor.
+  void tap_reset(const char* net) {
+    const size_t k = std::strlen(net);
+    for (auto& kv : taps)
+      if (kv.first.compare(0, k, net) == 0 && kv.first[k] == '.') kv.second.mask = kv.second.need = 0;
+  }
+  // `bytes` from `src` into tap `name` at byte offset `off`; `total`: the tap's size in this forward.  rows > 1: `rows`
+  // rows of `bytes`, `spitch` bytes apart in the source, packed in the tap.  segbits / need: see Tap.
+  int tap_copy(const std::string& name, size_t total, size_t off, const void* src, size_t bytes, unsigned segbits,
+               unsigned need, size_t rows = 1, size_t spitch = 0) {
+    auto it = taps.find(name);
+    if (it == taps.end() || arena.dry) return 0;
+    Tap& t = it->second;
+    if (t.bytes != total) {
+      set_error("tap '" + name + "': buffer of " + std::to_string(t.bytes) + " bytes, this forward stores " +
+                std::to_string(total));
+      return -8;
+    }
+    char* d = (char*)t.dst + off;
+    if (rows == 1) GCV_CHECK_HIP(hipMemcpyAsync(d, src, bytes, hipMemcpyDeviceToDevice, cur));
+    else GCV_CHECK_HIP(hipMemcpy2DAsync(d, bytes, src, spitch, bytes, rows, hipMemcpyDeviceToDevice, cur));
+    t.mask |= segbits;
+    t.need = need;
+    return 0;
+  }
+  int tap_net(const char* name, const void* src, size_t bytes) { return tap_copy(name, bytes, 0, src, bytes, 1u, 1u); }
+  // per-image elements of a backbone tap of segment s: kind 0 stem, 1 block output of stage i, 2 the operand of stage i's
+  // downsample GEMM, 3 pooled rows
+  static int64_t tap_img_elems(const TapPass& tp, int s, int kind, int i) {
+    const int64_t hw = (int64_t)((tp.H[s] / 4) >> i) * ((tp.W[s] / 4) >> i);
+    return kind == 3 ? 768 : kind == 2 ? hw * 4 * kDims[i - 1] : hw * kDims[i];
+  }
+  // segments [tp.first, tp.first + nseg) of backbone tap `<net>.bb.<what>`, contiguous at `src` (pool_ld > 0: pooled rows
+  // stored frame-major, row pool_ld * frame + segment)
+  int tap_bb(const TapPass& tp, int nseg, const std::string& what, int kind, int i, const T* src, int pool_ld = 0) {
+    const std::string name = std::string(tp.net) + ".bb." + what;
+    if (!taps.count(name)) return 0;
+    int64_t total = 0, off = 0, n = 0;
+    for (int s = 0; s < tp.nall; ++s) {
+      const int64_t e = tp.n[s] * tap_img_elems(tp, s, kind, i);
+      if (s == tp.first) off = total;
+      if (s >= tp.first && s < tp.first + nseg) n += e;
+      total += e;
+    }
+    const unsigned need = (1u << tp.nall) - 1, bits = ((1u << nseg) - 1) << tp.first;
+    if (!pool_ld) return tap_copy(name, total * sizeof(T), off * sizeof(T), src, n * sizeof(T), bits, need);
+    for (int s = 0; s < nseg; ++s) {
+      GCV_TRY(tap_copy(name, total * sizeof(T), off * sizeof(T), src + s * 768, 768 * sizeof(T), bits, need,
+                       tp.n[tp.first + s], (size_t)pool_ld * 768 * sizeof(T)));
+      off += (int64_t)tp.n[tp.first + s] * 768;
+    }
+    return 0;
   }
 
   // ------------------------------------------------------------ weight fetch helpers
@@ -559,7 +629,8 @@ template <typename T> struct NetImpl : NetBase {
   // ------------------------------------------------------------ ConvNeXt-T over token segments
   // keep = true leaves the token buffers allocated (the caller releases its own mark): two passes of one forward that run
   // on different streams must not share them
-  int run_convnext(const CnxW<T>& w, const Seg<T>* segs, int nseg, bool keep = false) {
+  // tp: taps of this pass (null: none registered)
+  int run_convnext(const CnxW<T>& w, const Seg<T>* segs, int nseg, bool keep = false, const TapPass* tp = nullptr) {
     int h[4], wd[4];
     int64_t m[4], moff[4], M = 0;
     int ntot = 0;
@@ -588,6 +659,7 @@ template <typename T> struct NetImpl : NetBase {
                                  X + moff[s] * 96, g.n, h[s], wd[s], 1e-6f, cur);
       }));
     }
+    if (tp) GCV_TRY(tap_bb(*tp, nseg, "stem", 0, 0, X));
     int bi = 0;
     bool lnp_fused = false;       // the previous stage's last MLP has already written the LayerNorm'ed patches (into Hd)
     for (int i = 0; i < 4; ++i) {
@@ -625,8 +697,13 @@ template <typename T> struct NetImpl : NetBase {
         g.A = lnp_fused ? Hd : Y; g.lda = 4 * Cp; g.Wt = w.down[i - 1].w; g.C = X; g.ldc = C; g.bias = w.down[i - 1].b;
         lnp_fused = false;
         g.M = (int)M; g.N = C; g.K = 4 * Cp; g.act = ACT_NONE; g.splitk = 1;
+        if (tp) GCV_TRY(tap_bb(*tp, nseg, "s" + std::to_string(i) + ".down_in", 2, i, (const T*)g.A));
         GCV_TRY(gemm("cnx.down_gemm", g, A_PLAIN, EPI_BIAS_ACT));
       }
+      // the residual stream after block j, unless its epilogue went straight to the stage boundary (lnp_fused)
+      auto tap_block = [&](int j) {
+        return tp && !lnp_fused ? tap_bb(*tp, nseg, "s" + std::to_string(i) + ".b" + std::to_string(j), 1, i, X) : 0;
+      };
       for (int j = 0; j < kDepths[i]; ++j, ++bi) {
         const CnxBlockW<T>& k = w.blk[bi];
         for (int s = 0; s < nseg;) {
@@ -659,6 +736,7 @@ template <typename T> struct NetImpl : NetBase {
             }
             GCV_TRY(run("cnx.fused_mlp", 16.0 * M * C * (double)C, 3.0 * sizeof(T) * (double)M * C + 16.0 * C * C,
                         [&] { return launch_xs_mlp<T>(xa, C, cur); }));
+            GCV_TRY(tap_block(j));
             continue;
           }
           if (k.fc2_wc && use_fused_mlp && (C < 384 || use_fused_mlp384)) {
@@ -681,6 +759,7 @@ template <typename T> struct NetImpl : NetBase {
             }
             GCV_TRY(run("cnx.fused_mlp", 16.0 * M * C * (double)C, 3.0 * sizeof(T) * (double)M * C + 16.0 * C * C,
                         [&] { return launch_fused_mlp<T>(ma, C, cur); }));
+            GCV_TRY(tap_block(j));
             continue;
           }
         }
@@ -691,6 +770,7 @@ template <typename T> struct NetImpl : NetBase {
                         [&] { return launch_xs_pw1<T>(pa, C, cur); }));
             GCV_TRY(run("cnx.pw2_scale_res", 8.0 * M * C * (double)C, sizeof(T) * (6.0 * M * C + 4.0 * C * C),
                         [&] { return launch_pw2f<T>(pa, C, cur); }));
+            GCV_TRY(tap_block(j));
             continue;
           }
         }
@@ -702,6 +782,7 @@ template <typename T> struct NetImpl : NetBase {
         g2.A = Hd; g2.lda = 4 * C; g2.Wt = k.fc2_w; g2.C = X; g2.ldc = C; g2.bias = k.fc2_b; g2.gamma = k.gamma;
         g2.resid = X; g2.M = (int)M; g2.N = C; g2.K = 4 * C; g2.act = ACT_NONE; g2.splitk = 1;
         GCV_TRY(gemm("cnx.pw2_scale_res", g2, A_PLAIN, EPI_RESID));
+        GCV_TRY(tap_block(j));
       }
     }
     // pooling + LayerNorm: one launch over neighbouring segments of one map size (their tokens are contiguous).  When the
@@ -734,6 +815,7 @@ template <typename T> struct NetImpl : NetBase {
       }
       no += segs[s].n;
     }
+    if (tp) GCV_TRY(tap_bb(*tp, nseg, "pool", 3, 0, Pool, one_fc ? nseg : 0));
     if (one_fc) {
       GemmArgs g{};
       g.A = Pool; g.lda = 768; g.Wt = w.head_fc_w; g.C = segs[0].out; g.ldc = 1000;
@@ -776,7 +858,8 @@ template <typename T> struct NetImpl : NetBase {
     }
     cur = s;
     const T* x = (const T*)xv;
-    const size_t mk = arena.mark();
+    if (!taps.empty()) tap_reset("ed");
+    const ArenaScope scope(arena);
     T* e1 = arena.get<T>((int64_t)B * 112 * 112 * 16);
     T* e2 = arena.get<T>((int64_t)B * 56 * 56 * 32);
     T* e3 = arena.get<T>((int64_t)B * 28 * 28 * 64);
@@ -830,9 +913,19 @@ template <typename T> struct NetImpl : NetBase {
     Seg<T> segs[2];
     segs[0] = Seg<T>{rec, (int64_t)224 * 224 * 3, 1, 224 * 3, 3, B, 224, 224, feat, 2000, ACT_GELU};
     segs[1] = Seg<T>{x, (int64_t)3 * 224 * 224, 224 * 224, 224, 1, B, 224, 224, feat + 1000, 2000, ACT_GELU};
-    GCV_TRY(run_convnext(bb_ed, segs, 2));
+    const TapPass tp{"ed", 2, 0, {B, B}, {224, 224}, {224, 224}};
+    GCV_TRY(run_convnext(bb_ed, segs, 2, false, taps.empty() ? nullptr : &tp));
     GCV_TRY(run_head(ed.head, feat, B, ACT_GELU, logits));
-    arena.release(mk);
+    if (!taps.empty()) {
+      const T* et[5] = {e1, e2, e3, e4, e5};
+      const int64_t ee[5] = {112 * 112 * 16, 56 * 56 * 32, 28 * 28 * 64, 14 * 14 * 128, 7 * 7 * 256};
+      const T* dt[4] = {d1, d2, d3, d4};
+      const int64_t de[4] = {14 * 14 * 128, 28 * 28 * 64, 56 * 56 * 32, 112 * 112 * 16};
+      for (int l = 0; l < 5; ++l) GCV_TRY(tap_net(("ed.e" + std::to_string(l + 1)).c_str(), et[l], B * ee[l] * sizeof(T)));
+      for (int l = 0; l < 4; ++l) GCV_TRY(tap_net(("ed.d" + std::to_string(l + 1)).c_str(), dt[l], B * de[l] * sizeof(T)));
+      GCV_TRY(tap_net("ed.rec", rec, (size_t)B * 224 * 224 * 3 * sizeof(T)));
+      GCV_TRY(tap_net("ed.feat", feat, (size_t)B * 2000 * sizeof(T)));
+    }
     return 0;
   }
 
@@ -847,11 +940,12 @@ template <typename T> struct NetImpl : NetBase {
     }
     cur = s;
     const T* x = (const T*)xv;
+    if (!taps.empty()) tap_reset("vae");
     // split-K plan of the 25088-deep mu / var GEMMs (392 K tiles of 64 = 8 * 49): 8 ways at 128-row tiles (98 x 8 = 784
     // workgroups), 7 ways for batches of 64 frames and fewer, whose 32- / 64-row tiles leave room for every one of the 686
     // workgroups at once (vae B = 32 bf16, same box: 0.143 -> 0.118 ms; at B = 128 seven ways measure 0.193 against 0.175)
     const int SPLITK = B <= 64 ? 7 : 8, KPS = 25088 / SPLITK;
-    const size_t mk = arena.mark();
+    const ArenaScope scope(arena);
     T* v1 = arena.get<T>((int64_t)B * 112 * 112 * 16);
     T* v2 = arena.get<T>((int64_t)B * 56 * 56 * 32);
     T* v3 = arena.get<T>((int64_t)B * 28 * 28 * 64);
@@ -873,8 +967,10 @@ template <typename T> struct NetImpl : NetBase {
     segs[0] = Seg<T>{x, (int64_t)3 * 224 * 224, 224 * 224, 224, 1, B, 224, 224, feat, 2000, ACT_RELU};
     segs[1] = Seg<T>{xhat, (int64_t)112 * 112 * 3, 1, 112 * 3, 3, B, 112, 112, feat + 1000, 2000, ACT_RELU};
     const bool split = (vae_split_env >= 0 ? vae_split_env != 0 : !in_ensemble) && !prof.enabled;   // (profiled steps stay on one stream: serial per-kernel times)
+    const TapPass tp0{"vae", 2, 0, {B, B}, {224, 112}, {224, 112}}, tp1{"vae", 2, 1, {B, B}, {224, 112}, {224, 112}};
+    const bool tapping = !taps.empty();
     Join join;
-    if (split) GCV_TRY(side_pass(bb_vae, &segs[0], s, join));
+    if (split) GCV_TRY(side_pass(bb_vae, &segs[0], s, join, tapping ? &tp0 : nullptr));
 
     GCV_TRY(run("vae.enc1_conv3s2_bn_leaky", 2.0 * B * 112 * 112 * 16 * 27,
                 sizeof(T) * (double)B * (3 * 224 * 224 + 16 * 112 * 112), [&] {
@@ -927,16 +1023,27 @@ template <typename T> struct NetImpl : NetBase {
                 sizeof(T) * (double)B * (16 * 56 * 56 + 3 * 112 * 112),
                 [&] { return launch_convt2_small<T>(d3, vae.dec4_w, vae.dec4_b, xhat, B, 56, 56, ACT_LEAKY, cur); }));
     if (after_chain && !arena.dry) GCV_TRY(after_chain());
-    if (split) { GCV_TRY(run_convnext(bb_vae, &segs[1], 1, true)); }
-    else { GCV_TRY(run_convnext(bb_vae, segs, 2)); }
+    if (split) { GCV_TRY(run_convnext(bb_vae, &segs[1], 1, true, tapping ? &tp1 : nullptr)); }
+    else { GCV_TRY(run_convnext(bb_vae, segs, 2, false, tapping ? &tp0 : nullptr)); }
     join.now();
+    if (tapping) {
+      const T* vt[4] = {v1, v2, v3, v4};
+      const int64_t ve[4] = {112 * 112 * 16, 56 * 56 * 32, 28 * 28 * 64, 14 * 14 * 128};
+      const T* dt[3] = {d1, d2, d3};
+      const int64_t de[3] = {14 * 14 * 64, 28 * 28 * 32, 56 * 56 * 16};
+      for (int l = 0; l < 4; ++l) GCV_TRY(tap_net(("vae.v" + std::to_string(l + 1)).c_str(), vt[l], B * ve[l] * sizeof(T)));
+      GCV_TRY(tap_net("vae.mu", mu, (size_t)B * 12544 * sizeof(float)));
+      GCV_TRY(tap_net("vae.z", z, (size_t)B * 12544 * sizeof(T)));
+      for (int l = 0; l < 3; ++l) GCV_TRY(tap_net(("vae.d" + std::to_string(l + 1)).c_str(), dt[l], B * de[l] * sizeof(T)));
+      GCV_TRY(tap_net("vae.xhat", xhat, (size_t)B * 112 * 112 * 3 * sizeof(T)));
+      GCV_TRY(tap_net("vae.feat", feat, (size_t)B * 2000 * sizeof(T)));
+    }
     GCV_TRY(run_head(vae.head, feat, B, ACT_RELU, logits));
     if (recon224 || mse) {
       GCV_TRY(run("vae.resize_mse", 30.0 * B * 224 * 224, sizeof(T) * (double)B * (3 * 112 * 112 + 6 * 224 * 224), [&] {
         return launch_resize_mse<T>(xhat, x, (T*)recon224, msepart, mse, B, cur);
       }));
     }
-    arena.release(mk);
     return 0;
   }
 

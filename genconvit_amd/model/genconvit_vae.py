@@ -48,11 +48,15 @@ class GenConViTVAE(HipModule):
             eps = torch.randn((B, self.latent_dims), dtype=torch.float32, device=x.device, generator=self._generator)
         else:
             eps = eps.to(device=x.device, dtype=torch.float32)
-        if B > 512:                                   # beyond one handle's workspace: consecutive chunks (kl: last chunk's)
+        if B > 512:                                   # beyond one handle's workspace: consecutive chunks
+            chunks = self._chunks(B)
             parts = [self._get_handle(hi - lo).vae_forward(x[lo:hi], eps[lo:hi], want_recon, want_mse, want_kl)
-                     for lo, hi in self._chunks(B)]
+                     for lo, hi in chunks]
             cat = lambda i: torch.cat([p[i] for p in parts]) if parts[0][i] is not None else None
-            logits, recon, mse, kl = cat(0), cat(1), cat(2), parts[-1][3]
+            logits, recon, mse = cat(0), cat(1), cat(2)
+            kl = None
+            if want_kl:   # Encoder.kl is a mean over the batch (genconvit_vae.py:58): each chunk's mean weighted by its frames
+                kl = sum(p[3] * (hi - lo) for p, (lo, hi) in zip(parts, chunks)) / B
         else:
             logits, recon, mse, kl = self._get_handle(B).vae_forward(x, eps, want_recon, want_mse, want_kl)
         self.kl = kl[0] if kl is not None else None

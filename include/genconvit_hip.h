@@ -154,6 +154,37 @@ int  gcv_allgather_logits(gcv_comm* c, const float* local, int n_local, float* a
 int gcv_profile_enable(gcv_handle* h, int on);
 const char* gcv_profile_report(gcv_handle* h);
 
+/* ---- taps: named intermediates of the forwards, copied into caller-owned device buffers (tests) ----
+ * gcv_tap_set registers `dst` (`bytes` long) for tap `name` on the handle; dst == NULL removes it.  Each following
+ * gcv_ed_forward / gcv_vae_forward / gcv_genconvit_forward of the handle enqueues a hipMemcpyAsync device-to-device
+ * of the tensor into `dst` on the stream that produced it (the VAE's side stream for backbone(x) under the split
+ * schedule), ordered before the forward's end on `stream` like the rest of its work.  With no tap set nothing is
+ * copied, launched or synchronised.  An unknown name is an error of gcv_tap_set; a buffer whose size differs from the
+ * tensor's size at the forward's batch makes the forward fail.
+ * gcv_tap_written: 1 if the last forward of the tap's network stored the whole tensor, 0 if the dispatch never stores
+ * it in HBM for some segment (then `dst` holds stale data), < 0 if no such tap is set.  Example: the residual stream
+ * after the last block of stage 0 / 1 when that block's MLP epilogue applies the stage boundary's LayerNorm-patchify.
+ * Layouts (T = the handle's storage dtype; NHWC = (B, H, W, C) row-major; B = the forward's batch):
+ *   ed.e1..ed.e5      encoder outputs, NHWC T: 112x112x16, 56x56x32, 28x28x64, 14x14x128, 7x7x256
+ *   ed.d1..ed.d4      decoder outputs, NHWC T: 14x14x128, 28x28x64, 56x56x32, 112x112x16;  ed.rec: 224x224x3 NHWC T
+ *   ed.feat           (B, 2000) T: GELU(cat(backbone(rec), backbone(x))), the input of the head's fc
+ *   vae.v1..vae.v4    encoder outputs, NHWC T: 112x112x16, 56x56x32, 28x28x64, 14x14x128
+ *   vae.mu            (B, 12544) fp32 in the reference's order (c * 49 + hw);  vae.z: the sample z, NHWC T 7x7x256
+ *   vae.d1..vae.d3    decoder outputs, NHWC T: 14x14x64, 28x28x32, 56x56x16;  vae.xhat: 112x112x3 NHWC T
+ *   vae.feat          (B, 2000) T: ReLU(cat(backbone(x), backbone(x_hat)))
+ *   <net>.bb.<t>      the ConvNeXt-T token stream of network <net> (ed, vae), its segments concatenated in the order
+ *                     ed: [backbone(rec) B images, backbone(x) B images], vae: [backbone(x) @224, backbone(x_hat) @112],
+ *                     whichever launches ran them.  Per segment, images in order, tokens (h, w) row-major, channels
+ *                     innermost, in T, with h = H/4 >> i, w = W/4 >> i at stage i (H = W = 224 or 112):
+ *     stem            (tokens, 96) after the stem's LayerNorm
+ *     s<i>.b<j>       (tokens, C_i) the residual stream after block j of stage i (C = 96, 192, 384, 768; j < 3, 3, 9, 3)
+ *     s<i>.down_in    i = 1..3: the operand of stage i's downsample GEMM, (h_i * w_i rows, 4 * C_(i-1)) with
+ *                     (dy, dx, c) innermost: LayerNorm2d + 2x2 patch rows of stage i-1's output, whichever kernel wrote it
+ *     pool            (images, 768) the pooled + LayerNorm'ed rows */
+int gcv_tap_set(gcv_handle* h, const char* name, void* dst, size_t bytes);
+int gcv_tap_clear(gcv_handle* h);
+int gcv_tap_written(gcv_handle* h, const char* name);
+
 /* ---- per-kernel entry points (unit parity tests; same kernels the forwards launch) ---- */
 enum { GCV_A_PLAIN = 0, GCV_A_IM2COL3_POOL = 1, GCV_A_IM2COL3_S2 = 2 };
 enum { GCV_EPI_BIAS_ACT = 0, GCV_EPI_RESID = 1, GCV_EPI_POOL4 = 2, GCV_EPI_CONVT = 3, GCV_EPI_SPLITK = 4 };

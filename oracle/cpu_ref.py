@@ -144,11 +144,36 @@ def convnext_block(sd, p, x, store=True, mfma_taps=False):
     return _q(y + x) if store else y + x
 
 
-def convnext_tiny(sd, prefix, x, taps=None, store_out=True, launch=None):
+# --------------------------------------------------------------------------- taps in the HIP path's layouts
+# (include/genconvit_hip.h, gcv_tap_set): NHWC token rows, library names.  ``None`` = a tensor the HIP dispatch never
+# stores (the block output that goes straight into a LayerNorm-patchify epilogue).
+def _rows(x):
+    """(n, C, h, w) -> (n * h * w, C): tokens row-major, channels innermost."""
+    return x.permute(0, 2, 3, 1).reshape(-1, x.shape[1])
+
+
+def _patch_rows(x):
+    """(n, C, h, w) -> (n * (h // 2) * (w // 2), 4C), (dy, dx, c) innermost: the operand of the k = s = 2 downsample GEMM
+    (an odd last row / column takes no part)."""
+    n, c, h, w = x.shape
+    h2, w2 = h // 2, w // 2
+    x = x[:, :, :2 * h2, :2 * w2].reshape(n, c, h2, 2, w2, 2)
+    return x.permute(0, 2, 4, 3, 5, 1).reshape(n * h2 * w2, 4 * c)
+
+
+def _join_segments(taps, prefix, parts):
+    """Backbone taps of the passes of one network, concatenated in the library's segment order."""
+    for k in parts[0]:
+        vals = [part[k] for part in parts]
+        taps[f"{prefix}.{k}"] = None if any(v is None for v in vals) else torch.cat(vals)
+
+
+def convnext_tiny(sd, prefix, x, taps=None, store_out=True, launch=None, seg_taps=None):
     """timm 0.6.5 ``convnext_tiny`` forward: stem -> 4 stages -> (norm_pre=Identity)
     -> head(global avg pool, LayerNorm2d, flatten, fc).  Called by the reference at
     model/genconvit_ed.py:82-83 and model/genconvit_vae.py:111-112.  ``launch`` (16-bit restatement only): the geometry of
-    the HIP launch this pass is a segment of; default = the pass on its own (gcv_convnext_forward)."""
+    the HIP launch this pass is a segment of; default = the pass on its own (gcv_convnext_forward).  ``seg_taps``: filled
+    with this pass's backbone taps in the HIP path's layout (``stem``, ``s<i>.b<j>``, ``s<i>.down_in``, ``pool``)."""
     p = prefix
     if launch is None:
         launch = Launch(x.shape[0] * (x.shape[2] // 4) * (x.shape[3] // 4), x.shape[0])
@@ -156,24 +181,34 @@ def convnext_tiny(sd, prefix, x, taps=None, store_out=True, launch=None):
     x = _q(_ln2d(x, sd[p + "stem.1.weight"], sd[p + "stem.1.bias"], LN_EPS_CONVNEXT))
     if taps is not None:
         taps["stem"] = x
+    if seg_taps is not None:
+        seg_taps["stem"] = _rows(x)
     for i, depth in enumerate(CONVNEXT_DEPTHS):
         if i > 0:
             x = _q(_ln2d(x, sd[p + f"stages.{i}.downsample.0.weight"],
                          sd[p + f"stages.{i}.downsample.0.bias"], LN_EPS_CONVNEXT))
+            if seg_taps is not None:
+                seg_taps[f"s{i}.down_in"] = _patch_rows(x)
             x = _q(F.conv2d(x, _q(sd[p + f"stages.{i}.downsample.1.weight"]),
                             sd[p + f"stages.{i}.downsample.1.bias"], stride=2))
         for j in range(depth):
             # the last block of stages 0 and 1 hands its fp32 output to the stage boundary's LayerNorm (epilogue fusion in
             # csrc/fused_mlp_res.h — only for launches of 65536 tokens and more — and csrc/xs_mlp.h)
-            fused = (j == depth - 1 and (i == 1 or (i == 0 and launch.stage0_tokens >= FUSED_LNP_MIN_TOKENS))
+            # (16-bit storage only: the fp32 path has no fused MLP and stores every block)
+            fused = (_STORE is not None and j == depth - 1
+                     and (i == 1 or (i == 0 and launch.stage0_tokens >= FUSED_LNP_MIN_TOKENS))
                      and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0)
             mfma = i == 0 and x.shape[-1] == 56 and launch.dw_images * x.shape[2] >= DW_MFMA_MIN_IMAGE_ROWS
             x = convnext_block(sd, p + f"stages.{i}.blocks.{j}.", x, store=not fused, mfma_taps=mfma)
+            if seg_taps is not None:
+                seg_taps[f"s{i}.b{j}"] = None if fused else _rows(x)
         if taps is not None:
             taps[f"stage{i}"] = x
     x = x.mean((2, 3), keepdim=True)
     x = _q(_ln2d(x, sd[p + "head.norm.weight"], sd[p + "head.norm.bias"], LN_EPS_CONVNEXT))
     x = torch.flatten(x, 1)
+    if seg_taps is not None:
+        seg_taps["pool"] = x
     x = F.linear(x, _q(sd[p + "head.fc.weight"]), sd[p + "head.fc.bias"])
     return _q(x) if store_out else x       # (ED / VAE store it after the head's first activation)
 
@@ -187,12 +222,23 @@ def ed_forward(sd, images, taps=None):
     decimg = ed_decoder(sd, encimg, taps)
     # both passes are one 2B-image launch of one geometry (net_impl.h ed_forward)
     la = Launch(2 * images.shape[0] * (images.shape[2] // 4) * (images.shape[3] // 4), 2 * images.shape[0])
-    x1 = convnext_tiny(sd, "backbone.", decimg, store_out=False, launch=la)
-    x2 = convnext_tiny(sd, "backbone.", images, taps, store_out=False, launch=la)
+    # (seg_taps only when asked for: tests/golden/make_hf_golden.py substitutes convnext_tiny without it)
+    seg = ({}, {}) if taps is not None else None
+    kw = (lambda i: {"seg_taps": seg[i]}) if seg else (lambda i: {})
+    x1 = convnext_tiny(sd, "backbone.", decimg, store_out=False, launch=la, **kw(0))
+    x2 = convnext_tiny(sd, "backbone.", images, taps, store_out=False, launch=la, **kw(1))
     x = torch.cat((x1, x2), dim=1)
     if taps is not None:
         taps["ed_feat"] = x
     x = _q(F.gelu(x))
+    if taps is not None:   # the HIP path's taps (include/genconvit_hip.h)
+        for li in range(5):
+            taps[f"ed.e{li + 1}"] = _rows(taps[f"ed_enc{li}"])
+        for li in range(4):
+            taps[f"ed.d{li + 1}"] = _rows(taps[f"ed_dec{li}"])
+        taps["ed.rec"] = _rows(taps["ed_dec4"])
+        taps["ed.feat"] = x
+        _join_segments(taps, "ed.bb", seg)
     x = _q(F.gelu(F.linear(x, _q(sd["fc.weight"]), sd["fc.bias"])))
     return F.linear(x, sd["fc2.weight"], sd["fc2.bias"])
 
@@ -274,12 +320,25 @@ def vae_forward(sd, x, eps, as_written=False, want_kl=False, taps=None, merged=F
     # inside gcv_genconvit_forward they are the two segments of one launch (``merged``: csrc/net_impl.h vae_forward)
     B, t224, t112 = x.shape[0], (x.shape[2] // 4) * (x.shape[3] // 4), (x_hat.shape[2] // 4) * (x_hat.shape[3] // 4)
     la1 = Launch(B * (t224 + t112), B) if merged else None
-    x1 = convnext_tiny(sd, "convnext_backbone.", x, store_out=False, launch=la1)
-    x2 = convnext_tiny(sd, "convnext_backbone.", x_hat, store_out=False, launch=la1)
+    # (seg_taps only when asked for: tests/golden/make_hf_golden.py substitutes convnext_tiny without it)
+    seg = ({}, {}) if taps is not None else None
+    kw = (lambda i: {"seg_taps": seg[i]}) if seg else (lambda i: {})
+    x1 = convnext_tiny(sd, "convnext_backbone.", x, store_out=False, launch=la1, **kw(0))
+    x2 = convnext_tiny(sd, "convnext_backbone.", x_hat, store_out=False, launch=la1, **kw(1))
     f = torch.cat((x1, x2), dim=1)
     if taps is not None:
         taps["vae_feat"] = f
     f = _q(F.relu(f))
+    if taps is not None:   # the HIP path's taps (include/genconvit_hip.h)
+        for li in range(4):
+            taps[f"vae.v{li + 1}"] = _rows(taps[f"vae_enc{li}"])
+        taps["vae.mu"] = taps["vae_mu"]
+        taps["vae.z"] = taps["vae_z"].reshape(B, 256, 49).transpose(1, 2).reshape(B, -1)
+        for li in range(3):
+            taps[f"vae.d{li + 1}"] = _rows(taps[f"vae_dec{li}"])
+        taps["vae.xhat"] = _rows(taps["vae_dec3"])
+        taps["vae.feat"] = f
+        _join_segments(taps, "vae.bb", seg)
     f = _q(F.relu(F.linear(f, _q(sd["fc.weight"]), sd["fc.bias"])))
     logits = F.linear(f, sd["fc2.weight"], sd["fc2.bias"])
     return logits, resize224(x_hat), kl

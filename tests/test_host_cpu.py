@@ -431,3 +431,51 @@ def test_gelu_polynomial_in_the_kernels_is_what_the_fit_produces():
     rms = lambda y: float(np.sqrt(((y.astype(np.float64) - truth) ** 2).mean()))
     exact = rms(truth.astype(np.float32).astype(f16))
     assert exact < 2.2e-4 and rms(y32) < 2.6e-4 and rms(ypk) < 3.5e-4
+
+
+# ----------------------------------------------------------------------------- the stage-by-stage tap check catches tile bugs
+@pytest.mark.parametrize("dtype", ["float16", "bfloat16"])
+@pytest.mark.parametrize("stage,block,seg,tok", [(0, 1, 0, 0), (0, 2, 1, 1000), (2, 4, 1, 10)])
+def test_tap_check_catches_a_skipped_tile(stage, block, seg, tok, dtype, monkeypatch):
+    """The check of tests/test_taps_gpu.py, with its committed bounds, on the same-dtype oracle against the same oracle in
+    which one 32-token tile of image 0 of one backbone segment skips one ConvNeXt block (its output = its input): the first
+    tap out of bounds is that block's output, at that tile.  The unmodified oracle passes."""
+    import torch
+    from genconvit_amd import synth
+    from oracle import cpu_ref
+    from tests import taputil
+    from tests.conftest import synthetic_sd
+    torch.set_grad_enabled(False)
+    sd, x, dtype = synthetic_sd("ed"), synth.make_frames(2), getattr(torch, dtype)
+    lay, bounds = taputil.layout("ed", 2), taputil.BOUNDS[dtype]
+
+    def oracle():
+        taps = {}
+        with cpu_ref.storage_dtype(dtype):
+            cpu_ref.ed_forward(sd, x, taps)
+        return taps
+
+    clean = oracle()
+    assert not taputil.failures(taputil.compare(clean, oracle(), lay, bounds))
+
+    orig, calls = cpu_ref.convnext_block, []
+    target = f"backbone.stages.{stage}.blocks.{block}."
+
+    def skipping(sd_, p, xin, store=True, mfma_taps=False):
+        y = orig(sd_, p, xin, store=store, mfma_taps=mfma_taps)
+        if p == target:
+            calls.append(p)
+            if len(calls) == seg + 1:      # segment order of the ED token stream: [recon, orig]
+                y = y.clone()
+                c = y.shape[1]
+                y[0].view(c, -1)[:, tok:tok + 32] = xin[0].reshape(c, -1)[:, tok:tok + 32]
+        return y
+
+    monkeypatch.setattr(cpu_ref, "convnext_block", skipping)
+    bad = taputil.failures(taputil.compare(oracle(), clean, lay, bounds))
+    assert bad, "a skipped tile went unnoticed"
+    first = bad[0]
+    assert first["name"] == f"ed.bb.s{stage}.b{block}", first["where"]
+    assert (first["seg"], first["img"]) == (taputil.BB_SEGMENTS["ed"][seg][0], 0), first["where"]
+    assert tok <= first["tok"] < tok + 32, first["where"]
+    print(f"\n{dtype} skip of stage {stage} block {block}: {first['where']} (bound {first['bound']})")
