@@ -52,6 +52,10 @@ SIGNATURES = {
     "gcv_ed_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "gcv_vae_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gcv_genconvit_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "gcv_ed_explain": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gcv_vae_explain": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gcv_genconvit_explain": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p]),
     "gcv_comm_available": (c_int, []),
     "gcv_comm_count": (c_int, [c_void_p]),
     "gcv_comm_unique_id": (c_int, [c_void_p]),
@@ -302,6 +306,55 @@ class Handle:
                                        current_stream_ptr(x.device)), "gcv_vae_forward")
         return out, recon, mse, kl
 
+    # -- explain: Grad-CAM maps of the real / fake decision (include/genconvit_hip.h, gcv_*_explain) ---------------
+    def _target(self, target, B, device):
+        import torch
+        if target is None:
+            return None
+        t = torch.as_tensor(target, device=device).to(torch.int32).reshape(-1).contiguous()
+        if t.numel() == 1 and B != 1:
+            t = t.expand(B).contiguous()
+        if t.numel() != B:
+            raise GenConViTHipError(f"target must hold one class per frame ({B}), got {t.numel()}")
+        return t
+
+    def ed_explain(self, x, target=None, upsample=True):
+        """ED forward + Grad-CAM.  Returns (logits (B,2), cam (B,2,7,7) fp32 [reconstruction pass, original pass],
+        cam224 (B,224,224) of the original pass or None)."""
+        import torch
+        x = self._check_x(x)
+        B = x.shape[0]
+        t = self._target(target, B, x.device)
+        out = torch.empty((B, 2), dtype=torch.float32, device=x.device)
+        cam = torch.empty((B, 2, 7, 7), dtype=torch.float32, device=x.device)
+        up = torch.empty((B, 224, 224), dtype=torch.float32, device=x.device) if upsample else None
+        check(self.lib.gcv_ed_explain(self._h, x.data_ptr(), B, t.data_ptr() if t is not None else None, out.data_ptr(),
+                                      cam.data_ptr(), up.data_ptr() if up is not None else None,
+                                      current_stream_ptr(x.device)), "gcv_ed_explain")
+        return out, cam, up
+
+    def vae_explain(self, x, eps, target=None, upsample=True):
+        """VAE forward + Grad-CAM.  Returns (logits (B,2), cam (B,58) fp32 = [7x7 of x at 224 px, 3x3 of x_hat at 112 px],
+        cam224 (B,224,224) of x or None)."""
+        import torch
+        x = self._check_x(x)
+        B = x.shape[0]
+        eps = self._check_eps(eps, B)
+        t = self._target(target, B, x.device)
+        out = torch.empty((B, 2), dtype=torch.float32, device=x.device)
+        cam = torch.empty((B, 58), dtype=torch.float32, device=x.device)
+        up = torch.empty((B, 224, 224), dtype=torch.float32, device=x.device) if upsample else None
+        check(self.lib.gcv_vae_explain(self._h, x.data_ptr(), eps.data_ptr(), B, t.data_ptr() if t is not None else None,
+                                       out.data_ptr(), cam.data_ptr(), up.data_ptr() if up is not None else None,
+                                       current_stream_ptr(x.device)), "gcv_vae_explain")
+        return out, cam, up
+
+    def _check_eps(self, eps, B):
+        import torch
+        if not (torch.is_tensor(eps) and eps.is_cuda and eps.device.index == self.device_index and tuple(eps.shape) == (B, 12544)):
+            raise GenConViTHipError(f"eps must be a tensor of shape ({B},12544) on device {self.device_index}")
+        return eps.float().contiguous()
+
     def convnext_forward(self, which, x):
         import torch
         x = self._check_x(x, res=x.shape[-1])
@@ -343,6 +396,26 @@ def genconvit_forward(h_ed: "Handle", h_vae: "Handle", x, eps):
     check(h_ed.lib.gcv_genconvit_forward(h_ed._h, h_vae._h, x.data_ptr(), eps.data_ptr(), B, out.data_ptr(),
                                          current_stream_ptr(x.device)), "gcv_genconvit_forward")
     return out
+
+
+def genconvit_explain(h_ed: "Handle", h_vae: "Handle", x, eps, target=None, upsample=True):
+    """``genconvit_forward`` + Grad-CAM of both networks (``gcv_genconvit_explain``).  Returns (logits (2B,2),
+    cam_ed (B,2,7,7), cam_vae (B,58), cam224 (2B,224,224) or None) — cam224 rows in the logits' row order."""
+    import torch
+    x = h_ed._check_x(x)
+    B = x.shape[0]
+    if h_vae.device_index != h_ed.device_index or h_vae.dtype != h_ed.dtype:
+        raise GenConViTHipError("ED and VAE handles must share device and dtype")
+    eps = h_ed._check_eps(eps, B)
+    t = h_ed._target(target, B, x.device)
+    out = torch.empty((2 * B, 2), dtype=torch.float32, device=x.device)
+    cam = torch.empty((B * (98 + 58),), dtype=torch.float32, device=x.device)
+    up = torch.empty((2 * B, 224, 224), dtype=torch.float32, device=x.device) if upsample else None
+    check(h_ed.lib.gcv_genconvit_explain(h_ed._h, h_vae._h, x.data_ptr(), eps.data_ptr(), B,
+                                         t.data_ptr() if t is not None else None, out.data_ptr(), cam.data_ptr(),
+                                         up.data_ptr() if up is not None else None, current_stream_ptr(x.device)),
+          "gcv_genconvit_explain")
+    return out, cam[:B * 98].view(B, 2, 7, 7), cam[B * 98:].view(B, 58), up
 
 
 class Comm:

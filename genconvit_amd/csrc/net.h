@@ -54,6 +54,16 @@ struct Tap {
 };
 bool tap_name_known(const std::string& name);
 
+// ---- explain (gcv_*_explain, include/genconvit_hip.h) ---------------------------------------------------------------
+// Grad-CAM request of one network's forward: target (B) device ints or null (argmax), maps at cam + b * cam_ld (the
+// network's layout), cam224 (B, 224, 224) nullable.
+struct Explain {
+  const int* target = nullptr;
+  float* cam = nullptr;
+  int cam_ld = 0;
+  float* cam224 = nullptr;
+};
+
 // ---- abstract network (dtype erased) ----------------------------------------
 struct NetBase {
   int device = 0;
@@ -73,6 +83,9 @@ struct NetBase {
   virtual int ed_forward(const void* x, int B, float* logits, hipStream_t s) = 0;
   virtual int vae_forward(const void* x, const float* eps, int B, float* logits, void* recon224, float* mse,
                           float* kl, hipStream_t s) = 0;
+  // the forwards above followed by the Grad-CAM chain (cam.h) on the same stream(s); the logits are the forward's
+  virtual int ed_explain(const void* x, int B, float* logits, const Explain& ex, hipStream_t s) = 0;
+  virtual int vae_explain(const void* x, const float* eps, int B, float* logits, const Explain& ex, hipStream_t s) = 0;
   virtual int convnext_forward(int which /*0 ed backbone, 1 vae backbone*/, const void* x, int B, int res,
                                void* logits1000, hipStream_t s) = 0;
   virtual int swin_forward(const void* x, int B, void* logits1000, hipStream_t s) = 0;

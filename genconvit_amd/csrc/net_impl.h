@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "cam.h"
 #include "fused_mlp.h"
 #include "mlp_pair.h"
 #include "xs_mlp.h"
@@ -150,6 +151,8 @@ template <typename T> struct Seg {
   T* out;                   // backbone logits (n,1000) written at out + i*out_ld
   int out_ld;
   int act;
+  T* pre = nullptr;           // explain: the backbone logits before `act`, at pre + i*out_ld (else null)
+  const T** s3 = nullptr;     // explain: receives this segment's stage-3 tokens (the pass then keeps its buffers)
 };
 
 template <typename T> struct NetImpl : NetBase {
@@ -645,6 +648,8 @@ template <typename T> struct NetImpl : NetBase {
       ntot += segs[s].n;
     }
     GCV_REQUIRE(M * 384 < (int64_t)1 << 31, "token count too large for 32-bit GEMM indexing");
+    bool saving = false;
+    for (int s = 0; s < nseg; ++s) saving = saving || segs[s].s3;
     const size_t mk = arena.mark();
     T* X = arena.get<T>(M * 96);
     T* Y = arena.get<T>(M * 96);
@@ -812,6 +817,10 @@ template <typename T> struct NetImpl : NetBase {
         g.A = Pool + (int64_t)no * 768; g.lda = 768; g.Wt = w.head_fc_w; g.C = segs[s].out; g.ldc = segs[s].out_ld;
         g.bias = w.head_fc_b; g.M = segs[s].n; g.N = 1000; g.K = 768; g.act = segs[s].act; g.splitk = 1;
         GCV_TRY(gemm("cnx.head_fc", g, A_PLAIN, EPI_BIAS_ACT));
+        if (segs[s].pre) {
+          g.C = segs[s].pre; g.act = ACT_NONE;
+          GCV_TRY(gemm("explain.head_fc_pre", g, A_PLAIN, EPI_BIAS_ACT));
+        }
       }
       no += segs[s].n;
     }
@@ -821,12 +830,20 @@ template <typename T> struct NetImpl : NetBase {
       g.A = Pool; g.lda = 768; g.Wt = w.head_fc_w; g.C = segs[0].out; g.ldc = 1000;
       g.bias = w.head_fc_b; g.M = ntot; g.N = 1000; g.K = 768; g.act = segs[0].act; g.splitk = 1;
       GCV_TRY(gemm("cnx.head_fc", g, A_PLAIN, EPI_BIAS_ACT));
+      if (segs[0].pre) {
+        g.C = segs[0].pre; g.act = ACT_NONE;
+        GCV_TRY(gemm("explain.head_fc_pre", g, A_PLAIN, EPI_BIAS_ACT));
+      }
     }
-    if (!keep) arena.release(mk);
+    // explain: stage 3 has no LayerNorm-patchify epilogue, so its last block always leaves its output in X
+    for (int s = 0; s < nseg; ++s)
+      if (segs[s].s3) *segs[s].s3 = X + moff[s] * 768;
+    if (!keep && !saving) arena.release(mk);
     return 0;
   }
 
-  int run_head(const HeadW<T>& hw, const T* feat, int B, int act, float* logits) {
+  // keep_part (explain): receives the fc's split-K partials, which then stay allocated (the caller releases its own mark)
+  int run_head(const HeadW<T>& hw, const T* feat, int B, int act, float* logits, const float** keep_part = nullptr) {
     // fc (2000 -> 500) eight ways split-K into fp32 partials; their sum, the bias, the activation and fc2 (500 -> 2) are one
     // small kernel (round 4: as one GEMM the layer was a chain of 32 K tiles on eight workgroups, 37 us at 128 rows)
     const int SK = 8, KPS = 256;
@@ -839,7 +856,31 @@ template <typename T> struct NetImpl : NetBase {
     GCV_TRY(run("head.fc2", 2.0 * B * 2 * 500, 4.0 * (double)SK * B * 500, [&] {
       return launch_head_tail_splitk<T>(part, SK, hw.fc_b, act, hw.fc2_w, hw.fc2_b, logits, B, 500, cur);
     }));
-    arena.release(mk);
+    if (keep_part) *keep_part = part;
+    else arena.release(mk);
+    return 0;
+  }
+
+  // ------------------------------------------------------------ explain: Grad-CAM after the forward (cam.h)
+  // part: the head's fc partials (8 ways, run_head); bbpre: (B, 2000) backbone logits before the activation; s3[p]: stage-3
+  // tokens of pass p (hw[p] = side[p]^2 per image), their map at ex.cam + b * ex.cam_ld + off[p]
+  int explain_tail(const CnxW<T>& bw, const HeadW<T>& hw, int act, int B, const float* part, const T* bbpre,
+                   const float* logits, const T* const s3[2], const int hwp[2], const int side[2], const int off[2],
+                   int up_pass, const Explain& ex) {
+    float* dfeat = arena.get<float>((int64_t)B * 2000);
+    float* dpool = arena.get<float>((int64_t)B * 2 * 768);
+    if (!arena.dry && arena.overflow) { set_error("workspace arena too small"); return -6; }
+    HeadBwdArgs ha{part, 8, hw.fc_b, hw.fc2_w, logits, ex.target, hw.fc_w, bbpre, dfeat, B, act};
+    GCV_TRY(run("explain.head_bwd", 2.0 * B * 500 * 2000, sizeof(T) * (500.0 * 2000 + 2.0 * B * 2000) + 4.0 * B * (8 * 500 + 2000),
+                [&] { return launch_head_bwd<T>(ha, cur); }));
+    GCV_TRY(run("explain.bb_fc_bwd", 2.0 * 2 * B * 1000 * 768, sizeof(T) * 1000.0 * 768 + 4.0 * B * (2000 + 2 * 768),
+                [&] { return launch_bb_bwd<T>(dfeat, bw.head_fc_w, dpool, 2 * B, cur); }));
+    CamArgs ca{};
+    for (int q = 0; q < 2; ++q) { ca.A[q] = s3[q]; ca.hw[q] = hwp[q]; ca.side[q] = side[q]; ca.cam_off[q] = off[q]; }
+    ca.npass = 2; ca.cam_ld = ex.cam_ld; ca.up_pass = up_pass; ca.lnw = bw.head_lnw; ca.dpool = dpool;
+    ca.cam = ex.cam; ca.cam224 = ex.cam224; ca.eps = 1e-6f; ca.B = B;
+    GCV_TRY(run("explain.cam", 4.0 * B * (hwp[0] + hwp[1]) * 768, sizeof(T) * (double)B * (hwp[0] + hwp[1]) * 768 +
+                (ex.cam224 ? 4.0 * B * 224 * 224 : 0.0), [&] { return launch_cam<T>(ca, cur); }));
     return 0;
   }
 
@@ -850,11 +891,17 @@ template <typename T> struct NetImpl : NetBase {
   }
 
   // ------------------------------------------------------------ ED (model/genconvit_ed.py:77-88)
-  int ed_forward(const void* xv, int B, float* logits, hipStream_t s) override {
+  int ed_forward(const void* xv, int B, float* logits, hipStream_t s) override { return ed_run(xv, B, logits, s, nullptr); }
+  int ed_explain(const void* xv, int B, float* logits, const Explain& ex, hipStream_t s) override {
+    return ed_run(xv, B, logits, s, &ex);
+  }
+  // ex: explain request (null: the plain forward, whose launches it leaves untouched)
+  int ed_run(const void* xv, int B, float* logits, hipStream_t s, const Explain* ex) {
     if (!arena.dry) {
       GCV_REQUIRE(has_ed, "ED weights not loaded (gcv_load_ed)");
       GCV_TRY(check_batch(B));
       GCV_REQUIRE(xv && logits, "null input/output");
+      GCV_REQUIRE(!ex || ex->cam, "null map output");
     }
     cur = s;
     const T* x = (const T*)xv;
@@ -871,6 +918,7 @@ template <typename T> struct NetImpl : NetBase {
     T* d4 = arena.get<T>((int64_t)B * 112 * 112 * 16);
     T* rec = arena.get<T>((int64_t)B * 224 * 224 * 3);
     T* feat = arena.get<T>((int64_t)B * 2000);
+    T* bbpre = ex ? arena.get<T>((int64_t)B * 2000) : nullptr;
     if (!arena.dry && arena.overflow) { set_error("workspace arena too small"); return -6; }
 
     GCV_TRY(run("ed.enc1_conv3_relu_pool", 2.0 * B * 224 * 224 * 16 * 27,
@@ -913,9 +961,18 @@ template <typename T> struct NetImpl : NetBase {
     Seg<T> segs[2];
     segs[0] = Seg<T>{rec, (int64_t)224 * 224 * 3, 1, 224 * 3, 3, B, 224, 224, feat, 2000, ACT_GELU};
     segs[1] = Seg<T>{x, (int64_t)3 * 224 * 224, 224 * 224, 224, 1, B, 224, 224, feat + 1000, 2000, ACT_GELU};
+    const T* s3[2] = {nullptr, nullptr};
+    const float* head_part = nullptr;
+    if (ex)
+      for (int q = 0; q < 2; ++q) { segs[q].pre = bbpre + 1000 * q; segs[q].s3 = &s3[q]; }
     const TapPass tp{"ed", 2, 0, {B, B}, {224, 224}, {224, 224}};
     GCV_TRY(run_convnext(bb_ed, segs, 2, false, taps.empty() ? nullptr : &tp));
-    GCV_TRY(run_head(ed.head, feat, B, ACT_GELU, logits));
+    GCV_TRY(run_head(ed.head, feat, B, ACT_GELU, logits, ex ? &head_part : nullptr));
+    if (ex) {
+      // maps [b][pass][7][7], passes in cat order (reconstruction, original); the original frame's map is upsampled
+      const int hwp[2] = {49, 49}, side[2] = {7, 7}, off[2] = {0, 49};
+      GCV_TRY(explain_tail(bb_ed, ed.head, ACT_GELU, B, head_part, bbpre, logits, s3, hwp, side, off, 1, *ex));
+    }
     if (!taps.empty()) {
       const T* et[5] = {e1, e2, e3, e4, e5};
       const int64_t ee[5] = {112 * 112 * 16, 56 * 56 * 32, 28 * 28 * 64, 14 * 14 * 128, 7 * 7 * 256};
@@ -932,11 +989,19 @@ template <typename T> struct NetImpl : NetBase {
   // ------------------------------------------------------------ VAE (model/genconvit_vae.py:107-116)
   int vae_forward(const void* xv, const float* eps, int B, float* logits, void* recon224, float* mse, float* kl,
                   hipStream_t s) override {
+    return vae_run(xv, eps, B, logits, recon224, mse, kl, s, nullptr);
+  }
+  int vae_explain(const void* xv, const float* eps, int B, float* logits, const Explain& ex, hipStream_t s) override {
+    return vae_run(xv, eps, B, logits, nullptr, nullptr, nullptr, s, &ex);
+  }
+  int vae_run(const void* xv, const float* eps, int B, float* logits, void* recon224, float* mse, float* kl,
+              hipStream_t s, const Explain* ex) {
     if (!arena.dry) {
       GCV_REQUIRE(has_vae, "VAE weights not loaded (gcv_load_vae)");
       GCV_TRY(check_batch(B));
       GCV_REQUIRE(xv && eps && logits, "null input/eps/output");
       GCV_REQUIRE(!kl || vae.var_w, "KL requested but encoder.var weights were not loaded");
+      GCV_REQUIRE(!ex || ex->cam, "null map output");
     }
     cur = s;
     const T* x = (const T*)xv;
@@ -960,12 +1025,17 @@ template <typename T> struct NetImpl : NetBase {
     T* xhat = arena.get<T>((int64_t)B * 112 * 112 * 3);
     T* feat = arena.get<T>((int64_t)B * 2000);
     float* msepart = arena.get<float>((int64_t)B * 196);
+    T* bbpre = ex ? arena.get<T>((int64_t)B * 2000) : nullptr;
     if (!arena.dry && arena.overflow) { set_error("workspace arena too small"); return -6; }
 
     // cat order (genconvit_vae.py:113): [backbone(x @224), backbone(x_hat @112)], activation ReLU (:104)
     Seg<T> segs[2];
     segs[0] = Seg<T>{x, (int64_t)3 * 224 * 224, 224 * 224, 224, 1, B, 224, 224, feat, 2000, ACT_RELU};
     segs[1] = Seg<T>{xhat, (int64_t)112 * 112 * 3, 1, 112 * 3, 3, B, 112, 112, feat + 1000, 2000, ACT_RELU};
+    const T* s3[2] = {nullptr, nullptr};
+    const float* head_part = nullptr;
+    if (ex)
+      for (int q = 0; q < 2; ++q) { segs[q].pre = bbpre + 1000 * q; segs[q].s3 = &s3[q]; }
     const bool split = (vae_split_env >= 0 ? vae_split_env != 0 : !in_ensemble) && !prof.enabled;   // (profiled steps stay on one stream: serial per-kernel times)
     const TapPass tp0{"vae", 2, 0, {B, B}, {224, 112}, {224, 112}}, tp1{"vae", 2, 1, {B, B}, {224, 112}, {224, 112}};
     const bool tapping = !taps.empty();
@@ -1038,7 +1108,12 @@ template <typename T> struct NetImpl : NetBase {
       GCV_TRY(tap_net("vae.xhat", xhat, (size_t)B * 112 * 112 * 3 * sizeof(T)));
       GCV_TRY(tap_net("vae.feat", feat, (size_t)B * 2000 * sizeof(T)));
     }
-    GCV_TRY(run_head(vae.head, feat, B, ACT_RELU, logits));
+    GCV_TRY(run_head(vae.head, feat, B, ACT_RELU, logits, ex ? &head_part : nullptr));
+    if (ex) {
+      // maps [b][7 x 7 of the original frame, 3 x 3 of x_hat at 112]; the original frame's map is upsampled
+      const int hwp[2] = {49, 9}, side[2] = {7, 3}, off[2] = {0, 49};
+      GCV_TRY(explain_tail(bb_vae, vae.head, ACT_RELU, B, head_part, bbpre, logits, s3, hwp, side, off, 0, *ex));
+    }
     if (recon224 || mse) {
       GCV_TRY(run("vae.resize_mse", 30.0 * B * 224 * 224, sizeof(T) * (double)B * (3 * 112 * 112 + 6 * 224 * 224), [&] {
         return launch_resize_mse<T>(xhat, x, (T*)recon224, msepart, mse, B, cur);
@@ -1071,10 +1146,12 @@ template <typename T> struct NetImpl : NetBase {
     GCV_CHECK_HIP(hipSetDevice(device));
     arena.dry = true;
     arena.off = arena.peak = 0;
-    int rc = ed_forward(nullptr, max_batch, nullptr, nullptr);
-    if (!rc) rc = vae_forward(nullptr, nullptr, max_batch, nullptr, nullptr, nullptr, nullptr, nullptr);
+    // the explain variants keep the head's inputs alive on top of the forward's buffers: the arena holds them too
+    const Explain ex;
+    int rc = ed_run(nullptr, max_batch, nullptr, nullptr, &ex);
+    if (!rc) rc = vae_run(nullptr, nullptr, max_batch, nullptr, nullptr, nullptr, nullptr, nullptr, &ex);
     in_ensemble = true;                    // both VAE schedules (see vae_split_env): the arena holds the larger footprint
-    if (!rc) rc = vae_forward(nullptr, nullptr, max_batch, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (!rc) rc = vae_run(nullptr, nullptr, max_batch, nullptr, nullptr, nullptr, nullptr, nullptr, &ex);
     in_ensemble = false;
     if (!rc) rc = swin_forward(nullptr, max_batch, nullptr, nullptr);
     arena.dry = false;

@@ -142,6 +142,14 @@ class HipModule(nn.Module):
         self._max_batch = min(max(int(max_batch), 1), MAX_HANDLE_BATCH)
         return self
 
+    @staticmethod
+    def _target_chunk(target, lo, hi):
+        """Per-frame targets of frames [lo, hi): None / a scalar class stay as they are, a per-frame sequence is sliced."""
+        if target is None:
+            return None
+        t = torch.as_tensor(target)
+        return t if t.dim() == 0 or t.numel() == 1 else t.reshape(-1)[lo:hi]
+
     def _prep_input(self, x):
         device, dtype = self._param_device_dtype()
         if x.device != device:

@@ -26,6 +26,13 @@ def _read_checkpoint(name):
     return ckpt["state_dict"] if isinstance(ckpt, dict) and "state_dict" in ckpt else ckpt
 
 
+def normalize_cams(cams):
+    """Scale each map of ``cams`` (..., H, W) to [0, 1] by its own min and max (a constant map becomes zeros)."""
+    flat = cams.flatten(-2)
+    lo, hi = flat.amin(-1, keepdim=True), flat.amax(-1, keepdim=True)
+    return ((flat - lo) / (hi - lo).clamp_min(1e-12)).view_as(cams)
+
+
 class GenConViT(nn.Module):
     concurrent = True        # run ED and VAE on two streams when net is the ensemble (class-level switch)
     # The HIP path always computes fp32 logits.  The reference returns them in the model's dtype (model/genconvit.py:59-61:
@@ -80,6 +87,47 @@ class GenConViT(nn.Module):
             m = self.model_ed if self.net != "vae" else self.model_vae
             out = out.to(m._param_device_dtype()[1])
         return out
+
+    @torch.no_grad()
+    def explain(self, x, eps=None, target=None, upsample=True):
+        """``forward`` plus Grad-CAM evidence maps of every frame's real / fake decision at the last ConvNeXt stage of each
+        network (include/genconvit_hip.h, gcv_*_explain).  ``target``: None (each frame's argmax, per network), a class
+        (0 / 1) or one class per frame.  Returns ``(logits, cams)``; the logits are ``forward``'s (fp32, same rows), and
+        ``cams`` holds fp32 maps, not normalised (see ``normalize_cams``):
+          'ed'        (B,2,7,7)  ED passes [reconstruction, original]          (net 'ed' and 'genconvit')
+          'vae'       (B,7,7)    VAE backbone(x)                                (net 'vae' and 'genconvit')
+          'vae_xhat'  (B,3,3)    VAE backbone(x_hat) at 112 px
+          'upsampled' (rows of the logits, 224, 224): each row's original-frame map resized like
+                      F.interpolate(mode='bilinear', align_corners=False), or None when ``upsample`` is False"""
+        if self.net == "ed":
+            return self.model_ed.explain(x, target=target, upsample=upsample)
+        if self.net == "vae":
+            return self.model_vae.explain(x, eps=eps, target=target, upsample=upsample)
+        if not (self.concurrent and next(self.model_ed.parameters()).is_cuda):
+            le, ce = self.model_ed.explain(x, target=target, upsample=upsample)
+            lv, cv = self.model_vae.explain(x, eps=eps, target=target, upsample=upsample)
+            up = torch.cat((ce["upsampled"], cv["upsampled"])) if upsample else None
+            return torch.cat((le, lv)), {"ed": ce["ed"], "vae": cv["vae"], "vae_xhat": cv["vae_xhat"], "upsampled": up}
+        x = self.model_ed._prep_input(x)
+        B = x.shape[0]
+        if B == 0:
+            z = lambda *s: torch.empty(s, dtype=torch.float32, device=x.device)
+            return z(0, 2), {"ed": z(0, 2, 7, 7), "vae": z(0, 7, 7), "vae_xhat": z(0, 3, 3),
+                             "upsampled": z(0, 224, 224) if upsample else None}
+        if eps is None:
+            eps = torch.randn((B, self.model_vae.latent_dims), dtype=torch.float32, device=x.device,
+                              generator=self.model_vae._generator)
+        else:
+            eps = eps.to(device=x.device, dtype=torch.float32)
+        parts = [_lib.genconvit_explain(self.model_ed._get_handle(hi - lo), self.model_vae._get_handle(hi - lo), x[lo:hi],
+                                        eps[lo:hi], self.model_ed._target_chunk(target, lo, hi), upsample)
+                 for lo, hi in self.model_ed._chunks(B)]
+        half = lambda t: (t[:t.shape[0] // 2], t[t.shape[0] // 2:])
+        logits = torch.cat([half(p[0])[0] for p in parts] + [half(p[0])[1] for p in parts])
+        vae = torch.cat([p[2] for p in parts])
+        up = torch.cat([half(p[3])[0] for p in parts] + [half(p[3])[1] for p in parts]) if upsample else None
+        return logits, {"ed": torch.cat([p[1] for p in parts]), "vae": vae[:, :49].reshape(B, 7, 7),
+                        "vae_xhat": vae[:, 49:].reshape(B, 3, 3), "upsampled": up}
 
     def _forward_fp32(self, x, eps=None):
         if self.net == "ed":

@@ -38,6 +38,26 @@ class GenConViTED(HipModule):
             return torch.cat([self._get_handle(hi - lo).ed_forward(images[lo:hi]) for lo, hi in self._chunks(images.shape[0])])
         return self._get_handle(images.shape[0]).ed_forward(images)
 
+    @torch.no_grad()
+    def explain(self, images, eps=None, target=None, upsample=True):
+        """Forward + Grad-CAM of the real / fake decision at the last ConvNeXt stage (``gcv_ed_explain``).  ``target``:
+        None (each frame's argmax), a class (0 / 1) or one class per frame.  Returns ``(logits, cams)``: the logits equal
+        ``forward``'s; ``cams['ed']`` (B,2,7,7) fp32 maps of the [reconstruction, original] passes (not normalised) and
+        ``cams['upsampled']`` (B,224,224) the original pass's map resized like ``F.interpolate(mode='bilinear')``, or None.
+        ``eps`` is accepted for a signature shared with the VAE and ignored."""
+        images = self._prep_input(images)
+        B = images.shape[0]
+        if B > 512:
+            parts = [self._get_handle(hi - lo).ed_explain(images[lo:hi], self._target_chunk(target, lo, hi), upsample)
+                     for lo, hi in self._chunks(B)]
+        else:
+            parts = [self._get_handle(B).ed_explain(images, target, upsample)] if B else []
+        if not parts:
+            z = lambda *s: torch.empty(s, dtype=torch.float32, device=images.device)
+            return z(0, 2), {"ed": z(0, 2, 7, 7), "upsampled": z(0, 224, 224) if upsample else None}
+        cat = lambda i: torch.cat([p[i] for p in parts]) if parts[0][i] is not None else None
+        return cat(0), {"ed": cat(1), "upsampled": cat(2)}
+
     def backbone_forward(self, images):
         """ConvNeXt-T alone (timm ``convnext_tiny`` forward, call site genconvit_ed.py:82-83)."""
         images = self._prep_input(images)

@@ -15,7 +15,7 @@ import torch
 
 from .. import _lib, synth
 from .config import load_config
-from .genconvit import GenConViT
+from .genconvit import GenConViT, normalize_cams
 
 device = "cuda" if torch.cuda.is_available() else "cpu"
 
@@ -58,6 +58,19 @@ def pred_vid(df, model):
         if df.device != p.device:
             df = df.to(p.device)
         return max_prediction_value(torch.sigmoid(model(df).squeeze()))
+
+
+def pred_vid_explain(df, model, target=None):
+    """``pred_vid`` with evidence maps: returns ``((y, y_val), maps)`` where ``(y, y_val)`` is what ``pred_vid(df, model)``
+    returns for the same logits and ``maps`` is the model's per-frame Grad-CAM maps upsampled to 224 x 224 and scaled to
+    [0, 1] per map, in the logits' row order ((2n, 224, 224) for the ensemble: ED rows, then VAE rows).  ``target``: as in
+    ``GenConViT.explain`` (default: each frame's own decision)."""
+    p = next(model.parameters())
+    if df.device != p.device:
+        df = df.to(p.device)
+    logits, cams = model.explain(df, target=target, upsample=True)
+    out = logits.to(p.dtype) if getattr(model, "reference_logits_dtype", False) else logits
+    return max_prediction_value(torch.sigmoid(out.squeeze())), normalize_cams(cams["upsampled"])
 
 
 def pred_vids(dfs, model, max_batch=128):

@@ -93,6 +93,36 @@ int gcv_vae_forward(gcv_handle* h, const void* x_nchw, const float* eps, int bat
 int gcv_genconvit_forward(gcv_handle* h_ed, gcv_handle* h_vae, const void* x_nchw, const float* eps, int batch,
                           float* logits_2Bx2, gcv_stream stream);
 
+/* ---- explain: Grad-CAM evidence maps of each frame's real / fake decision (new capability) ----
+ * Each entry runs the corresponding forward above — the same launches, so `logits` are bit-identical to the forward's on
+ * the same input (and eps) — and then, on the same stream(s), the backward of the network's head from the target logit
+ * to the last ConvNeXt stage: fc2^T, the activation mask (GELU' for ED, ReLU' for the VAE, at the hidden layer and at the
+ * backbone logits, using the forward's pre-activations), fc^T (500 -> 2000), the backbone fc^T (1000 -> 768) and the
+ * pooled LayerNorm2d's backward.  Average pooling makes d logit / d A_c(h, w) the same vector g (768, fp32) at every
+ * position of the stage-3 map A of a pass, so the Grad-CAM weights are g itself and
+ *   CAM(h, w) = ReLU(sum_c g_c A_c(h, w))       (fp32, not normalised: callers choose their own scaling)
+ * over the stored stage-3 tokens (tap <net>.bb.s3.b2).  The CAM of the reconstruction passes stops at the backbone: it is
+ * the map over the reconstructed image, not propagated through the encoder / decoder.
+ *   target   nullable (B) int32 device array: class 0 or 1 per frame (a non-zero value means 1); null = the argmax of each
+ *            frame's logits (ties -> class 0)
+ *   cam_raw  fp32, not null.  ED : [B][2][7][7] — pass 0 = backbone(reconstruction), pass 1 = backbone(x) (the reference's
+ *                                  x1, x2 order, model/genconvit_ed.py:82-83)
+ *                             VAE: [B][7*7 + 3*3] — backbone(x) at 224 px, then backbone(x_hat) at 112 px
+ *   cam224   nullable fp32 (B, 224, 224): F.interpolate(map of backbone(x), size=(224, 224), mode='bilinear',
+ *            align_corners=False)
+ * The workspace arena created with the handle holds the saved tensors at every batch up to max_batch: no allocation, copy
+ * or synchronisation happens inside a call. */
+int gcv_ed_explain(gcv_handle* h, const void* x_nchw, int batch, const int* target, float* logits, float* cam_raw,
+                   float* cam224, gcv_stream stream);
+int gcv_vae_explain(gcv_handle* h, const void* x_nchw, const float* eps, int batch, const int* target, float* logits,
+                    float* cam_raw, float* cam224, gcv_stream stream);
+/* Both networks as in gcv_genconvit_forward (two internal streams, the same schedule), with their maps in the (2B) row
+ * order of the logits: cam_raw = ED block (B x 98 floats, layout above) followed by the VAE block (B x 58 floats);
+ * cam224 (2B, 224, 224): rows 0..B-1 the ED maps of x, rows B..2B-1 the VAE's.  `target` (B) applies to both networks;
+ * null = each network's own argmax. */
+int gcv_genconvit_explain(gcv_handle* h_ed, gcv_handle* h_vae, const void* x_nchw, const float* eps, int batch,
+                          const int* target, float* logits_2Bx2, float* cam_raw, float* cam224, gcv_stream stream);
+
 /* timm convnext_tiny forward alone (call sites model/genconvit_ed.py:82-83,
  * model/genconvit_vae.py:111-112): which = 0 the ED backbone, 1 the VAE backbone;
  * x (B,3,res,res) -> logits1000 (B,1000) in the handle dtype. */
