@@ -12,10 +12,8 @@
 #include <sstream>
 #include <vector>
 
-#include "fused_mlp.h"
+#include "cnx_mlp.h"
 #include "gemm.h"
-#include "mlp_pair.h"
-#include "xs_mlp.h"
 #include "kernels.h"
 #include "net.h"
 
@@ -162,50 +160,57 @@ static int to_map(const gcv_tensor_desc* w, int n, TensorMap& m) {
   return 0;
 }
 
-// ConvNeXt MLP (16-bit only): W1 is given as (4C, C) T, W2 as plain (C, 4C) fp32 on the device; both are packed here.
-// C = 96 / 192: the fused kernels; C = 384: the pw1 / pw2 kernel pair with its fragment-major hidden tensor.
-// iters == 0: one launch.  iters > 0 (gcv_k_fused_mlp_timed): the weights are packed once, then `iters` launches are timed
-// with HIP events on the stream; ms[0] = average of the whole MLP, ms[1] / ms[2] = pw1 / pw2 of the C = 384 pair (else 0).
-// lnp != nullptr (gcv_k_fused_mlp_lnp): the stage boundary's LayerNorm2d + 2x2 space-to-depth in the epilogue (C = 96 at
-// M >= 65536 tokens, C = 192), `out` is then the patchified (M/4, 4C) tensor.
-struct LnpSpec {
-  const float *w, *b;
-  float eps;
-  int nseg;
-  const int *tok0, *hw, *wd, *out0;
+// launch_cnx_mlp's launcher for the test entry: the kernels of every run() tag, or of tag `only`
+template <typename T> struct MlpTestRunner {
+  hipStream_t s;
+  const char* only;
+  template <class F> int run(const char* tag, double, double, F&& f) { return only && std::strcmp(tag, only) ? 0 : f(); }
+  int gemm(const char*, const GemmArgs& g, int a_mode, int epi) { return launch_gemm<T>(g, a_mode, epi, s); }
 };
-template <typename A> static void set_lnp(A& a, const LnpSpec* l) {
-  if (!l) return;
-  a.lnp_w = l->w; a.lnp_b = l->b; a.lnp_eps = l->eps; a.lnp_nseg = l->nseg;
-  for (int i = 0; i < l->nseg && i < 4; ++i) {
-    a.lnp_tok0[i] = l->tok0[i]; a.lnp_hw[i] = l->hw[i]; a.lnp_wd[i] = l->wd[i]; a.lnp_out0[i] = l->out0[i];
-  }
-}
+// ConvNeXt MLP (16-bit only) as the network runs it (cnx_mlp.h): W1 is given as (4C, C) T, W2 as plain (C, 4C) fp32 on the
+// device; both are packed here for the block's kind.  iters == 0: one launch.  iters > 0 (gcv_k_fused_mlp_timed): the
+// weights are packed once, then `iters` launches are timed with HIP events on the stream; ms[0] = average of the whole MLP,
+// ms[1] / ms[2] = pw1 / pw2 of the C = 384 pair (else 0).  lnp (gcv_k_fused_mlp_lnp): the stage boundary's LayerNorm2d +
+// 2x2 space-to-depth in the epilogue, `out` is then the patchified (M/4, 4C) tensor.
 template <typename T>
 static int k_mlp_dispatch(int C, const void* x, const void* w1, const float* b1, const float* w2_f32, const float* b2,
                           const float* gamma, const void* resid, void* out, int M, hipStream_t s, int iters = 0,
                           float* ms = nullptr, const LnpSpec* lnp = nullptr) {
-  struct DevBuf {                                  // freed on every exit path (after the stream has drained)
-    void* p = nullptr;
+  struct Bufs {                                    // freed on every exit path (after the stream has drained)
     hipStream_t s;
-    explicit DevBuf(hipStream_t st) : s(st) {}
-    ~DevBuf() { if (p) { (void)hipStreamSynchronize(s); (void)hipFree(p); } }
+    std::vector<void*> p;
+    ~Bufs() { (void)hipStreamSynchronize(s); for (void* q : p) (void)hipFree(q); }
+  } bufs{s, {}};
+  auto alloc = [&](size_t n) -> void* {
+    void* q = nullptr;
+    if (hipMalloc(&q, n) != hipSuccess) return nullptr;
+    bufs.p.push_back(q);
+    return q;
   };
   struct Ev {
     hipEvent_t e = nullptr;
     ~Ev() { if (e) (void)hipEventDestroy(e); }
   };
-  DevBuf w2c(s), w1f(s), hid(s);
-  GCV_CHECK_HIP(hipMalloc(&w2c.p, (size_t)4 * C * C * 2));
-  // timed(f, &avg): warm-up launch, then `iters` launches between two events
-  auto timed = [&](auto&& f, float* avg) -> int {
-    if (iters <= 0) return f();
+  CnxMlpW<T> w;
+  w.kind = mlp_kind(sizeof(T), C);
+  GCV_REQUIRE(w.kind != MlpKind::Gemm, "the fused MLP kernels cover C = 96, 192 and 384");
+  w.w1 = (const T*)w1; w.b1 = b1; w.b2 = b2; w.gamma = gamma;
+  GCV_TRY(pack_cnx_mlp<T>(w, C, w2_f32, alloc, s));
+  T* hidden = w.kind == MlpKind::Pair384 ? (T*)alloc(mlp_pair_hidden_bytes(M, C)) : nullptr;
+  GCV_REQUIRE(hidden || w.kind != MlpKind::Pair384, "hipMalloc of the hidden tensor");
+  auto launch = [&](const char* only) {
+    MlpTestRunner<T> r{s, only};
+    return launch_cnx_mlp<T>(r, w, C, (const T*)x, (const T*)resid, (T*)out, hidden, M, lnp, s);
+  };
+  // timed(only, &avg): warm-up launch, then `iters` launches between two events
+  auto timed = [&](const char* only, float* avg) -> int {
+    if (iters <= 0) return launch(only);
     Ev e0, e1;
     GCV_CHECK_HIP(hipEventCreate(&e0.e));
     GCV_CHECK_HIP(hipEventCreate(&e1.e));
-    GCV_TRY(f());
+    GCV_TRY(launch(only));
     GCV_CHECK_HIP(hipEventRecord(e0.e, s));
-    for (int i = 0; i < iters; ++i) GCV_TRY(f());
+    for (int i = 0; i < iters; ++i) GCV_TRY(launch(only));
     GCV_CHECK_HIP(hipEventRecord(e1.e, s));
     GCV_CHECK_HIP(hipEventSynchronize(e1.e));
     float t = 0.0f;
@@ -214,45 +219,33 @@ static int k_mlp_dispatch(int C, const void* x, const void* w1, const float* b1,
     return 0;
   };
   if (ms) ms[0] = ms[1] = ms[2] = 0.0f;
-  if (lnp) {
-    GCV_REQUIRE(lnp->nseg >= 1 && lnp->nseg <= 4 && lnp->w && lnp->b && lnp->tok0 && lnp->hw && lnp->wd && lnp->out0,
-                "fused MLP with LN-patchify epilogue: 1..4 segments and their tables");
-    GCV_REQUIRE((C == 96 && fused_mlp_res_applies(C, M)) || xs_mlp_default(C),
-                "the LN-patchify epilogue exists at C = 96 (M >= 65536 tokens) and C = 192");
-    int64_t covered = 0;
-    for (int i = 0; i < lnp->nseg; ++i) {
-      const int end = i + 1 < lnp->nseg ? lnp->tok0[i + 1] : M;
-      const int wd = lnp->wd[i], hw = lnp->hw[i];
-      GCV_REQUIRE(wd > 0 && hw > 0 && hw % wd == 0 && wd % 2 == 0 && (hw / wd) % 2 == 0 && lnp->tok0[i] == covered &&
-                      end > lnp->tok0[i] && (end - lnp->tok0[i]) % hw == 0 && lnp->out0[i] * 4 == lnp->tok0[i],
-                  "LN-patchify segments: contiguous whole images with even height and width");
-      covered = end;
-    }
+  if (iters > 0 && w.kind == MlpKind::Pair384) {
+    GCV_TRY(timed("cnx.pw1_gelu", ms + 1));         // (gcv_k_fused_mlp_timed requires ms)
+    GCV_TRY(timed("cnx.pw2_scale_res", ms + 2));
   }
-  if (mlp_pair_supported(C)) {
-    GCV_CHECK_HIP(hipMalloc(&w1f.p, (size_t)4 * C * C * 2));
-    GCV_CHECK_HIP(hipMalloc(&hid.p, mlp_pair_hidden_bytes(M, C)));
-    GCV_TRY((launch_pack_w1_frag<T, T>((const T*)w1, (T*)w1f.p, C, s)));
-    GCV_TRY((launch_pack_w2_frag<T, float>(w2_f32, gamma, (T*)w2c.p, C, s)));
-    MlpPairArgs a{x, w1f.p, b1, w2c.p, b2, gamma, resid, out, hid.p, M};
-    if (iters > 0) {
-      GCV_TRY(timed([&] { return launch_xs_pw1<T>(a, C, s); }, ms ? ms + 1 : nullptr));
-      GCV_TRY(timed([&] { return launch_pw2f<T>(a, C, s); }, ms ? ms + 2 : nullptr));
-    }
-    return timed([&] { return launch_mlp_pair<T>(a, C, s); }, ms);
+  return timed(nullptr, ms);
+}
+
+// the caller's segment tables of gcv_k_fused_mlp_lnp -> the network's LnpSpec (lnp_plan)
+static int lnp_from_tables(LnpSpec& l, int C, int M, const float* w, const float* b, float eps, int nseg, const int* tok0,
+                           const int* hw, const int* wd, const int* out0) {
+  GCV_REQUIRE(nseg >= 1 && nseg <= 4 && w && b && tok0 && hw && wd && out0,
+              "fused MLP with LN-patchify epilogue: 1..4 segments and their tables");
+  int n[4], h[4];
+  int64_t covered = 0;
+  for (int i = 0; i < nseg; ++i) {
+    const int end = i + 1 < nseg ? tok0[i + 1] : M;
+    GCV_REQUIRE(wd[i] > 0 && hw[i] > 0 && hw[i] % wd[i] == 0 && wd[i] % 2 == 0 && (hw[i] / wd[i]) % 2 == 0 &&
+                    tok0[i] == covered && end > tok0[i] && (end - tok0[i]) % hw[i] == 0 && out0[i] * 4 == tok0[i],
+                "LN-patchify segments: contiguous whole images with even height and width");
+    n[i] = (end - tok0[i]) / hw[i];
+    h[i] = hw[i] / wd[i];
+    covered = end;
   }
-  static const bool legacy = exp_env("GCV_MLP_LEGACY") != nullptr;   // A/B: the round-2 fused kernels
-  if (xs_mlp_default(C) && !legacy) {
-    GCV_CHECK_HIP(hipMalloc(&w1f.p, xs_mlp_packed_elems(C) * sizeof(T)));
-    GCV_TRY((launch_pack_xs_mlp<T, float>((const T*)w1, w2_f32, (T*)w1f.p, C, s)));
-    XsMlpArgs xa{x, w1f.p, b1, b2, gamma, resid, out, M};
-    set_lnp(xa, lnp);
-    return timed([&] { return launch_xs_mlp<T>(xa, C, s); }, ms);
-  }
-  MlpArgs a{x, w1, b1, w2c.p, b2, gamma, resid, out, M};
-  set_lnp(a, lnp);
-  GCV_TRY(launch_pack_w2_chunks<T>(w2_f32, (T*)w2c.p, C, s));
-  return timed([&] { return launch_fused_mlp<T>(a, C, s); }, ms);
+  GCV_REQUIRE(lnp_plan(l, mlp_kind(2, C), C, M, nseg, n, h, wd),
+              "the LN-patchify epilogue exists at C = 96 (M >= 65536 tokens) and C = 192");
+  l.w = w; l.b = b; l.eps = eps;
+  return 0;
 }
 
 extern "C" {
@@ -681,7 +674,8 @@ int gcv_k_fused_mlp_lnp(int dtype, int C, const void* x, const void* w1, const f
                         float eps, int nseg, const int* tok0, const int* hw, const int* wd, const int* out0, void* out, int M,
                         gcv_stream s) {
   GCV_REQUIRE(dtype == GCV_F16 || dtype == GCV_BF16, "the MLP kernels are built for 16-bit storage");
-  const LnpSpec l{ln_w, ln_b, eps, nseg, tok0, hw, wd, out0};
+  LnpSpec l;
+  GCV_TRY(lnp_from_tables(l, C, M, ln_w, ln_b, eps, nseg, tok0, hw, wd, out0));
   if (dtype == GCV_F16)
     return k_mlp_dispatch<half_t>(C, x, w1, b1, w2_f32, b2, gamma, resid, out, M, (hipStream_t)s, 0, nullptr, &l);
   return k_mlp_dispatch<bf16_t>(C, x, w1, b1, w2_f32, b2, gamma, resid, out, M, (hipStream_t)s, 0, nullptr, &l);

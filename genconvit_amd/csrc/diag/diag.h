@@ -1,8 +1,7 @@
 // Diagnostic switches of the kernels, in one place.  A product build (the Makefile's) defines none of them: every
 // GCV_*_ABLATE mask is 0, every *_STAMP(...) expands to nothing and no stamp buffer or reader exists in the library.
 // Only the variant builds of profiles/build_variant.sh (-DGCV_XS_STAMPS=1, -DGCV_P2_ABLATE=2, -DGCV_EXPERIMENTS, ...) turn
-// anything on; their outputs are read by profiles/*_stamps.py.  Also here: diag/fused_mlp_ring.h, the LDS-DMA ring MLP that
-// was measured slower twice and is compiled in GCV_EXPERIMENTS builds only.
+// anything on; their outputs are read by profiles/*_stamps.py.
 #pragma once
 
 // ---- ablation masks (bit set = that part of the kernel is compiled out; results are then wrong on purpose)
@@ -27,14 +26,6 @@
 #ifndef GCV_DWM_ABLATE
 #define GCV_DWM_ABLATE 0   // dwconv7_ln_mfma_kernel: 1 no MFMAs, 2 no LayerNorm (reads, math, stores), 4 no operand gathers
 #endif
-// ---- schedule variants of xs_pw1_kernel that were measured against the product's (mlp_pair.h)
-#ifndef GCV_XS_PAIR
-#define GCV_XS_PAIR 1      // two hidden chunks per barrier (0: one, the first version of the kernel)
-#endif
-#ifndef GCV_XS_SGB
-#define GCV_XS_SGB 1       // 1 = 1 MFMA : 1 LDS read : n vector instructions (product); 0 / 2 / 3 diagnostics, see sub_block
-#endif
-
 // ---- s_memtime stamps: <FAMILY>_STAMP(...) writes the cycle counter of chosen waves of the first workgroups into a
 // __device__ buffer nothing else reads; gcv_debug_read_*_stamps copies it out (exported by the family's f16 TU).
 #ifndef GCV_XS_STAMPS

@@ -94,7 +94,6 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) xs_pw1_kernel(const MlpPairAr
   constexpr int NPC = SLOT / 1024;                         // DMA pieces per chunk
   static_assert(NPC % NW == 0, "pieces per wave");
   constexpr int PPW = NPC / NW;
-  constexpr int WAITN = (D - 2) * PPW;                     // see the count at step()
   constexpr int NKC = 4 * C / 32;                          // hidden chunks in all
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -153,7 +152,7 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) xs_pw1_kernel(const MlpPairAr
   //  86 us against 80 us at 256 images.  An LDS-DMA instruction costs its SIMD the same issue time wherever it sits.)
   XS_STAMP(0);
 #pragma unroll
-  for (int s = 0; s < (GCV_XS_PAIR ? D - 2 : D - 1); ++s) issue();
+  for (int s = 0; s < D - 2; ++s) issue();
 
   // hidden tensor as a buffer: blocks of token blocks >= ntb are out of range and their stores are dropped
   const __amdgpu_buffer_rsrc_t rsh =
@@ -229,7 +228,6 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) xs_pw1_kernel(const MlpPairAr
       if (j % 3 == 0 && !(GCV_XS_ABLATE & 1)) gelu_a(cur, j / 3);
       if (j % 3 == 1 && !(GCV_XS_ABLATE & 1)) gelu_b();
       if (j % 3 == 2) gelu_c(cur, j / 3, kc - 1);
-#if GCV_XS_SGB == 1
       if (j == 0) __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);    // vector work first: the first fragments are
 #pragma unroll                                                          // still on their way from LDS
       for (int i = 0; i < 4; ++i) {
@@ -237,15 +235,6 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) xs_pw1_kernel(const MlpPairAr
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x002, j == 0 ? 6 : 9, 0);
       }
-#elif GCV_XS_SGB == 2                                                   // diagnostic: the four MFMAs, then the vector work
-      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-      __builtin_amdgcn_sched_group_barrier(0x002, 40, 0);
-#elif GCV_XS_SGB == 3                                                   // diagnostic: the vector work, then the four MFMAs
-      __builtin_amdgcn_sched_group_barrier(0x002, 40, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-#endif
     }
     __builtin_amdgcn_sched_barrier(0);
     if (gelu_prev && (kc == 10 || kc == 11)) XS_STAMP(32 + 8 * (kc - 10) + j);
@@ -276,7 +265,6 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) xs_pw1_kernel(const MlpPairAr
     GCV_XS_SUBBLOCKS(cur, nxt, kc, decltype(gc)::value);
   };
   f32x16 accA, accB;
-#if GCV_XS_PAIR
   // TWO chunks per barrier (nch is even: launcher): at the head of pair (kc, kc+1) the ring holds chunks kc .. kc+3, the
   // slots of kc-2 and kc-1 are free; both needed chunks have landed when at most the 2 * PPW pieces of kc+2, kc+3 are
   // outstanding (the stores of the previous pair are younger still: the count is conservative by them)
@@ -299,35 +287,6 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) xs_pw1_kernel(const MlpPairAr
   }
   XS_STAMP(1);
   gelu_tail(accB, nch - 1);
-#else
-  // One chunk per barrier.  Wait count: the DMAs of chunk kc were issued D-1 steps ago; younger than them are the
-  // (D-2) * PPW DMAs of chunks kc+1 .. kc+D-2 and the 2 stores of each step since; vmcnt((D-2) * PPW) ignores the stores
-  auto step = [&](f32x16& cur, f32x16& nxt, int kc) {
-    if (kc >= 8 && kc < 16) XS_STAMP(2 * kc);
-    GCV_XS_WAIT(WAITN);
-    if (kc >= 8 && kc < 16) XS_STAMP(2 * kc + 1);
-    if (!(GCV_XS_ABLATE & 2)) issue();
-    chunk(cur, nxt, kc, std::true_type{});
-  };
-  GCV_XS_WAIT(WAITN);
-#pragma unroll
-  for (int p = 0; p < KP; ++p) asm volatile("" : "+v"(xf[p]));   // no use of xf may move above the wait
-  issue();
-  chunk(accA, accA, 0, std::false_type{});
-  int kc = 1;
-#pragma unroll 1
-  for (; kc + 1 < nch; kc += 2) {
-    step(accA, accB, kc);
-    step(accB, accA, kc + 1);
-  }
-  XS_STAMP(1);
-  if (kc < nch) {                                          // nch even: one more chunk, it ends up in accB
-    step(accA, accB, kc);
-    gelu_tail(accB, kc);
-  } else {
-    gelu_tail(accA, kc - 1);
-  }
-#endif
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // no DMA may outlive the workgroup's LDS
   XS_STAMP(2);
 }
@@ -595,15 +554,14 @@ __global__ void __launch_bounds__(512, 2) pw2f_kernel(const MlpPairArgs a) {
   P2_STAMP(42);
 }
 
-// the two halves (separately, so that a caller can time them) and both in stream order
+// the two halves, launched one after the other in stream order (launch_cnx_mlp)
 template <typename T> int launch_xs_pw1(const MlpPairArgs& a, int C, hipStream_t s);
 template <typename T> int launch_pw2f(const MlpPairArgs& a, int C, hipStream_t s);
-template <typename T> int launch_mlp_pair(const MlpPairArgs& a, int C, hipStream_t s);
 // (4C, C) / (C, 4C) row-major weights of type S (T or float) on the device -> fragment-major T
 template <typename T, typename S> int launch_pack_w1_frag(const S* w1, T* out, int C, hipStream_t s);
 template <typename T, typename S> int launch_pack_w2_frag(const S* w2, const float* gamma, T* out, int C, hipStream_t s);
 static inline bool mlp_pair_supported(int C) { return C == 384; }
-// bytes of the hidden workspace launch_mlp_pair needs for M tokens
+// bytes of the hidden workspace the pair needs for M tokens
 static inline size_t mlp_pair_hidden_bytes(int64_t M, int C) { return (size_t)((M + 31) / 32) * (size_t)(4 * C / 32) * 2048; }
 
 }  // namespace gcv

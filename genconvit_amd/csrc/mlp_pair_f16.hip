@@ -3,7 +3,6 @@
 namespace gcv {
 template int launch_xs_pw1<half_t>(const MlpPairArgs&, int, hipStream_t);
 template int launch_pw2f<half_t>(const MlpPairArgs&, int, hipStream_t);
-template int launch_mlp_pair<half_t>(const MlpPairArgs&, int, hipStream_t);
 template int launch_pack_w1_frag<half_t, half_t>(const half_t*, half_t*, int, hipStream_t);
 template int launch_pack_w2_frag<half_t, float>(const float*, const float*, half_t*, int, hipStream_t);
 }

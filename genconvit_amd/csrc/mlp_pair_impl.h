@@ -86,9 +86,5 @@ template <typename T> int launch_pw2f(const MlpPairArgs& a, int C, hipStream_t s
   GCV_TRY(mlp_pair_check(a, C));
   return launch_pw2f_c<T, 384>(a, s);
 }
-template <typename T> int launch_mlp_pair(const MlpPairArgs& a, int C, hipStream_t s) {
-  GCV_TRY(launch_xs_pw1<T>(a, C, s));
-  return launch_pw2f<T>(a, C, s);
-}
 
 }  // namespace gcv

@@ -13,9 +13,7 @@
 #include <cstring>
 
 #include "cam.h"
-#include "fused_mlp.h"
-#include "mlp_pair.h"
-#include "xs_mlp.h"
+#include "cnx_mlp.h"
 #include "gemm.h"
 #include "kernels.h"
 #include "net.h"
@@ -101,11 +99,8 @@ __global__ void __launch_bounds__(256) pack_mu_kernel(const float* __restrict__ 
 
 // ---------------------------------------------------------------- packed weights
 template <typename T> struct CnxBlockW {
-  float *dw_w, *dw_b, *ln_w, *ln_b, *fc1_b, *fc2_b, *gamma;
-  T *fc1_w, *fc2_w;
-  T* fc2_wc;       // 16-bit, C <= 192: W2 packed for the fused MLP kernels (else null)
-  T* fc_wp;        // 16-bit, C <= 192: W1 | W2 records of the x-stationary fused MLP (xs_mlp.h) (else null)
-  T *fc1_wf, *fc2_wf;   // 16-bit, C = 384: W1 / W2 in MFMA-fragment order for the pw1 / pw2 kernel pair (else null)
+  float *dw_w, *dw_b, *ln_w, *ln_b;
+  CnxMlpW<T> mlp;
 };
 template <typename T> struct CnxW {
   float *stem_w, *stem_b, *stem_lnw, *stem_lnb;
@@ -164,16 +159,6 @@ template <typename T> struct NetImpl : NetBase {
   bool has_ed = false, has_vae = false, has_swin = false;
   Arena arena;
   hipStream_t cur = nullptr;
-  bool use_fused_mlp = exp_env("GCV_NO_FUSED_MLP") == nullptr;   // A/B switches for profiling
-  // (GCV_EXPERIMENTS builds only, see common.h exp_env: the round-2 kernels behind their old switches)
-  bool use_fused_mlp384 = exp_env("GCV_FUSED_MLP384") != nullptr;
-#ifdef GCV_NO_LNP_EPILOGUE
-  bool use_lnp_epilogue = false;                         // A/B builds: LayerNorm-patchify as its own launch everywhere
-#else
-  bool use_lnp_epilogue = true;
-#endif
-  bool use_mlp_pair = exp_env("GCV_NO_MLP_PAIR") == nullptr;     // C = 384: pw1 / pw2 kernel pair (mlp_pair.h)
-  bool use_xs_mlp = exp_env("GCV_MLP_LEGACY") == nullptr;        // C = 192: x-stationary fused MLP (xs_mlp.h)
   // Schedule of vae_forward.  SPLIT: backbone(x) — which depends on nothing but the input — runs on a side stream while
   // the encoder / mu GEMM / decoder chain (small, latency-bound launches) and then backbone(x_hat) run on the caller's
   // stream.  MERGED: one stream, one two-segment backbone pass.  Alone on the GPU the split hides the codec chain
@@ -237,10 +222,10 @@ template <typename T> struct NetImpl : NetBase {
     r.e0 = prof.get_event();
     r.e1 = prof.get_event();
     roctx_push(tag);
+    struct Pop { ~Pop() { roctx_pop(); } } pop;     // closes the range on every exit path
     GCV_CHECK_HIP(hipEventRecord(r.e0, cur));
     const int rc = f();
     GCV_CHECK_HIP(hipEventRecord(r.e1, cur));
-    roctx_pop();
     prof.recs.push_back(r);
     return rc;
   }
@@ -403,6 +388,25 @@ template <typename T> struct NetImpl : NetBase {
     return 0;
   }
 
+  // packs a ConvNeXt block's MLP for its kind (cnx_mlp.h); the kinds that pack fc2 from fp32 get it uploaded here, for as
+  // long as their packing kernels run
+  int pack_mlp(const TensorMap& w, const std::string& fc2_name, int C, WeightStore& st, CnxMlpW<T>& mw) {
+    if (mw.kind == MlpKind::Gemm) return 0;
+    struct DevBuf {                        // freed on every exit path
+      float* p = nullptr;
+      ~DevBuf() { if (p) (void)hipFree(p); }
+    } w2f;
+    if (mlp_packs_from_f32(mw.kind)) {
+      std::vector<float> v;
+      GCV_TRY(fetch(w, fc2_name, (int64_t)4 * C * C, v));
+      GCV_CHECK_HIP(hipMalloc((void**)&w2f.p, v.size() * 4));
+      GCV_CHECK_HIP(hipMemcpy(w2f.p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
+    }
+    GCV_TRY(pack_cnx_mlp<T>(mw, C, w2f.p, [&](size_t n) { return st.raw(n); }, nullptr));
+    GCV_CHECK_HIP(hipDeviceSynchronize());
+    return 0;
+  }
+
   int pack_convnext(const TensorMap& w, const std::string& p, WeightStore& st, CnxW<T>& o) {
     {
       std::vector<float> v, t(48 * 96);
@@ -438,59 +442,15 @@ template <typename T> struct NetImpl : NetBase {
         GCV_TRY(up_f32(w, b + "conv_dw.bias", C, st, k.dw_b));
         GCV_TRY(up_f32(w, b + "norm.weight", C, st, k.ln_w));
         GCV_TRY(up_f32(w, b + "norm.bias", C, st, k.ln_b));
-        GCV_TRY(up_cast(w, b + "mlp.fc1.weight", (int64_t)4 * C * C, st, k.fc1_w));
-        GCV_TRY(up_f32(w, b + "mlp.fc1.bias", 4 * C, st, k.fc1_b));
-        GCV_TRY(up_cast(w, b + "mlp.fc2.weight", (int64_t)4 * C * C, st, k.fc2_w));
-        k.fc2_wc = nullptr;
-        k.fc1_wf = k.fc2_wf = nullptr;
-        k.fc_wp = nullptr;
-        if constexpr (sizeof(T) == 2) {
-          if (xs_mlp_default(C) && use_xs_mlp) {
-            k.fc_wp = (T*)st.raw(xs_mlp_packed_elems(C) * sizeof(T));
-            if (!k.fc_wp) { set_error("hipMalloc failed for the packed fc1 | fc2 records"); return -5; }
-            GCV_TRY((launch_pack_xs_mlp<T, T>(k.fc1_w, k.fc2_w, k.fc_wp, C, nullptr)));
-            GCV_CHECK_HIP(hipDeviceSynchronize());
-          }
-          if (mlp_pair_supported(C) && use_mlp_pair) {
-            k.fc1_wf = (T*)st.raw((size_t)4 * C * C * sizeof(T));
-            k.fc2_wf = (T*)st.raw((size_t)4 * C * C * sizeof(T));
-            if (!k.fc1_wf || !k.fc2_wf) { set_error("hipMalloc failed for the fragment-major fc1 / fc2"); return -5; }
-            GCV_TRY((launch_pack_w1_frag<T, T>(k.fc1_w, k.fc1_wf, C, nullptr)));
-            {
-              // the block's layer scale is folded into the packed fc2 (mlp_pair.h): packed from the fp32 source so that
-              // gamma * W2 is rounded to T once
-              std::vector<float> v, gv;
-              GCV_TRY(fetch(w, b + "mlp.fc2.weight", (int64_t)4 * C * C, v));
-              GCV_TRY(fetch(w, b + "gamma", C, gv));
-              struct DevBuf {                      // freed on every exit path
-                float* p = nullptr;
-                ~DevBuf() { if (p) (void)hipFree(p); }
-              } tmp, tg;
-              GCV_CHECK_HIP(hipMalloc((void**)&tmp.p, v.size() * 4));
-              GCV_CHECK_HIP(hipMalloc((void**)&tg.p, gv.size() * 4));
-              GCV_CHECK_HIP(hipMemcpy(tmp.p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-              GCV_CHECK_HIP(hipMemcpy(tg.p, gv.data(), gv.size() * 4, hipMemcpyHostToDevice));
-              GCV_TRY((launch_pack_w2_frag<T, float>(tmp.p, tg.p, k.fc2_wf, C, nullptr)));
-              GCV_CHECK_HIP(hipDeviceSynchronize());
-            }
-          }
-          if ((C <= 192 && !k.fc_wp) || (C == 384 && use_fused_mlp384)) {   // stages with a round-2 fused MLP kernel in use
-            std::vector<float> v;
-            GCV_TRY(fetch(w, b + "mlp.fc2.weight", (int64_t)4 * C * C, v));
-            struct DevBuf {                        // freed on every exit path
-              float* p = nullptr;
-              ~DevBuf() { if (p) (void)hipFree(p); }
-            } tmp;
-            GCV_CHECK_HIP(hipMalloc((void**)&tmp.p, v.size() * 4));
-            GCV_CHECK_HIP(hipMemcpy(tmp.p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-            k.fc2_wc = (T*)st.raw(v.size() * sizeof(T));
-            if (!k.fc2_wc) { set_error("hipMalloc failed for packed fc2"); return -5; }
-            GCV_TRY(launch_pack_w2_chunks<T>(tmp.p, k.fc2_wc, C, nullptr));
-            GCV_CHECK_HIP(hipDeviceSynchronize());
-          }
-        }
-        GCV_TRY(up_f32(w, b + "mlp.fc2.bias", C, st, k.fc2_b));
-        GCV_TRY(up_f32(w, b + "gamma", C, st, k.gamma));
+        T *w1, *w2;
+        float *b1, *b2, *gamma;
+        GCV_TRY(up_cast(w, b + "mlp.fc1.weight", (int64_t)4 * C * C, st, w1));
+        GCV_TRY(up_f32(w, b + "mlp.fc1.bias", 4 * C, st, b1));
+        GCV_TRY(up_cast(w, b + "mlp.fc2.weight", (int64_t)4 * C * C, st, w2));
+        GCV_TRY(up_f32(w, b + "mlp.fc2.bias", C, st, b2));
+        GCV_TRY(up_f32(w, b + "gamma", C, st, gamma));
+        k.mlp = CnxMlpW<T>{mlp_kind(sizeof(T), C), w1, w2, b1, b2, gamma};
+        GCV_TRY(pack_mlp(w, b + "mlp.fc2.weight", C, st, k.mlp));
       }
     }
     GCV_TRY(up_f32(w, p + "head.norm.weight", 768, st, o.head_lnw));
@@ -634,12 +594,13 @@ template <typename T> struct NetImpl : NetBase {
   // on different streams must not share them
   // tp: taps of this pass (null: none registered)
   int run_convnext(const CnxW<T>& w, const Seg<T>* segs, int nseg, bool keep = false, const TapPass* tp = nullptr) {
-    int h[4], wd[4];
+    int segn[4], h[4], wd[4];
     int64_t m[4], moff[4], M = 0;
     int ntot = 0;
     GCV_REQUIRE(nseg >= 1 && nseg <= 4, "1..4 segments");
     for (int s = 0; s < nseg; ++s) {
       GCV_REQUIRE(segs[s].H % 4 == 0 && segs[s].W % 4 == 0 && segs[s].n > 0, "segment geometry");
+      segn[s] = segs[s].n;
       h[s] = segs[s].H / 4;
       wd[s] = segs[s].W / 4;
       m[s] = (int64_t)segs[s].n * h[s] * wd[s];
@@ -723,70 +684,13 @@ template <typename T> struct NetImpl : NetBase {
           }));
           s = e;
         }
-        if constexpr (sizeof(T) == 2) {
-          if (k.fc_wp) {
-            XsMlpArgs xa{Y, k.fc_wp, k.fc1_b, k.fc2_b, k.gamma, X, X, (int)M};
-            if (j == kDepths[i] - 1 && i < 3 && use_lnp_epilogue) {   // stage boundary in the epilogue (see the C = 96 case below)
-              bool even = true;
-              int64_t o0 = 0;
-              for (int s = 0; s < nseg; ++s) {
-                xa.lnp_tok0[s] = (int)moff[s]; xa.lnp_hw[s] = h[s] * wd[s]; xa.lnp_wd[s] = wd[s]; xa.lnp_out0[s] = (int)o0;
-                o0 += (int64_t)segs[s].n * (h[s] / 2) * (wd[s] / 2);
-                even = even && h[s] % 2 == 0 && wd[s] % 2 == 0;
-              }
-              if (even) {
-                xa.out = Hd; xa.lnp_w = w.down[i].ln_w; xa.lnp_b = w.down[i].ln_b; xa.lnp_eps = 1e-6f; xa.lnp_nseg = nseg;
-                lnp_fused = true;
-              }
-            }
-            GCV_TRY(run("cnx.fused_mlp", 16.0 * M * C * (double)C, 3.0 * sizeof(T) * (double)M * C + 16.0 * C * C,
-                        [&] { return launch_xs_mlp<T>(xa, C, cur); }));
-            GCV_TRY(tap_block(j));
-            continue;
-          }
-          if (k.fc2_wc && use_fused_mlp && (C < 384 || use_fused_mlp384)) {
-            MlpArgs ma{Y, k.fc1_w, k.fc1_b, k.fc2_wc, k.fc2_b, k.gamma, X, X, (int)M};
-            // last block of the stage on the LDS-resident kernel: its epilogue applies the stage boundary's LayerNorm2d +
-            // space-to-depth and writes the down-sampling GEMM's operand (into Hd: Y is still being read as x_ln); the
-            // residual stream ends here and is not written
-            if (j == kDepths[i] - 1 && i < 3 && use_lnp_epilogue && fused_mlp_res_applies(C, M)) {
-              ma.out = Hd;
-              ma.lnp_w = w.down[i].ln_w; ma.lnp_b = w.down[i].ln_b; ma.lnp_eps = 1e-6f; ma.lnp_nseg = nseg;
-              int64_t o0 = 0;
-              bool even = true;
-              for (int s = 0; s < nseg; ++s) {
-                ma.lnp_tok0[s] = (int)moff[s]; ma.lnp_hw[s] = h[s] * wd[s]; ma.lnp_wd[s] = wd[s]; ma.lnp_out0[s] = (int)o0;
-                o0 += (int64_t)segs[s].n * (h[s] / 2) * (wd[s] / 2);
-                even = even && h[s] % 2 == 0 && wd[s] % 2 == 0;
-              }
-              if (even) lnp_fused = true;
-              else { ma.out = X; ma.lnp_nseg = 0; }     // odd maps drop their last row / column: the separate kernel does that
-            }
-            GCV_TRY(run("cnx.fused_mlp", 16.0 * M * C * (double)C, 3.0 * sizeof(T) * (double)M * C + 16.0 * C * C,
-                        [&] { return launch_fused_mlp<T>(ma, C, cur); }));
-            GCV_TRY(tap_block(j));
-            continue;
-          }
-        }
-        if constexpr (sizeof(T) == 2) {
-          if (k.fc1_wf && k.fc2_wf) {
-            MlpPairArgs pa{Y, k.fc1_wf, k.fc1_b, k.fc2_wf, k.fc2_b, k.gamma, X, X, Hd, (int)M};
-            GCV_TRY(run("cnx.pw1_gelu", 8.0 * M * C * (double)C, sizeof(T) * (5.0 * M * C + 4.0 * C * C),
-                        [&] { return launch_xs_pw1<T>(pa, C, cur); }));
-            GCV_TRY(run("cnx.pw2_scale_res", 8.0 * M * C * (double)C, sizeof(T) * (6.0 * M * C + 4.0 * C * C),
-                        [&] { return launch_pw2f<T>(pa, C, cur); }));
-            GCV_TRY(tap_block(j));
-            continue;
-          }
-        }
-        GemmArgs g1{};
-        g1.A = Y; g1.lda = C; g1.Wt = k.fc1_w; g1.C = Hd; g1.ldc = 4 * C; g1.bias = k.fc1_b;
-        g1.M = (int)M; g1.N = 4 * C; g1.K = C; g1.act = ACT_GELU; g1.splitk = 1;
-        GCV_TRY(gemm("cnx.pw1_gelu", g1, A_PLAIN, EPI_BIAS_ACT));
-        GemmArgs g2{};
-        g2.A = Hd; g2.lda = 4 * C; g2.Wt = k.fc2_w; g2.C = X; g2.ldc = C; g2.bias = k.fc2_b; g2.gamma = k.gamma;
-        g2.resid = X; g2.M = (int)M; g2.N = C; g2.K = 4 * C; g2.act = ACT_NONE; g2.splitk = 1;
-        GCV_TRY(gemm("cnx.pw2_scale_res", g2, A_PLAIN, EPI_RESID));
+        // the last block of stages 0..2 may apply the stage boundary's LayerNorm2d + space-to-depth in its epilogue and write
+        // the down-sampling GEMM's operand (into Hd: Y is still being read as x_ln); the residual stream then ends there
+        LnpSpec l;
+        const bool fuse = j == kDepths[i] - 1 && i < 3 && lnp_plan(l, k.mlp.kind, C, M, nseg, segn, h, wd);
+        if (fuse) { l.w = w.down[i].ln_w; l.b = w.down[i].ln_b; l.eps = 1e-6f; }
+        GCV_TRY(launch_cnx_mlp<T>(*this, k.mlp, C, Y, X, fuse ? Hd : X, Hd, (int)M, fuse ? &l : nullptr, cur));
+        lnp_fused = fuse;
         GCV_TRY(tap_block(j));
       }
     }

@@ -420,15 +420,10 @@ __global__ void __launch_bounds__(512, 2) xs_mlp_kernel(const XsMlpArgs a, const
 template <typename T> int launch_xs_mlp(const XsMlpArgs& a, int C, hipStream_t s);
 // W1 (4C, C) of T and W2 (C, 4C) of S (T or float) on the device -> the packed records
 template <typename T, typename S> int launch_pack_xs_mlp(const T* w1, const S* w2, T* out, int C, hipStream_t s);
-// C = 96 works (and is what the template was first written for) but measures 270 us at 256 images against 215 us for the
-// LDS-resident fused_mlp_res_kernel: twelve steps of 12 MFMAs each pay a barrier and a ring refill per step.  It is
-// instantiated in GCV_EXPERIMENTS builds only; the product path uses this kernel at C = 192.
-#ifdef GCV_EXPERIMENTS
-static inline bool xs_mlp_supported(int C) { return C == 96 || C == 192; }
-#else
+// C = 96 works (and is what the template was first written for) but measured 270 us at 256 images against 215 us for the
+// LDS-resident fused_mlp_res_kernel: twelve steps of 12 MFMAs each pay a barrier and a ring refill per step.  The library
+// runs this kernel at C = 192 only.
 static inline bool xs_mlp_supported(int C) { return C == 192; }
-#endif
-static inline bool xs_mlp_default(int C) { return C == 192 || (C == 96 && exp_env("GCV_XS_MLP96") != nullptr); }
 static inline size_t xs_mlp_packed_elems(int C) { return (size_t)(4 * C / 32) * (size_t)(C / 16 + 2 * (C / 32)) * 512; }
 
 }  // namespace gcv

@@ -1,4 +1,4 @@
-// x-stationary fused ConvNeXt MLP (C = 96 / 192) for storage dtype bf16_t
+// x-stationary fused ConvNeXt MLP (C = 192) for storage dtype bf16_t
 #include "xs_mlp_impl.h"
 namespace gcv {
 template int launch_xs_mlp<bf16_t>(const XsMlpArgs&, int, hipStream_t);

@@ -33,9 +33,6 @@ template <typename T> int launch_xs_mlp(const XsMlpArgs& a, int C, hipStream_t s
   GCV_REQUIRE(a.M > 0 && a.X && a.Wp && a.b1 && a.b2 && a.gamma && a.resid && a.out, "xs MLP: null argument");
   auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
   GCV_REQUIRE(al(a.X) && al(a.Wp) && al(a.resid) && al(a.out), "xs MLP: operands must be 16-byte aligned");
-#ifdef GCV_EXPERIMENTS
-  if (C == 96) return launch_xs_mlp_c<T, 96>(a, s);
-#endif
   if (C == 192) return launch_xs_mlp_c<T, 192>(a, s);
   set_error("xs MLP is built for C = 192");
   return -3;

@@ -30,7 +30,7 @@ import re
 # kernels those tags launch in a 16-bit run: the MLP kernels proper, and gemm_glds_kernel only in the two instantiations
 # run_convnext uses for pw1 (bias + GELU: EPI 0, ACT 2) and pw2 (layer-scale residual: EPI 1) — NOT the down-sampling /
 # head GEMMs (EPI 0, ACT 0 / 1), which an earlier version of this script swept in.
-MLP = ("xs_pw1_kernel", "pw2f_kernel", "xs_mlp_kernel", "fused_mlp_res_kernel", "fused_mlp_kernel", "fused_mlp_ring_kernel")
+MLP = ("xs_pw1_kernel", "pw2f_kernel", "xs_mlp_kernel", "fused_mlp_res_kernel", "fused_mlp_kernel")
 def fam(k):
     if any(m in k for m in MLP): return "mfma_gemm"
     # (the counter CSV carries mangled names: gemm_glds_kernelI<T>Li<EPI>ELi<ACT>ELi<BKB>EE; demangled ones are matched too)
