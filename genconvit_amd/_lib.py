@@ -44,6 +44,8 @@ class GemmArgs(ctypes.Structure):
 SIGNATURES = {
     "gcv_last_error": (c_char_p, []),
     "gcv_create": (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int]),
+    "gcv_create_arch": (c_int, [ctypes.POINTER(c_void_p), c_int, c_int, c_int, c_int]),
+    "gcv_handle_arch": (c_int, [c_void_p]),
     "gcv_destroy": (None, [c_void_p]),
     "gcv_workspace_bytes": (c_size_t, [c_void_p]),
     "gcv_load_ed": (c_int, [c_void_p, ctypes.POINTER(TensorDesc), c_int]),
@@ -76,6 +78,8 @@ SIGNATURES = {
     "gcv_k_gemm": (c_int, [c_int, c_int, c_int, ctypes.POINTER(GemmArgs), c_void_p]),
     "gcv_k_stem_ln": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
+    "gcv_k_stem_ln_c": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "gcv_k_dwconv7_ln": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                  c_int, c_int, c_float, c_void_p]),
     "gcv_k_ln_patchify": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
@@ -173,10 +177,17 @@ def current_stream_ptr(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
-class Handle:
-    """Owns one ``gcv_handle`` (packed weights + workspace) on one device / dtype."""
+# ConvNeXt backbone of a handle (include/genconvit_hip.h, GCV_CONVNEXT_*) and the largest max_batch each one takes
+ARCH_TINY, ARCH_LARGE = 0, 1
+ARCH_CODES = {"convnext_tiny": ARCH_TINY, "convnext_large": ARCH_LARGE}
+ARCH_MAX_BATCH = {ARCH_TINY: 512, ARCH_LARGE: 256}
 
-    def __init__(self, device_index: int, torch_dtype, max_batch: int):
+
+class Handle:
+    """Owns one ``gcv_handle`` (packed weights + workspace) on one device / dtype / ConvNeXt backbone (``arch``:
+    ``ARCH_TINY`` or ``ARCH_LARGE``)."""
+
+    def __init__(self, device_index: int, torch_dtype, max_batch: int, arch: int = ARCH_TINY):
         import torch
         self.lib = load()
         if not torch.cuda.is_available():
@@ -186,8 +197,9 @@ class Handle:
         self.dtype = torch_dtype
         self.max_batch = int(max_batch)
         self._h = c_void_p()
-        check(self.lib.gcv_create(ctypes.byref(self._h), self.device_index, dtype_code(torch_dtype), self.max_batch),
-              "gcv_create")
+        check(self.lib.gcv_create_arch(ctypes.byref(self._h), self.device_index, dtype_code(torch_dtype), self.max_batch,
+                                       int(arch)), "gcv_create_arch")
+        self.arch = self.lib.gcv_handle_arch(self._h)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:

@@ -64,14 +64,14 @@ struct Roctx {
 };
 Roctx& roctx() { static Roctx r; return r; }
 }  // namespace
-bool tap_name_known(const std::string& name) {
-  static const std::set<std::string> names = [] {
+bool tap_name_known(const std::string& name, int arch) {
+  auto make = [](int arch) {
     std::set<std::string> n;
     for (const char* t : {"ed.e1", "ed.e2", "ed.e3", "ed.e4", "ed.e5", "ed.d1", "ed.d2", "ed.d3", "ed.d4", "ed.rec", "ed.feat",
                           "vae.v1", "vae.v2", "vae.v3", "vae.v4", "vae.mu", "vae.z", "vae.d1", "vae.d2", "vae.d3", "vae.xhat",
                           "vae.feat"})
       n.insert(t);
-    static const int depths[4] = {3, 3, 9, 3};
+    const int* depths = cnx_arch(arch).depths;
     for (const char* net : {"ed", "vae"}) {
       const std::string p = std::string(net) + ".bb.";
       n.insert(p + "stem");
@@ -82,8 +82,9 @@ bool tap_name_known(const std::string& name) {
       }
     }
     return n;
-  }();
-  return names.count(name) != 0;
+  };
+  static const std::set<std::string> tiny = make(0), large = make(1);
+  return (arch == 1 ? large : tiny).count(name) != 0;
 }
 void roctx_push(const char* tag) { if (roctx().push) (void)roctx().push(tag); }
 void roctx_pop() { if (roctx().pop) (void)roctx().pop(); }
@@ -262,9 +263,17 @@ struct DeviceGuard {
 };
 
 int gcv_create(gcv_handle** out, int device, int dtype, int max_batch) {
+  return gcv_create_arch(out, device, dtype, max_batch, GCV_CONVNEXT_TINY);
+}
+
+int gcv_create_arch(gcv_handle** out, int device, int dtype, int max_batch, int arch) {
   GCV_REQUIRE(out != nullptr, "null handle pointer");
   *out = nullptr;
+  GCV_REQUIRE(arch == GCV_CONVNEXT_TINY || arch == GCV_CONVNEXT_LARGE, "arch must be GCV_CONVNEXT_TINY or GCV_CONVNEXT_LARGE");
   GCV_REQUIRE(max_batch >= 1 && max_batch <= 512, "max_batch must be in [1,512]");
+  // ConvNeXt-L: stage 0's hidden tensor of the ED network's two passes at 512 frames (1024 x 3136 tokens x 768) passes 2^31
+  GCV_REQUIRE(arch != GCV_CONVNEXT_LARGE || max_batch <= GCV_LARGE_MAX_BATCH,
+              "max_batch must be in [1,256] for a ConvNeXt-L handle (32-bit GEMM indexing)");
   int ndev = 0;
   GCV_CHECK_HIP(hipGetDeviceCount(&ndev));
   GCV_REQUIRE(device >= 0 && device < ndev, "no such HIP device");
@@ -282,6 +291,7 @@ int gcv_create(gcv_handle** out, int device, int dtype, int max_batch) {
   net->device = device;
   net->dtype = dtype;
   net->max_batch = max_batch;
+  net->arch = arch;
   DeviceGuard g(device);                                 // init() makes `device` current: restore the caller's on return
   const int rc = net->init();
   if (rc) { delete net; return rc; }
@@ -355,6 +365,7 @@ static int genconvit_run(gcv_handle* he, gcv_handle* hv, const void* x_nchw, con
                          gcv_stream stream, const Explain* ex_ed, const Explain* ex_vae) {
   GCV_REQUIRE(he && hv && he != hv, "two distinct handles (ED, VAE) are needed");
   GCV_REQUIRE(he->net->device == hv->net->device && he->net->dtype == hv->net->dtype, "ED and VAE handles differ in device / dtype");
+  GCV_REQUIRE(he->net->arch == hv->net->arch, "ED and VAE handles differ in backbone architecture");
   GCV_REQUIRE(x_nchw && eps && logits && batch >= 1, "null input / eps / output");
   DeviceGuard g(he->net->device);
   if (!he->side[0]) {
@@ -500,7 +511,7 @@ int gcv_vote_segments(const float* logits, int batch, int nets, const int* offse
 
 int gcv_tap_set(gcv_handle* h, const char* name, void* dst, size_t bytes) {
   GCV_REQUIRE(h && name, "null handle / tap name");
-  GCV_REQUIRE(tap_name_known(name), std::string("unknown tap '") + name + "'");
+  GCV_REQUIRE(tap_name_known(name, h->net->arch), std::string("unknown tap '") + name + "'");
   if (!dst) { h->net->taps.erase(name); return 0; }
   GCV_REQUIRE(bytes > 0, "tap buffer of 0 bytes");
   Tap t;
@@ -524,6 +535,8 @@ int gcv_tap_written(gcv_handle* h, const char* name) {
 }
 
 size_t gcv_workspace_bytes(const gcv_handle* h) { return h ? h->net->workspace_bytes() : 0; }
+
+int gcv_handle_arch(const gcv_handle* h) { return h ? h->net->arch : -1; }
 
 int gcv_profile_enable(gcv_handle* h, int on) {
   GCV_REQUIRE(h, "null handle");
@@ -584,6 +597,13 @@ int gcv_k_stem_ln(int dtype, const void* x, int64_t sb, int64_t sc, int64_t sy, 
                   float eps, gcv_stream s) {
   DISPATCH_DT(dtype, launch_stem_ln<T>((const T*)x, sb, sc, sy, sx, wp, bias, lnw, lnb, (T*)out, nimg, Ho, Wo, eps,
                                        (hipStream_t)s));
+}
+
+int gcv_k_stem_ln_c(int dtype, const void* x, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* wp,
+                    const float* bias, const float* lnw, const float* lnb, void* out, int nimg, int Ho, int Wo, int C,
+                    float eps, gcv_stream s) {
+  DISPATCH_DT(dtype, launch_stem_ln<T>((const T*)x, sb, sc, sy, sx, wp, bias, lnw, lnb, (T*)out, nimg, Ho, Wo, eps,
+                                       (hipStream_t)s, C));
 }
 
 int gcv_k_dwconv7_ln(int dtype, const void* x, const float* wdw, const float* bdw, const float* lnw,

@@ -25,12 +25,12 @@ struct HeadBwdArgs {
   int B, act;
 };
 struct CamArgs {
-  const void* A[2];       // stage-3 tokens of pass p: image b at A[p] + b * hw[p] * 768, (hw, 768) in T
+  const void* A[2];       // stage-3 tokens of pass p: image b at A[p] + b * hw[p] * C, (hw, C) in T (C: launch_cam's)
   int hw[2], side[2];     // side * side = hw
   int cam_off[2];         // map of (b, p) at cam + b * cam_ld + cam_off[p]
   int npass, cam_ld, up_pass;
-  const float* lnw;       // head.norm.weight (768)
-  const float* dpool;     // (B, npass, 768) fp32: d logit / d LayerNorm output
+  const float* lnw;       // head.norm.weight (C)
+  const float* dpool;     // (B, npass, C) fp32: d logit / d LayerNorm output
   float* cam;
   float* cam224;          // nullable: (B, 224, 224) fp32 upsample of pass up_pass's map
   float eps;
@@ -38,8 +38,8 @@ struct CamArgs {
 };
 
 template <typename T> int launch_head_bwd(const HeadBwdArgs& a, hipStream_t s);
-// d pooled row (rows, 768) = dfeat rows (rows, 1000) . W, W = head.fc.weight (1000, 768) in T
-template <typename T> int launch_bb_bwd(const float* dfeat, const void* W, float* dpool, int rows, hipStream_t s);
-template <typename T> int launch_cam(const CamArgs& a, hipStream_t s);
+// d pooled row (rows, C) = dfeat rows (rows, 1000) . W, W = head.fc.weight (1000, C) in T; C = 768 (ConvNeXt-T) or 1536 (-L)
+template <typename T> int launch_bb_bwd(const float* dfeat, const void* W, float* dpool, int rows, int C, hipStream_t s);
+template <typename T> int launch_cam(const CamArgs& a, int C, hipStream_t s);
 
 }  // namespace gcv

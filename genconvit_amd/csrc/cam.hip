@@ -78,10 +78,10 @@ __global__ void __launch_bounds__(256) head_bwd_kernel(HeadBwdArgs p) {
   }
 }
 
-template <typename T>
+template <typename T, int N = 768>
 __global__ void __launch_bounds__(256) bb_bwd_kernel(const float* __restrict__ dfeat, const T* __restrict__ W,
                                                      float* __restrict__ dpool, int rows) {
-  constexpr int K = 1000, N = 768;
+  constexpr int K = 1000;
   __shared__ __attribute__((aligned(16))) float a[kRB][K];
   __shared__ float red[4][kRB][64];
   const int tid = threadIdx.x, r0 = blockIdx.x * kRB;
@@ -109,10 +109,11 @@ __device__ __forceinline__ float block_sum256(float v, float* red) {
 }
 
 // one workgroup per (frame, pass): four waves share the LayerNorm backward, then each wave takes every fourth stage-3
-// token and reduces its 768-channel dot product with g across the wave (DPP rows + two cross-row steps)
-template <typename T>
+// token and reduces its C-channel dot product with g across the wave (DPP rows + two cross-row steps); C = 768 (ConvNeXt-T)
+// or 1536 (ConvNeXt-L), NV = C / 256 channels per thread
+template <typename T, int C = 768>
 __global__ void __launch_bounds__(256) cam_kernel(CamArgs p) {
-  constexpr int C = 768;
+  constexpr int NV = C / 256;
   __shared__ float g[C];
   __shared__ float red[4];
   __shared__ float map[49];
@@ -120,25 +121,30 @@ __global__ void __launch_bounds__(256) cam_kernel(CamArgs p) {
   const int hw = p.hw[pass];
   const T* A = (const T*)p.A[pass] + (int64_t)b * hw * C;
   // the pooled row and its LayerNorm statistics, as pool_ln_kernel computes them
-  float m[3] = {0.f, 0.f, 0.f};
+  float m[NV];
+#pragma unroll
+  for (int k = 0; k < NV; ++k) m[k] = 0.0f;
   for (int q = 0; q < hw; ++q) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) m[k] += to_f(A[(int64_t)q * C + tid + 256 * k]);
+    for (int k = 0; k < NV; ++k) m[k] += to_f(A[(int64_t)q * C + tid + 256 * k]);
   }
   const float inv = 1.0f / (float)hw;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) m[k] *= inv;
-  const float mean = block_sum256(m[0] + m[1] + m[2], red) / (float)C;
+  for (int k = 0; k < NV; ++k) m[k] *= inv;
+  float msum = m[0];
+#pragma unroll
+  for (int k = 1; k < NV; ++k) msum += m[k];
+  const float mean = block_sum256(msum, red) / (float)C;
   float d2 = 0.0f;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) { const float d = m[k] - mean; d2 = fmaf(d, d, d2); }
+  for (int k = 0; k < NV; ++k) { const float d = m[k] - mean; d2 = fmaf(d, d, d2); }
   const float rstd = 1.0f / sqrtf(block_sum256(d2, red) / (float)C + p.eps);
   // LayerNorm backward: dx = rstd * (dy - mean(dy) - xhat * mean(dy * xhat)), dy = d out * weight; the pooled row's
   // gradient spreads evenly over the hw tokens
   const float* dp = p.dpool + ((int64_t)b * p.npass + pass) * C;
-  float dy[3], xh[3], s1 = 0.0f, s2 = 0.0f;
+  float dy[NV], xh[NV], s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
+  for (int k = 0; k < NV; ++k) {
     const int c = tid + 256 * k;
     dy[k] = dp[c] * p.lnw[c];
     xh[k] = (m[k] - mean) * rstd;
@@ -148,7 +154,7 @@ __global__ void __launch_bounds__(256) cam_kernel(CamArgs p) {
   const float mdy = block_sum256(s1, red) / (float)C;
   const float mdyx = block_sum256(s2, red) / (float)C;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) g[tid + 256 * k] = rstd * (dy[k] - mdy - xh[k] * mdyx) * inv;
+  for (int k = 0; k < NV; ++k) g[tid + 256 * k] = rstd * (dy[k] - mdy - xh[k] * mdyx) * inv;
   __syncthreads();
   float* out = p.cam + (int64_t)b * p.cam_ld + p.cam_off[pass];
   for (int q = wv; q < hw; q += 4) {
@@ -189,26 +195,30 @@ template <typename T> int launch_head_bwd(const HeadBwdArgs& a, hipStream_t s) {
   return 0;
 }
 
-template <typename T> int launch_bb_bwd(const float* dfeat, const void* W, float* dpool, int rows, hipStream_t s) {
-  GCV_REQUIRE(rows > 0, "bb_bwd: empty");
-  hipLaunchKernelGGL((bb_bwd_kernel<T>), dim3(cdiv(rows, kRB), 768 / 64), dim3(256), 0, s, dfeat, (const T*)W, dpool, rows);
+template <typename T> int launch_bb_bwd(const float* dfeat, const void* W, float* dpool, int rows, int C, hipStream_t s) {
+  GCV_REQUIRE(rows > 0 && (C == 768 || C == 1536), "bb_bwd: empty, or C not 768 / 1536");
+  if (C == 768)
+    hipLaunchKernelGGL((bb_bwd_kernel<T, 768>), dim3(cdiv(rows, kRB), 768 / 64), dim3(256), 0, s, dfeat, (const T*)W, dpool, rows);
+  else
+    hipLaunchKernelGGL((bb_bwd_kernel<T, 1536>), dim3(cdiv(rows, kRB), 1536 / 64), dim3(256), 0, s, dfeat, (const T*)W, dpool, rows);
   GCV_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
-template <typename T> int launch_cam(const CamArgs& a, hipStream_t s) {
-  GCV_REQUIRE(a.B > 0 && a.npass >= 1 && a.npass <= 2, "cam: empty");
+template <typename T> int launch_cam(const CamArgs& a, int C, hipStream_t s) {
+  GCV_REQUIRE(a.B > 0 && a.npass >= 1 && a.npass <= 2 && (C == 768 || C == 1536), "cam: empty, or C not 768 / 1536");
   for (int q = 0; q < a.npass; ++q)
     GCV_REQUIRE(a.A[q] && a.side[q] >= 1 && a.side[q] * a.side[q] == a.hw[q] && a.hw[q] <= 49, "cam: stage-3 map of at most 7 x 7");
-  hipLaunchKernelGGL((cam_kernel<T>), dim3(a.B, a.npass), dim3(256), 0, s, a);
+  if (C == 768) hipLaunchKernelGGL((cam_kernel<T, 768>), dim3(a.B, a.npass), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((cam_kernel<T, 1536>), dim3(a.B, a.npass), dim3(256), 0, s, a);
   GCV_CHECK_HIP(hipGetLastError());
   return 0;
 }
 
 #define GCV_INSTANTIATE_CAM(T)                                                          \
   template int launch_head_bwd<T>(const HeadBwdArgs&, hipStream_t);                     \
-  template int launch_bb_bwd<T>(const float*, const void*, float*, int, hipStream_t);   \
-  template int launch_cam<T>(const CamArgs&, hipStream_t);
+  template int launch_bb_bwd<T>(const float*, const void*, float*, int, int, hipStream_t); \
+  template int launch_cam<T>(const CamArgs&, int, hipStream_t);
 GCV_INSTANTIATE_CAM(float)
 GCV_INSTANTIATE_CAM(half_t)
 GCV_INSTANTIATE_CAM(bf16_t)

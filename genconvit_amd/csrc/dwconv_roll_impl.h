@@ -4,8 +4,9 @@
 #pragma once
 #include <cstdlib>
 
-#include "dwconv_roll.h"
 #include "dwconv_mfma.h"
+#include "dwconv_pair.h"
+#include "dwconv_roll.h"
 #include "kernels.h"
 
 namespace gcv {
@@ -68,15 +69,32 @@ static int launch_dw_mfma_cfg(const T* x, const float* wdw, const float* bdw, co
   }
 }
 
-// shapes covered: the whole image width (W = 7 * NS) in one workgroup of NS * C <= 768 threads
+// the two-channels-per-lane kernel (dwconv_pair.h) at NS * C = 1536, the 224-pixel stages of ConvNeXt-L: a workgroup per
+// (image, band of rows), bands enough for two workgroups per CU
+template <typename T, int C, int NS>
+static int launch_dw_pair_cfg(const T* x, const float* wdw, const float* bdw, const float* lnw, const float* lnb, T* y,
+                              int nimg, int H, float eps, hipStream_t s) {
+  const int nb = std::max(1, std::min(H, (512 + nimg - 1) / nimg));
+  const int band_rows = (H + nb - 1) / nb;
+  const int nbands = (H + band_rows - 1) / band_rows;
+  GCV_REQUIRE((int64_t)H * 7 * NS * C * (int64_t)sizeof(T) < (int64_t)1 << 31, "dwconv: one image must stay below 2 GiB");
+  hipLaunchKernelGGL((dwconv7_ln_pair_kernel<T, C, NS>), dim3(nimg * nbands), dim3(kDwPairThreads), 0, s, x, wdw, bdw, lnw, lnb,
+                     y, H, band_rows, nbands, eps);
+  GCV_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// shapes covered: the whole image width (W = 7 * NS) in one workgroup of NS * C <= 768 threads, and (dwconv_pair.h) the
+// four NS * C = 1536 shapes of ConvNeXt-L
 template <typename T> bool dwconv_roll_applicable(int H, int W, int C) {
   if (W % 7 != 0 || H < 1) return false;
   const int ns = W / 7;
   switch (C) {
     case 96:  return ns == 4 || ns == 8;
-    case 192: return ns == 2 || ns == 4;
-    case 384: return ns == 1 || ns == 2;
-    case 768: return ns == 1;
+    case 192: return ns == 2 || ns == 4 || ns == 8;
+    case 384: return ns == 1 || ns == 2 || ns == 4;
+    case 768: return ns == 1 || ns == 2;
+    case 1536: return ns == 1;
   }
   return false;
 }
@@ -110,6 +128,9 @@ int launch_dwconv7_ln_roll(const T* x, const float* wdw, const float* bdw, const
   GCV_ROLL(384, 2); GCV_ROLL(384, 1);
   GCV_ROLL(768, 1);
 #undef GCV_ROLL
+#define GCV_PAIR(CC, NSS) if (C == CC && ns == NSS) return launch_dw_pair_cfg<T, CC, NSS>(x, wdw, bdw, lnw, lnb, y, nimg, H, eps, s)
+  GCV_PAIR(192, 8); GCV_PAIR(384, 4); GCV_PAIR(768, 2); GCV_PAIR(1536, 1);
+#undef GCV_PAIR
   set_error("dwconv7_ln_roll: unsupported shape");
   return -3;
 }

@@ -18,7 +18,7 @@ namespace gcv {
 // ------------------------------------------------------------------ launch wrappers (defined in kernels_impl.h)
 template <typename T> int launch_stem_ln(const T* x, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* wp,
                                          const float* bias, const float* lnw, const float* lnb, T* out, int nimg,
-                                         int Ho, int Wo, float eps, hipStream_t s);
+                                         int Ho, int Wo, float eps, hipStream_t s, int C = 96);
 template <typename T> int launch_dwconv7_ln(const T* x, const float* wdw, const float* bdw, const float* lnw,
                                             const float* lnb, T* y, int nimg, int H, int W, int C, float eps,
                                             hipStream_t s);

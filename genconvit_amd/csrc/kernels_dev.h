@@ -26,22 +26,25 @@ template <typename T> __device__ __forceinline__ float from_bits16(uint32_t u) {
 }
 
 // ------------------------------------------------------------------ K3: stem
-// conv 4x4 stride 4 (3 -> 96) + LayerNorm over the 96 channels, output NHWC tokens.
+// conv 4x4 stride 4 (3 -> C) + LayerNorm over the C channels, output NHWC tokens; C = 96 (ConvNeXt-T) or 192 (ConvNeXt-L).
 // Input addressed by element strides so NCHW frames and the NHWC reconstruction both work.
-// wp: [48][96] fp32 with k = ci*16 + ky*4 + kx.
-constexpr int kStemTok = 128;          // tokens per workgroup
-template <typename T>
+// wp: [48][C] fp32 with k = ci*16 + ky*4 + kx.
+template <int C> constexpr int stem_tok() { return 256 / (C / 12) * 4; }   // tokens per workgroup: 128 at C = 96, 64 at 192
+constexpr int kStemTok = stem_tok<96>();
+template <typename T, int C = 96>
 __global__ void __launch_bounds__(256) stem_ln_kernel(const T* __restrict__ x, int64_t sb, int64_t sc, int64_t sy,
                                                       int64_t sx, const float* __restrict__ wp,
                                                       const float* __restrict__ bias, const float* __restrict__ lnw,
                                                       const float* __restrict__ lnb, T* __restrict__ out, int nimg,
                                                       int Ho, int Wo, float eps) {
-  __shared__ __attribute__((aligned(16))) float sW[48 * 96];
-  __shared__ float sIn[kStemTok][49];
+  static_assert(C == 96 || C == 192, "stem widths of ConvNeXt-T / -L");
+  constexpr int TOK = stem_tok<C>(), CG = C / 12;     // CG 12-channel groups per token
+  __shared__ __attribute__((aligned(16))) float sW[48 * C];
+  __shared__ float sIn[TOK][49];
   const int tid = threadIdx.x;
-  for (int i = tid; i < 48 * 96 / 4; i += 256) reinterpret_cast<float4*>(sW)[i] = reinterpret_cast<const float4*>(wp)[i];
+  for (int i = tid; i < 48 * C / 4; i += 256) reinterpret_cast<float4*>(sW)[i] = reinterpret_cast<const float4*>(wp)[i];
   const int64_t total = (int64_t)nimg * Ho * Wo;
-  const int64_t p0 = (int64_t)blockIdx.x * kStemTok;
+  const int64_t p0 = (int64_t)blockIdx.x * TOK;
   // patch staging.  Both layouts the path uses keep 4 consecutive patch elements contiguous in memory — NCHW: the 4 kx
   // of one (ci, ky); NHWC: 4 of the 12 (kx, ci) of one ky — so a work item is one 8-byte load (per-element staging
   // spent ~20 integer instructions and one 2-byte load on each of the 48 patch elements).
@@ -50,7 +53,7 @@ __global__ void __launch_bounds__(256) stem_ln_kernel(const T* __restrict__ x, i
   const bool nhwc4 = sizeof(T) == 2 && al && sc == 1 && sx == 3;
   if constexpr (sizeof(T) == 2) {
    if (nchw4 || nhwc4) {
-    for (int e = tid; e < kStemTok * 12; e += 256) {
+    for (int e = tid; e < TOK * 12; e += 256) {
       const int p = e / 12, r = e - p * 12;              // NCHW: r = ci*4 + ky ; NHWC: r = ky*3 + third
       const int64_t gp = p0 + p;
       uint2 raw = {0u, 0u};
@@ -80,7 +83,7 @@ __global__ void __launch_bounds__(256) stem_ln_kernel(const T* __restrict__ x, i
    }
   }
   if (!(nchw4 || nhwc4)) {
-    for (int e = tid; e < kStemTok * 48; e += 256) {
+    for (int e = tid; e < TOK * 48; e += 256) {
       const int p = e / 48, k = e - p * 48;
       const int64_t gp = p0 + p;
       float v = 0.0f;
@@ -98,7 +101,7 @@ __global__ void __launch_bounds__(256) stem_ln_kernel(const T* __restrict__ x, i
   __syncthreads();
   // thread = (4 tokens, 12-channel group): three float4 of weights from LDS feed 48 FMAs (one token per thread issued
   // 13 LDS reads per 12 FMAs)
-  const int pq = tid >> 3, cg = tid & 7;               // tokens 4 pq .. 4 pq + 3, channels 12 cg .. 12 cg + 11
+  const int pq = tid / CG, cg = tid % CG;              // tokens 4 pq .. 4 pq + 3, channels 12 cg .. 12 cg + 11
   float acc[4][12];
 #pragma unroll
   for (int t = 0; t < 4; ++t)
@@ -106,7 +109,7 @@ __global__ void __launch_bounds__(256) stem_ln_kernel(const T* __restrict__ x, i
     for (int i = 0; i < 12; ++i) acc[t][i] = bias[cg * 12 + i];
 #pragma unroll 2
   for (int k = 0; k < 48; ++k) {
-    const float4* wr = reinterpret_cast<const float4*>(sW + k * 96 + cg * 12);
+    const float4* wr = reinterpret_cast<const float4*>(sW + k * C + cg * 12);
     float w[12];
 #pragma unroll
     for (int g4 = 0; g4 < 3; ++g4) {
@@ -128,16 +131,16 @@ __global__ void __launch_bounds__(256) stem_ln_kernel(const T* __restrict__ x, i
     float s = 0.0f;
 #pragma unroll
     for (int i = 0; i < 12; ++i) s += acc[t][i];
-    s = group8_sum(s);
-    const float mean = s * (1.0f / 96.0f);
+    s = CG == 8 ? group8_sum(s) : row16_sum(s);
+    const float mean = s * (1.0f / C);
     float q = 0.0f;
 #pragma unroll
     for (int i = 0; i < 12; ++i) { const float d = acc[t][i] - mean; q = fmaf(d, d, q); }
-    q = group8_sum(q);
-    const float rstd = 1.0f / sqrtf(q * (1.0f / 96.0f) + eps);
+    q = CG == 8 ? group8_sum(q) : row16_sum(q);
+    const float rstd = 1.0f / sqrtf(q * (1.0f / C) + eps);
     const int64_t gp = p0 + 4 * pq + t;
     if (gp < total) {
-      T* o = out + gp * 96 + cg * 12;
+      T* o = out + gp * C + cg * 12;
 #pragma unroll
       for (int i = 0; i < 12; ++i) o[i] = from_f<T>((acc[t][i] - mean) * rstd * lw[i] + lb[i]);
     }
@@ -152,31 +155,35 @@ __global__ void __launch_bounds__(256) stem_ln_kernel(const T* __restrict__ x, i
 // 9 MFMAs per tile; the 16-bit weight fragments (k permuted to the frame's memory order) are built once per
 // workgroup in LDS.  LayerNorm runs on the accumulator (token on the lane, the two half-waves hold 48 channels
 // each; two-pass statistics, one v_permlane32_swap per partial), and the store is six 16-byte pieces per lane.
-template <typename T>
-__global__ void __launch_bounds__(256, 3) stem_ln_mfma_kernel(const T* __restrict__ x, int64_t sb, int64_t sc, int64_t sy,
+// NO channel tiles of 32: 3 for the 96 channels of ConvNeXt-T, 6 for the 192 of ConvNeXt-L (whose 18 weight fragments and
+// 6 accumulators take two waves per SIMD instead of three).
+template <typename T, int NO = 3>
+__global__ void __launch_bounds__(256, (NO == 3) ? 3 : 2) stem_ln_mfma_kernel(const T* __restrict__ x, int64_t sb, int64_t sc, int64_t sy,
                                                            int nhwc, const float* __restrict__ wp,
                                                            const float* __restrict__ bias, const float* __restrict__ lnw,
                                                            const float* __restrict__ lnb, T* __restrict__ out, int total,
                                                            int Ho, int Wo, float eps) {
   static_assert(sizeof(T) == 2, "matrix-pipe stem is built for 16-bit storage");
-  __shared__ __attribute__((aligned(16))) T sWf[9 * 64 * 8];          // [o][p][lane][8]
-  __shared__ __attribute__((aligned(16))) float sPar[3 * 96];         // bias | ln weight | ln bias
+  static_assert(NO == 3 || NO == 6, "stem widths of ConvNeXt-T / -L");
+  constexpr int C = 32 * NO;
+  __shared__ __attribute__((aligned(16))) T sWf[NO * 3 * 64 * 8];     // [o][p][lane][8]
+  __shared__ __attribute__((aligned(16))) float sPar[3 * C];          // bias | ln weight | ln bias
   const int tid = threadIdx.x;
-  for (int idx = tid; idx < 48 * 96; idx += 256) {
-    const int k = idx / 96, n = idx - k * 96;
+  for (int idx = tid; idx < 48 * C; idx += 256) {
+    const int k = idx / C, n = idx - k * C;
     const int ci = k >> 4, ky = (k >> 2) & 3, kx = k & 3;
     const int kk = nhwc ? ky * 12 + kx * 3 + ci : k;                  // position in the frame's memory order
     const int o = n >> 5, lr = n & 31, p = kk >> 4, lh = (kk >> 3) & 1, i = kk & 7;
     sWf[((o * 3 + p) * 64 + lh * 32 + lr) * 8 + i] = from_f<T>(wp[idx]);
   }
-  for (int i = tid; i < 3 * 96; i += 256) sPar[i] = i < 96 ? bias[i] : (i < 192 ? lnw[i - 96] : lnb[i - 192]);
+  for (int i = tid; i < 3 * C; i += 256) sPar[i] = i < C ? bias[i] : (i < 2 * C ? lnw[i - C] : lnb[i - 2 * C]);
   __syncthreads();
 
   const int lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 31, lh = lane >> 5;
-  u32x4 wf[3][3];
+  u32x4 wf[NO][3];
 #pragma unroll
-  for (int o = 0; o < 3; ++o)
+  for (int o = 0; o < NO; ++o)
 #pragma unroll
     for (int p = 0; p < 3; ++p) wf[o][p] = *reinterpret_cast<const u32x4*>(sWf + ((o * 3 + p) * 64 + lane) * 8);
 
@@ -210,9 +217,9 @@ __global__ void __launch_bounds__(256, 3) stem_ln_mfma_kernel(const T* __restric
   for (; tile < ntiles; tile += stride) {
     const float* sp = sPar;                                // (through an empty asm: the parameter reads stay in the loop
     asm volatile("" : "+v"(sp));                           //  instead of 144 hoisted registers)
-    f32x16 acc[3];
+    f32x16 acc[NO];
 #pragma unroll
-    for (int o = 0; o < 3; ++o)
+    for (int o = 0; o < NO; ++o)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const f32x4 bv = *reinterpret_cast<const f32x4*>(sp + 32 * o + 8 * q + 4 * lh);
@@ -223,36 +230,36 @@ __global__ void __launch_bounds__(256, 3) stem_ln_mfma_kernel(const T* __restric
     for (int p = 0; p < 3; ++p) {
       const u32x4 xv = {xf[p][0][0], xf[p][0][1], xf[p][1][0], xf[p][1][1]};
 #pragma unroll
-      for (int o = 0; o < 3; ++o) Mfma<T>::run(wf[o][p], xv, acc[o]);
+      for (int o = 0; o < NO; ++o) Mfma<T>::run(wf[o][p], xv, acc[o]);
     }
     if (tile + stride < ntiles) load_x(tile + stride);      // lands under the LayerNorm and the stores
-    // LayerNorm over the token's 96 channels: 48 on this lane, 48 on lane ^ 32
+    // LayerNorm over the token's C channels: C / 2 on this lane, C / 2 on lane ^ 32
     // (ds_bpermute, not v_permlane32_swap: with one value as both operands hipcc 7.2 folds the two results into one
     // register and adds it to itself)
     auto both = [&](float v) { return v + __shfl_xor(v, 32, 64); };
     float s = 0.0f;
 #pragma unroll
-    for (int o = 0; o < 3; ++o)
+    for (int o = 0; o < NO; ++o)
 #pragma unroll
       for (int r = 0; r < 16; ++r) s += acc[o][r];
-    const float mean = both(s) * (1.0f / 96.0f);
+    const float mean = both(s) * (1.0f / C);
     float qq = 0.0f;
 #pragma unroll
-    for (int o = 0; o < 3; ++o)
+    for (int o = 0; o < NO; ++o)
 #pragma unroll
       for (int r = 0; r < 16; ++r) { const float d = acc[o][r] - mean; qq = fmaf(d, d, qq); }
-    const float rstd = 1.0f / sqrtf(both(qq) * (1.0f / 96.0f) + eps);
+    const float rstd = 1.0f / sqrtf(both(qq) * (1.0f / C) + eps);
     const int m = tile * 32 + lr;
 #pragma unroll
-    for (int o = 0; o < 3; ++o)
+    for (int o = 0; o < NO; ++o)
 #pragma unroll
       for (int q = 0; q < 4; q += 2) {
         uint2 pk[2];
 #pragma unroll
         for (int d = 0; d < 2; ++d) {
           const int n = 32 * o + 8 * (q + d) + 4 * lh;
-          const f32x4 lw4 = *reinterpret_cast<const f32x4*>(sp + 96 + n);
-          const f32x4 lb4 = *reinterpret_cast<const f32x4*>(sp + 192 + n);
+          const f32x4 lw4 = *reinterpret_cast<const f32x4*>(sp + C + n);
+          const f32x4 lb4 = *reinterpret_cast<const f32x4*>(sp + 2 * C + n);
           t4 o4;
 #pragma unroll
           for (int e = 0; e < 4; ++e) o4[e] = from_f<T>(fmaf((acc[o][4 * (q + d) + e] - mean) * rstd, lw4[e], lb4[e]));
@@ -262,7 +269,7 @@ __global__ void __launch_bounds__(256, 3) stem_ln_mfma_kernel(const T* __restric
         const auto sx = __builtin_amdgcn_permlane32_swap(pk[0].x, pk[1].x, false, false);
         const auto sy2 = __builtin_amdgcn_permlane32_swap(pk[0].y, pk[1].y, false, false);
         const u32x4 w = {sx[0], sy2[0], sx[1], sy2[1]};
-        if (m < total) *reinterpret_cast<u32x4*>(out + (int64_t)m * 96 + 32 * o + 8 * q + 8 * lh) = w;
+        if (m < total) *reinterpret_cast<u32x4*>(out + (int64_t)m * C + 32 * o + 8 * q + 8 * lh) = w;
       }
   }
 }
@@ -902,11 +909,11 @@ __global__ void __launch_bounds__(256) mean_tokens_kernel(const T* __restrict__ 
   }
 }
 
-// ------------------------------------------------------------------ K7: avg-pool + LN(768)
-template <typename T>
+// ------------------------------------------------------------------ K7: avg-pool + LN(C), C = 256 NV (768, 1536)
+template <typename T, int NV = 3>
 __global__ void __launch_bounds__(256) pool_ln_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                                       const float* __restrict__ bvec, T* __restrict__ out, int HW,
-                                                      int C /*768*/, float eps, int seg_n, int row_stride, int row0) {
+                                                      int C /*256 NV*/, float eps, int seg_n, int row_stride, int row0) {
   // image b of the launch (its passes one after the other, seg_n images each) -> output row
   // (b % seg_n) * row_stride + row0 + b / seg_n: with row_stride = the network's number of passes the rows of one frame's
   // passes are neighbours, and the classifier GEMM over all of them writes the (B, passes * 1000) feature matrix in one launch
@@ -914,27 +921,32 @@ __global__ void __launch_bounds__(256) pool_ln_kernel(const T* __restrict__ x, c
   const int b = blockIdx.x, tid = threadIdx.x;
   const int orow = (b % seg_n) * row_stride + row0 + b / seg_n;
   const T* src = x + (int64_t)b * HW * C;
-  float m[3] = {0.f, 0.f, 0.f};
+  float m[NV];
+#pragma unroll
+  for (int k = 0; k < NV; ++k) m[k] = 0.0f;
   for (int p = 0; p < HW; ++p) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) m[k] += to_f(src[(int64_t)p * C + tid + 256 * k]);
+    for (int k = 0; k < NV; ++k) m[k] += to_f(src[(int64_t)p * C + tid + 256 * k]);
   }
   const float inv = 1.0f / (float)HW;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) m[k] *= inv;
-  float s = wave_sum(m[0] + m[1] + m[2]);
+  for (int k = 0; k < NV; ++k) m[k] *= inv;
+  float s = m[0];
+#pragma unroll
+  for (int k = 1; k < NV; ++k) s += m[k];
+  s = wave_sum(s);
   if ((tid & 63) == 0) red[tid >> 6] = s;
   __syncthreads();
   const float mean = (red[0] + red[1] + red[2] + red[3]) / (float)C;
   float q = 0.0f;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) { const float d = m[k] - mean; q = fmaf(d, d, q); }
+  for (int k = 0; k < NV; ++k) { const float d = m[k] - mean; q = fmaf(d, d, q); }
   q = wave_sum(q);
   if ((tid & 63) == 0) red[4 + (tid >> 6)] = q;
   __syncthreads();
   const float rstd = 1.0f / sqrtf((red[4] + red[5] + red[6] + red[7]) / (float)C + eps);
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
+  for (int k = 0; k < NV; ++k) {
     const int c = tid + 256 * k;
     out[(int64_t)orow * C + c] = from_f<T>((m[k] - mean) * rstd * w[c] + bvec[c]);
   }

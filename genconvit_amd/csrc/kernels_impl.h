@@ -3,14 +3,15 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "dwconv_pair.h"
 #include "kernels.h"
 #include "kernels_dev.h"
 
 namespace gcv {
 
-template <typename T>
-int launch_stem_ln(const T* x, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* wp, const float* bias,
-                   const float* lnw, const float* lnb, T* out, int nimg, int Ho, int Wo, float eps, hipStream_t s) {
+template <typename T, int C>
+static int launch_stem_ln_c(const T* x, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* wp, const float* bias,
+                            const float* lnw, const float* lnb, T* out, int nimg, int Ho, int Wo, float eps, hipStream_t s) {
   const int64_t total = (int64_t)nimg * Ho * Wo;
   GCV_REQUIRE(total > 0, "stem: empty");
   GCV_REQUIRE((reinterpret_cast<uintptr_t>(wp) & 15u) == 0, "stem: packed weights must be 16-byte aligned");
@@ -23,16 +24,25 @@ int launch_stem_ln(const T* x, int64_t sb, int64_t sc, int64_t sy, int64_t sx, c
     if (!valu && (nchw4 || nhwc4) && total < (int64_t)1 << 30) {
       const int ntiles = (int)cdiv64(total, 32);
       const int grid = std::min(cdiv(ntiles, 4), 256 * 8);
-      hipLaunchKernelGGL((stem_ln_mfma_kernel<T>), dim3(grid), dim3(256), 0, s, x, sb, sc, sy, nhwc4 ? 1 : 0, wp, bias, lnw,
-                         lnb, out, (int)total, Ho, Wo, eps);
+      hipLaunchKernelGGL((stem_ln_mfma_kernel<T, C / 32>), dim3(grid), dim3(256), 0, s, x, sb, sc, sy, nhwc4 ? 1 : 0, wp, bias,
+                         lnw, lnb, out, (int)total, Ho, Wo, eps);
       GCV_CHECK_HIP(hipGetLastError());
       return 0;
     }
   }
-  hipLaunchKernelGGL((stem_ln_kernel<T>), dim3((unsigned)cdiv64(total, kStemTok)), dim3(256), 0, s, x, sb, sc, sy, sx, wp,
-                     bias, lnw, lnb, out, nimg, Ho, Wo, eps);
+  hipLaunchKernelGGL((stem_ln_kernel<T, C>), dim3((unsigned)cdiv64(total, stem_tok<C>())), dim3(256), 0, s, x, sb, sc, sy, sx,
+                     wp, bias, lnw, lnb, out, nimg, Ho, Wo, eps);
   GCV_CHECK_HIP(hipGetLastError());
   return 0;
+}
+
+template <typename T>
+int launch_stem_ln(const T* x, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* wp, const float* bias,
+                   const float* lnw, const float* lnb, T* out, int nimg, int Ho, int Wo, float eps, hipStream_t s, int C) {
+  if (C == 96) return launch_stem_ln_c<T, 96>(x, sb, sc, sy, sx, wp, bias, lnw, lnb, out, nimg, Ho, Wo, eps, s);
+  if (C == 192) return launch_stem_ln_c<T, 192>(x, sb, sc, sy, sx, wp, bias, lnw, lnb, out, nimg, Ho, Wo, eps, s);
+  set_error("stem: C must be 96 or 192");
+  return -3;
 }
 
 template <typename T, int C>
@@ -69,13 +79,23 @@ int launch_dwconv7_ln(const T* x, const float* wdw, const float* bdw, const floa
     GCV_DW_TINY(1) GCV_DW_TINY(2) GCV_DW_TINY(3) GCV_DW_TINY(4)
 #undef GCV_DW_TINY
   }
+  if (C == 1536 && H == W && H <= 4) {                      // ConvNeXt-L: two channels per lane (dwconv_pair.h)
+#define GCV_DW_TINY2(S)                                                                                              \
+    if (H == S) {                                                                                                   \
+      hipLaunchKernelGGL((dwconv7_ln_tiny2_kernel<T, 1536, S>), dim3(nimg), dim3(768), 0, s, x, wdw, bdw, lnw, lnb, y, eps); \
+      GCV_CHECK_HIP(hipGetLastError());                                                                             \
+      return 0;                                                                                                     \
+    }
+    GCV_DW_TINY2(1) GCV_DW_TINY2(2) GCV_DW_TINY2(3) GCV_DW_TINY2(4)
+#undef GCV_DW_TINY2
+  }
   switch (C) {
     case 96:  return launch_dw_c<T, 96>(x, wdw, bdw, lnw, lnb, y, nimg, H, W, eps, s);
     case 192: return launch_dw_c<T, 192>(x, wdw, bdw, lnw, lnb, y, nimg, H, W, eps, s);
     case 384: return launch_dw_c<T, 384>(x, wdw, bdw, lnw, lnb, y, nimg, H, W, eps, s);
     case 768: return launch_dw_c<T, 768>(x, wdw, bdw, lnw, lnb, y, nimg, H, W, eps, s);
   }
-  set_error("dwconv7_ln: C must be one of 96/192/384/768");
+  set_error("dwconv7_ln: C must be one of 96/192/384/768 (1536: 7-pixel-wide maps, or up to 4 x 4, only)");
   return -3;
 }
 
@@ -116,9 +136,12 @@ int launch_layernorm_rows(const T* x, const float* w, const float* b, T* out, in
 template <typename T>
 int launch_pool_ln(const T* x, const float* w, const float* b, T* out, int nimg, int HW, int C, float eps,
                    hipStream_t s, int seg_n, int row_stride, int row0) {
-  GCV_REQUIRE(C == 768 && nimg > 0 && HW > 0, "pool_ln: C == 768");
+  GCV_REQUIRE((C == 768 || C == 1536) && nimg > 0 && HW > 0, "pool_ln: C is 768 or 1536");
   if (seg_n <= 0) { seg_n = nimg; row_stride = 1; row0 = 0; }            // plain order: image b -> row b
-  hipLaunchKernelGGL((pool_ln_kernel<T>), dim3(nimg), dim3(256), 0, s, x, w, b, out, HW, C, eps, seg_n, row_stride, row0);
+  if (C == 768)
+    hipLaunchKernelGGL((pool_ln_kernel<T, 3>), dim3(nimg), dim3(256), 0, s, x, w, b, out, HW, C, eps, seg_n, row_stride, row0);
+  else
+    hipLaunchKernelGGL((pool_ln_kernel<T, 6>), dim3(nimg), dim3(256), 0, s, x, w, b, out, HW, C, eps, seg_n, row_stride, row0);
   GCV_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -263,7 +286,7 @@ template <typename T> int launch_preprocess(const unsigned char* u8, T* out, int
 
 #define GCV_INSTANTIATE_KERNELS(T)                                                                                    \
   template int launch_stem_ln<T>(const T*, int64_t, int64_t, int64_t, int64_t, const float*, const float*,            \
-                                 const float*, const float*, T*, int, int, int, float, hipStream_t);                  \
+                                 const float*, const float*, T*, int, int, int, float, hipStream_t, int);             \
   template int launch_dwconv7_ln<T>(const T*, const float*, const float*, const float*, const float*, T*, int, int,   \
                                     int, int, float, hipStream_t);                                                    \
   template int launch_ln_patchify<T>(const T*, const float*, const float*, T*, int, int, int, int, float, hipStream_t); \

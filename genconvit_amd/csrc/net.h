@@ -52,7 +52,7 @@ struct Tap {
   size_t bytes = 0;
   unsigned mask = 0, need = 0;
 };
-bool tap_name_known(const std::string& name);
+bool tap_name_known(const std::string& name, int arch);
 
 // ---- explain (gcv_*_explain, include/genconvit_hip.h) ---------------------------------------------------------------
 // Grad-CAM request of one network's forward: target (B) device ints or null (argmax), maps at cam + b * cam_ld (the
@@ -64,11 +64,25 @@ struct Explain {
   float* cam224 = nullptr;
 };
 
+// ---- ConvNeXt backbone architecture (gcv_create_arch) ------------------------
+// timm 0.6.5 convnext_tiny / convnext_large: same stem, block, downsample and head, widths and stage depths differ
+struct CnxArch {
+  int dims[4];
+  int depths[4];
+  int nblocks() const { return depths[0] + depths[1] + depths[2] + depths[3]; }
+};
+constexpr int kMaxCnxBlocks = 36;
+inline const CnxArch& cnx_arch(int arch) {       // arch: GCV_CONVNEXT_TINY (0) / GCV_CONVNEXT_LARGE (1)
+  static const CnxArch tiny{{96, 192, 384, 768}, {3, 3, 9, 3}}, large{{192, 384, 768, 1536}, {3, 3, 27, 3}};
+  return arch == 1 ? large : tiny;
+}
+
 // ---- abstract network (dtype erased) ----------------------------------------
 struct NetBase {
   int device = 0;
   int dtype = 0;
   int max_batch = 0;
+  int arch = 0;                   // GCV_CONVNEXT_TINY / GCV_CONVNEXT_LARGE: the backbone of both networks of the handle
   Profiler prof;
   bool in_ensemble = false;   // set by gcv_genconvit_forward around vae_forward: the VAE shares the GPU with the ED network
   // host-side enqueue order of the ensemble (gcv_genconvit_forward): called by vae_forward once its encoder -> mu ->

@@ -104,7 +104,7 @@ template <typename T> struct CnxBlockW {
 };
 template <typename T> struct CnxW {
   float *stem_w, *stem_b, *stem_lnw, *stem_lnb;
-  CnxBlockW<T> blk[18];
+  CnxBlockW<T> blk[kMaxCnxBlocks];
   struct { float *ln_w, *ln_b, *b; T* w; } down[3];
   float *head_lnw, *head_lnb, *head_fc_b;
   T* head_fc_w;
@@ -135,9 +135,6 @@ template <typename T> struct VaeW {
   float *dec4_w, *dec4_b;
   HeadW<T> head;
 };
-
-static const int kDims[4] = {96, 192, 384, 768};
-static const int kDepths[4] = {3, 3, 9, 3};
 
 template <typename T> struct Seg {
   const T* x;
@@ -272,9 +269,10 @@ template <typename T> struct NetImpl : NetBase {
   int tap_net(const char* name, const void* src, size_t bytes) { return tap_copy(name, bytes, 0, src, bytes, 1u, 1u); }
   // per-image elements of a backbone tap of segment s: kind 0 stem, 1 block output of stage i, 2 the operand of stage i's
   // downsample GEMM, 3 pooled rows
-  static int64_t tap_img_elems(const TapPass& tp, int s, int kind, int i) {
+  int64_t tap_img_elems(const TapPass& tp, int s, int kind, int i) const {
+    const int* dims = cnx_arch(arch).dims;
     const int64_t hw = (int64_t)((tp.H[s] / 4) >> i) * ((tp.W[s] / 4) >> i);
-    return kind == 3 ? 768 : kind == 2 ? hw * 4 * kDims[i - 1] : hw * kDims[i];
+    return kind == 3 ? dims[3] : kind == 2 ? hw * 4 * dims[i - 1] : hw * dims[i];
   }
   // segments [tp.first, tp.first + nseg) of backbone tap `<net>.bb.<what>`, contiguous at `src` (pool_ld > 0: pooled rows
   // stored frame-major, row pool_ld * frame + segment)
@@ -290,10 +288,11 @@ template <typename T> struct NetImpl : NetBase {
     }
     const unsigned need = (1u << tp.nall) - 1, bits = ((1u << nseg) - 1) << tp.first;
     if (!pool_ld) return tap_copy(name, total * sizeof(T), off * sizeof(T), src, n * sizeof(T), bits, need);
+    const int C3 = cnx_arch(arch).dims[3];
     for (int s = 0; s < nseg; ++s) {
-      GCV_TRY(tap_copy(name, total * sizeof(T), off * sizeof(T), src + s * 768, 768 * sizeof(T), bits, need,
-                       tp.n[tp.first + s], (size_t)pool_ld * 768 * sizeof(T)));
-      off += (int64_t)tp.n[tp.first + s] * 768;
+      GCV_TRY(tap_copy(name, total * sizeof(T), off * sizeof(T), src + s * C3, C3 * sizeof(T), bits, need,
+                       tp.n[tp.first + s], (size_t)pool_ld * C3 * sizeof(T)));
+      off += (int64_t)tp.n[tp.first + s] * C3;
     }
     return 0;
   }
@@ -407,29 +406,32 @@ template <typename T> struct NetImpl : NetBase {
     return 0;
   }
 
+  // the backbone of this handle's arch (cnx_arch): stages.{i}.blocks.{j} for j < depths[i], widths dims[i]
   int pack_convnext(const TensorMap& w, const std::string& p, WeightStore& st, CnxW<T>& o) {
+    const CnxArch& A = cnx_arch(arch);
+    const int C0 = A.dims[0], C3 = A.dims[3];
     {
-      std::vector<float> v, t(48 * 96);
-      GCV_TRY(fetch(w, p + "stem.0.weight", 96 * 48, v));
-      for (int co = 0; co < 96; ++co)
-        for (int k = 0; k < 48; ++k) t[k * 96 + co] = v[co * 48 + k];
+      std::vector<float> v, t((size_t)48 * C0);
+      GCV_TRY(fetch(w, p + "stem.0.weight", (int64_t)C0 * 48, v));
+      for (int co = 0; co < C0; ++co)
+        for (int k = 0; k < 48; ++k) t[k * C0 + co] = v[co * 48 + k];
       GCV_UP(o.stem_w, st, t);
     }
-    GCV_TRY(up_f32(w, p + "stem.0.bias", 96, st, o.stem_b));
-    GCV_TRY(up_f32(w, p + "stem.1.weight", 96, st, o.stem_lnw));
-    GCV_TRY(up_f32(w, p + "stem.1.bias", 96, st, o.stem_lnb));
+    GCV_TRY(up_f32(w, p + "stem.0.bias", C0, st, o.stem_b));
+    GCV_TRY(up_f32(w, p + "stem.1.weight", C0, st, o.stem_lnw));
+    GCV_TRY(up_f32(w, p + "stem.1.bias", C0, st, o.stem_lnb));
     int bi = 0;
     for (int i = 0; i < 4; ++i) {
-      const int C = kDims[i];
+      const int C = A.dims[i];
       if (i > 0) {
-        const int Cp = kDims[i - 1];
+        const int Cp = A.dims[i - 1];
         const std::string d = p + "stages." + std::to_string(i) + ".downsample.";
         GCV_TRY(up_f32(w, d + "0.weight", Cp, st, o.down[i - 1].ln_w));
         GCV_TRY(up_f32(w, d + "0.bias", Cp, st, o.down[i - 1].ln_b));
         GCV_TRY(up_conv_gemm(w, d + "1.weight", C, Cp, 2, 2, nullptr, st, o.down[i - 1].w));
         GCV_TRY(up_f32(w, d + "1.bias", C, st, o.down[i - 1].b));
       }
-      for (int j = 0; j < kDepths[i]; ++j, ++bi) {
+      for (int j = 0; j < A.depths[i]; ++j, ++bi) {
         const std::string b = p + "stages." + std::to_string(i) + ".blocks." + std::to_string(j) + ".";
         CnxBlockW<T>& k = o.blk[bi];
         {
@@ -453,9 +455,9 @@ template <typename T> struct NetImpl : NetBase {
         GCV_TRY(pack_mlp(w, b + "mlp.fc2.weight", C, st, k.mlp));
       }
     }
-    GCV_TRY(up_f32(w, p + "head.norm.weight", 768, st, o.head_lnw));
-    GCV_TRY(up_f32(w, p + "head.norm.bias", 768, st, o.head_lnb));
-    GCV_TRY(up_cast(w, p + "head.fc.weight", 1000 * 768, st, o.head_fc_w));
+    GCV_TRY(up_f32(w, p + "head.norm.weight", C3, st, o.head_lnw));
+    GCV_TRY(up_f32(w, p + "head.norm.bias", C3, st, o.head_lnb));
+    GCV_TRY(up_cast(w, p + "head.fc.weight", (int64_t)1000 * C3, st, o.head_fc_w));
     GCV_TRY(up_f32(w, p + "head.fc.bias", 1000, st, o.head_fc_b));
     return 0;
   }
@@ -589,7 +591,7 @@ template <typename T> struct NetImpl : NetBase {
     return 0;
   }
 
-  // ------------------------------------------------------------ ConvNeXt-T over token segments
+  // ------------------------------------------------------------ ConvNeXt-T / -L (the handle's arch) over token segments
   // keep = true leaves the token buffers allocated (the caller releases its own mark): two passes of one forward that run
   // on different streams must not share them
   // tp: taps of this pass (null: none registered)
@@ -608,30 +610,33 @@ template <typename T> struct NetImpl : NetBase {
       M += m[s];
       ntot += segs[s].n;
     }
-    GCV_REQUIRE(M * 384 < (int64_t)1 << 31, "token count too large for 32-bit GEMM indexing");
+    const CnxArch& A = cnx_arch(arch);
+    const int C0 = A.dims[0], C3 = A.dims[3];
+    // the widest GEMM operand is stage 0's (M, 4 C0) hidden tensor (and every later stage's is smaller)
+    GCV_REQUIRE(M * 4 * C0 < (int64_t)1 << 31, "token count too large for 32-bit GEMM indexing");
     bool saving = false;
     for (int s = 0; s < nseg; ++s) saving = saving || segs[s].s3;
     const size_t mk = arena.mark();
-    T* X = arena.get<T>(M * 96);
-    T* Y = arena.get<T>(M * 96);
-    T* Hd = arena.get<T>(M * 384);
-    T* Pool = arena.get<T>((int64_t)ntot * 768);
+    T* X = arena.get<T>(M * C0);
+    T* Y = arena.get<T>(M * C0);
+    T* Hd = arena.get<T>(M * 4 * C0);
+    T* Pool = arena.get<T>((int64_t)ntot * C3);
     if (!arena.dry && arena.overflow) { set_error("workspace arena too small: batch exceeds max_batch"); return -6; }
 
     for (int s = 0; s < nseg; ++s) {
       const Seg<T>& g = segs[s];
-      GCV_TRY(run("cnx.stem_ln", 2.0 * m[s] * 96 * 48, sizeof(T) * (double)m[s] * (48 + 96), [&] {
+      GCV_TRY(run("cnx.stem_ln", 2.0 * m[s] * C0 * 48, sizeof(T) * (double)m[s] * (48 + C0), [&] {
         return launch_stem_ln<T>(g.x, g.sb, g.sc, g.sy, g.sx, w.stem_w, w.stem_b, w.stem_lnw, w.stem_lnb,
-                                 X + moff[s] * 96, g.n, h[s], wd[s], 1e-6f, cur);
+                                 X + moff[s] * C0, g.n, h[s], wd[s], 1e-6f, cur, C0);
       }));
     }
     if (tp) GCV_TRY(tap_bb(*tp, nseg, "stem", 0, 0, X));
     int bi = 0;
     bool lnp_fused = false;       // the previous stage's last MLP has already written the LayerNorm'ed patches (into Hd)
     for (int i = 0; i < 4; ++i) {
-      const int C = kDims[i];
+      const int C = A.dims[i];
       if (i > 0) {
-        const int Cp = kDims[i - 1];
+        const int Cp = A.dims[i - 1];
         int64_t newM = 0, noff[4];
         for (int s = 0; s < nseg;) {
           // neighbouring segments of one geometry (ED: reconstruction + original pass) are contiguous on both sides:
@@ -670,7 +675,7 @@ template <typename T> struct NetImpl : NetBase {
       auto tap_block = [&](int j) {
         return tp && !lnp_fused ? tap_bb(*tp, nseg, "s" + std::to_string(i) + ".b" + std::to_string(j), 1, i, X) : 0;
       };
-      for (int j = 0; j < kDepths[i]; ++j, ++bi) {
+      for (int j = 0; j < A.depths[i]; ++j, ++bi) {
         const CnxBlockW<T>& k = w.blk[bi];
         for (int s = 0; s < nseg;) {
           // neighbouring segments of one geometry (ED: reconstruction + original pass) are contiguous in the token
@@ -687,7 +692,7 @@ template <typename T> struct NetImpl : NetBase {
         // the last block of stages 0..2 may apply the stage boundary's LayerNorm2d + space-to-depth in its epilogue and write
         // the down-sampling GEMM's operand (into Hd: Y is still being read as x_ln); the residual stream then ends there
         LnpSpec l;
-        const bool fuse = j == kDepths[i] - 1 && i < 3 && lnp_plan(l, k.mlp.kind, C, M, nseg, segn, h, wd);
+        const bool fuse = j == A.depths[i] - 1 && i < 3 && lnp_plan(l, k.mlp.kind, C, M, nseg, segn, h, wd);
         if (fuse) { l.w = w.down[i].ln_w; l.b = w.down[i].ln_b; l.eps = 1e-6f; }
         GCV_TRY(launch_cnx_mlp<T>(*this, k.mlp, C, Y, X, fuse ? Hd : X, Hd, (int)M, fuse ? &l : nullptr, cur));
         lnp_fused = fuse;
@@ -708,18 +713,18 @@ template <typename T> struct NetImpl : NetBase {
         int e = s, nimg = 0;
         int64_t mm = 0;
         while (e < nseg && h[e] * wd[e] == h[s] * wd[s]) { nimg += segs[e].n; mm += m[e]; ++e; }
-        GCV_TRY(run("cnx.pool_ln", 2.0 * mm * 768, sizeof(T) * (double)mm * 768, [&] {
+        GCV_TRY(run("cnx.pool_ln", 2.0 * mm * C3, sizeof(T) * (double)mm * C3, [&] {
           if (one_fc)
-            return launch_pool_ln<T>(X + moff[s] * 768, w.head_lnw, w.head_lnb, Pool, nimg, h[s] * wd[s], 768, 1e-6f, cur,
+            return launch_pool_ln<T>(X + moff[s] * C3, w.head_lnw, w.head_lnb, Pool, nimg, h[s] * wd[s], C3, 1e-6f, cur,
                                      segs[0].n, nseg, s);
-          return launch_pool_ln<T>(X + moff[s] * 768, w.head_lnw, w.head_lnb, Pool + (int64_t)no * 768, nimg, h[s] * wd[s],
-                                   768, 1e-6f, cur);
+          return launch_pool_ln<T>(X + moff[s] * C3, w.head_lnw, w.head_lnb, Pool + (int64_t)no * C3, nimg, h[s] * wd[s],
+                                   C3, 1e-6f, cur);
         }));
       }
       if (!one_fc) {
         GemmArgs g{};
-        g.A = Pool + (int64_t)no * 768; g.lda = 768; g.Wt = w.head_fc_w; g.C = segs[s].out; g.ldc = segs[s].out_ld;
-        g.bias = w.head_fc_b; g.M = segs[s].n; g.N = 1000; g.K = 768; g.act = segs[s].act; g.splitk = 1;
+        g.A = Pool + (int64_t)no * C3; g.lda = C3; g.Wt = w.head_fc_w; g.C = segs[s].out; g.ldc = segs[s].out_ld;
+        g.bias = w.head_fc_b; g.M = segs[s].n; g.N = 1000; g.K = C3; g.act = segs[s].act; g.splitk = 1;
         GCV_TRY(gemm("cnx.head_fc", g, A_PLAIN, EPI_BIAS_ACT));
         if (segs[s].pre) {
           g.C = segs[s].pre; g.act = ACT_NONE;
@@ -731,8 +736,8 @@ template <typename T> struct NetImpl : NetBase {
     if (tp) GCV_TRY(tap_bb(*tp, nseg, "pool", 3, 0, Pool, one_fc ? nseg : 0));
     if (one_fc) {
       GemmArgs g{};
-      g.A = Pool; g.lda = 768; g.Wt = w.head_fc_w; g.C = segs[0].out; g.ldc = 1000;
-      g.bias = w.head_fc_b; g.M = ntot; g.N = 1000; g.K = 768; g.act = segs[0].act; g.splitk = 1;
+      g.A = Pool; g.lda = C3; g.Wt = w.head_fc_w; g.C = segs[0].out; g.ldc = 1000;
+      g.bias = w.head_fc_b; g.M = ntot; g.N = 1000; g.K = C3; g.act = segs[0].act; g.splitk = 1;
       GCV_TRY(gemm("cnx.head_fc", g, A_PLAIN, EPI_BIAS_ACT));
       if (segs[0].pre) {
         g.C = segs[0].pre; g.act = ACT_NONE;
@@ -741,7 +746,7 @@ template <typename T> struct NetImpl : NetBase {
     }
     // explain: stage 3 has no LayerNorm-patchify epilogue, so its last block always leaves its output in X
     for (int s = 0; s < nseg; ++s)
-      if (segs[s].s3) *segs[s].s3 = X + moff[s] * 768;
+      if (segs[s].s3) *segs[s].s3 = X + moff[s] * C3;
     if (!keep && !saving) arena.release(mk);
     return 0;
   }
@@ -771,20 +776,21 @@ template <typename T> struct NetImpl : NetBase {
   int explain_tail(const CnxW<T>& bw, const HeadW<T>& hw, int act, int B, const float* part, const T* bbpre,
                    const float* logits, const T* const s3[2], const int hwp[2], const int side[2], const int off[2],
                    int up_pass, const Explain& ex) {
+    const int C3 = cnx_arch(arch).dims[3];
     float* dfeat = arena.get<float>((int64_t)B * 2000);
-    float* dpool = arena.get<float>((int64_t)B * 2 * 768);
+    float* dpool = arena.get<float>((int64_t)B * 2 * C3);
     if (!arena.dry && arena.overflow) { set_error("workspace arena too small"); return -6; }
     HeadBwdArgs ha{part, 8, hw.fc_b, hw.fc2_w, logits, ex.target, hw.fc_w, bbpre, dfeat, B, act};
     GCV_TRY(run("explain.head_bwd", 2.0 * B * 500 * 2000, sizeof(T) * (500.0 * 2000 + 2.0 * B * 2000) + 4.0 * B * (8 * 500 + 2000),
                 [&] { return launch_head_bwd<T>(ha, cur); }));
-    GCV_TRY(run("explain.bb_fc_bwd", 2.0 * 2 * B * 1000 * 768, sizeof(T) * 1000.0 * 768 + 4.0 * B * (2000 + 2 * 768),
-                [&] { return launch_bb_bwd<T>(dfeat, bw.head_fc_w, dpool, 2 * B, cur); }));
+    GCV_TRY(run("explain.bb_fc_bwd", 2.0 * 2 * B * 1000 * C3, sizeof(T) * 1000.0 * C3 + 4.0 * B * (2000 + 2 * C3),
+                [&] { return launch_bb_bwd<T>(dfeat, bw.head_fc_w, dpool, 2 * B, C3, cur); }));
     CamArgs ca{};
     for (int q = 0; q < 2; ++q) { ca.A[q] = s3[q]; ca.hw[q] = hwp[q]; ca.side[q] = side[q]; ca.cam_off[q] = off[q]; }
     ca.npass = 2; ca.cam_ld = ex.cam_ld; ca.up_pass = up_pass; ca.lnw = bw.head_lnw; ca.dpool = dpool;
     ca.cam = ex.cam; ca.cam224 = ex.cam224; ca.eps = 1e-6f; ca.B = B;
-    GCV_TRY(run("explain.cam", 4.0 * B * (hwp[0] + hwp[1]) * 768, sizeof(T) * (double)B * (hwp[0] + hwp[1]) * 768 +
-                (ex.cam224 ? 4.0 * B * 224 * 224 : 0.0), [&] { return launch_cam<T>(ca, cur); }));
+    GCV_TRY(run("explain.cam", 4.0 * B * (hwp[0] + hwp[1]) * C3, sizeof(T) * (double)B * (hwp[0] + hwp[1]) * C3 +
+                (ex.cam224 ? 4.0 * B * 224 * 224 : 0.0), [&] { return launch_cam<T>(ca, C3, cur); }));
     return 0;
   }
 

@@ -33,6 +33,17 @@ def build_param_tree(root: nn.Module, entries, init: str, seed: int, tag: str):
             node.register_parameter(parts[-1], nn.Parameter(t, requires_grad=False))
 
 
+def backbone_of(config) -> str:
+    """config['model']['backbone'] if this library builds it (convnext_tiny, the reference default; convnext_large,
+    prediction.py --s large), else ValueError.  The embedder (Swin-T / Swin-L) never runs in forward:
+    its name is not checked and its checkpoint keys are ignored."""
+    name = config["model"]["backbone"]
+    if name not in _lib.ARCH_CODES:
+        raise ValueError(f"backbone {name!r} is not built: only convnext_tiny (reference default, model/config.yaml:2) "
+                         "and convnext_large (prediction.py --s large) are")
+    return name
+
+
 # state_dict keys of the published checkpoints that never take part in forward (SURVEY.md §0.4,
 # Appendix A.3): the Swin "embedder" (registered twice) and HybridEmbed.proj, BN counters.
 OFF_PATH_MARKERS = ("embedder.", "patch_embed.", "num_batches_tracked")
@@ -43,13 +54,19 @@ OFF_PATH_MARKERS = ("embedder.", "patch_embed.", "num_batches_tracked")
 # They stay host-resident (``.to(device)`` / ``.cuda()`` change only their dtype), are packed into the handle
 # tensor by tensor (descriptor ``on_device = 0``), and ``state_dict()`` keeps returning them under the reference's keys.
 HOST_RESIDENT_NUMEL = 1 << 24
-MAX_HANDLE_BATCH = 512          # gcv_create's upper bound for max_batch
+MAX_HANDLE_BATCH = 512          # gcv_create's upper bound for max_batch (ConvNeXt-T; _lib.ARCH_MAX_BATCH per backbone)
 
 
 class HipModule(nn.Module):
     """Base class: parameter tree + handle lifecycle."""
 
     _default_max_batch = 32
+    _arch = _lib.ARCH_TINY          # ConvNeXt backbone of the handle (_lib.ARCH_*); set by the ConvNeXt-backed networks
+
+    @property
+    def _cap(self) -> int:
+        """Largest batch one handle of this module's backbone runs (512 frames; 256 for ConvNeXt-L)."""
+        return _lib.ARCH_MAX_BATCH[self._arch]
 
     def __init__(self):
         super().__init__()
@@ -109,7 +126,7 @@ class HipModule(nn.Module):
         return (sum(p._version for p in ps), sum(p.data_ptr() for p in ps) & 0xFFFFFFFFFFFF)
 
     def _get_handle(self, batch: int):
-        batch = min(batch, MAX_HANDLE_BATCH)
+        batch = min(batch, self._cap)
         device, dtype = self._param_device_dtype()
         if device.type != "cuda":
             raise _lib.GenConViTHipError(
@@ -117,11 +134,12 @@ class HipModule(nn.Module):
                 "on a machine with an MI355X")
         if batch > self._max_batch:
             self._max_batch = 1 << (batch - 1).bit_length()
-        key = (device.index if device.index is not None else torch.cuda.current_device(), dtype, self._max_batch)
+        self._max_batch = min(self._max_batch, self._cap)
+        key = (device.index if device.index is not None else torch.cuda.current_device(), dtype, self._max_batch, self._arch)
         if self._handle is None or self._handle_key != key:
             if self._handle is not None:
                 self._handle.close()
-            self._handle = _lib.Handle(key[0], dtype, self._max_batch)
+            self._handle = _lib.Handle(key[0], dtype, self._max_batch, self._arch)
             self._handle_key = key
             self._dirty = True
         if not self._dirty and self._weights_signature() != self._loaded_sig:
@@ -134,12 +152,14 @@ class HipModule(nn.Module):
         return self._handle
 
     def _chunks(self, n: int):
-        """Batches beyond one handle's workspace (512 frames) run as consecutive chunks: the reference accepts any B."""
-        return [(i, min(i + MAX_HANDLE_BATCH, n)) for i in range(0, n, MAX_HANDLE_BATCH)]
+        """Batches beyond one handle's workspace (512 frames, 256 for ConvNeXt-L) run as consecutive chunks: the reference
+        accepts any B."""
+        cap = self._cap
+        return [(i, min(i + cap, n)) for i in range(0, n, cap)]
 
     def reserve(self, max_batch: int):
         """Size the workspace for batches up to ``max_batch`` ahead of the first call."""
-        self._max_batch = min(max(int(max_batch), 1), MAX_HANDLE_BATCH)
+        self._max_batch = min(max(int(max_batch), 1), self._cap)
         return self
 
     @staticmethod

@@ -147,7 +147,7 @@ class GenConViT(nn.Module):
                                   generator=self.model_vae._generator)
             else:
                 eps = eps.to(device=x.device, dtype=torch.float32)
-            if B <= 512:
+            if B <= self.model_ed._cap:
                 return _lib.genconvit_forward(self.model_ed._get_handle(B), self.model_vae._get_handle(B), x, eps)
             parts = [_lib.genconvit_forward(self.model_ed._get_handle(hi - lo), self.model_vae._get_handle(hi - lo),
                                             x[lo:hi], eps[lo:hi]) for lo, hi in self.model_ed._chunks(B)]

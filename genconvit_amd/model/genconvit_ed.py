@@ -10,7 +10,8 @@ from __future__ import annotations
 import torch
 
 from .. import spec, synth
-from ._base import HipModule, build_param_tree
+from .. import _lib
+from ._base import HipModule, backbone_of, build_param_tree
 
 
 class GenConViTED(HipModule):
@@ -21,9 +22,9 @@ class GenConViTED(HipModule):
         uninitialised (``init='empty'``, when a checkpoint is loaded right after)."""
         super().__init__()
         self.config = config
-        if config["model"]["backbone"] != "convnext_tiny":
-            raise ValueError("only the convnext_tiny backbone is built (reference default, model/config.yaml:2)")
-        build_param_tree(self, spec.ed_spec(), init, seed, "ed/")
+        self.backbone_name = backbone_of(config)
+        self._arch = _lib.ARCH_CODES[self.backbone_name]
+        build_param_tree(self, spec.ed_spec(self.backbone_name), init, seed, "ed/")
         self.num_features = spec.NUM_BACKBONE_CLASSES * 2          # genconvit_ed.py:72
 
     def _load_into(self, handle):
@@ -34,7 +35,7 @@ class GenConViTED(HipModule):
         images = self._prep_input(images)
         if images.shape[0] == 0:                      # an empty batch is an empty result, as with the reference's nn.Modules
             return torch.empty((0, 2), dtype=torch.float32, device=images.device)
-        if images.shape[0] > 512:
+        if images.shape[0] > self._cap:
             return torch.cat([self._get_handle(hi - lo).ed_forward(images[lo:hi]) for lo, hi in self._chunks(images.shape[0])])
         return self._get_handle(images.shape[0]).ed_forward(images)
 
@@ -47,7 +48,7 @@ class GenConViTED(HipModule):
         ``eps`` is accepted for a signature shared with the VAE and ignored."""
         images = self._prep_input(images)
         B = images.shape[0]
-        if B > 512:
+        if B > self._cap:
             parts = [self._get_handle(hi - lo).ed_explain(images[lo:hi], self._target_chunk(target, lo, hi), upsample)
                      for lo, hi in self._chunks(B)]
         else:
@@ -59,6 +60,6 @@ class GenConViTED(HipModule):
         return cat(0), {"ed": cat(1), "upsampled": cat(2)}
 
     def backbone_forward(self, images):
-        """ConvNeXt-T alone (timm ``convnext_tiny`` forward, call site genconvit_ed.py:82-83)."""
+        """The ConvNeXt backbone alone (timm ``convnext_tiny`` / ``convnext_large`` forward, call site genconvit_ed.py:82-83)."""
         images = self._prep_input(images)
         return self._get_handle(images.shape[0]).convnext_forward(0, images)

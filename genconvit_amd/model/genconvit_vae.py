@@ -10,7 +10,8 @@ from __future__ import annotations
 import torch
 
 from .. import spec, synth
-from ._base import HipModule, build_param_tree
+from .. import _lib
+from ._base import HipModule, backbone_of, build_param_tree
 
 
 class GenConViTVAE(HipModule):
@@ -20,9 +21,9 @@ class GenConViTVAE(HipModule):
         self.latent_dims = config["model"]["latent_dims"]
         if self.latent_dims != spec.LATENT_DIMS:
             raise ValueError("latent_dims must be 12544 = 256*7*7 (decoder Unflatten, genconvit_vae.py:81)")
-        if config["model"]["backbone"] != "convnext_tiny":
-            raise ValueError("only the convnext_tiny backbone is built (reference default, model/config.yaml:2)")
-        build_param_tree(self, spec.vae_spec(include_unused=True), init, seed, "vae/")
+        self.backbone_name = backbone_of(config)
+        self._arch = _lib.ARCH_CODES[self.backbone_name]
+        build_param_tree(self, spec.vae_spec(include_unused=True, backbone=self.backbone_name), init, seed, "vae/")
         self.num_feature = spec.NUM_BACKBONE_CLASSES * 2
         self.kl = None          # Encoder.kl side effect (genconvit_vae.py:58), filled when want_kl
         self.mse = None
@@ -48,7 +49,7 @@ class GenConViTVAE(HipModule):
             eps = torch.randn((B, self.latent_dims), dtype=torch.float32, device=x.device, generator=self._generator)
         else:
             eps = eps.to(device=x.device, dtype=torch.float32)
-        if B > 512:                                   # beyond one handle's workspace: consecutive chunks
+        if B > self._cap:                             # beyond one handle's workspace: consecutive chunks
             chunks = self._chunks(B)
             parts = [self._get_handle(hi - lo).vae_forward(x[lo:hi], eps[lo:hi], want_recon, want_mse, want_kl)
                      for lo, hi in chunks]

@@ -7,6 +7,8 @@ Names and shapes follow the reference state_dict layout so that the published
 * VAE  : /root/reference/model/genconvit_vae.py:10-105
 * ConvNeXt-T (third-party timm==0.6.5 ``convnext_tiny``; call sites
   genconvit_ed.py:68,82-83 and genconvit_vae.py:97,111-112; spec SURVEY Appendix A.1)
+* ConvNeXt-L (timm==0.6.5 ``convnext_large``), the backbone ``prediction.py --s large``
+  configures (prediction.py:314-318): the same layout, wider and with 27 stage-2 blocks
 
 Each entry is ``(name, shape, kind)``; ``kind`` selects the synthetic
 distribution in :mod:`genconvit_amd.synth` and is ignored when real
@@ -16,6 +18,13 @@ from __future__ import annotations
 
 CONVNEXT_DIMS = (96, 192, 384, 768)
 CONVNEXT_DEPTHS = (3, 3, 9, 3)
+CONVNEXT_LARGE_DIMS = (192, 384, 768, 1536)
+CONVNEXT_LARGE_DEPTHS = (3, 3, 27, 3)
+# backbone name (config['model']['backbone']) -> (dims, depths)
+CONVNEXT_ARCHS = {
+    "convnext_tiny": (CONVNEXT_DIMS, CONVNEXT_DEPTHS),
+    "convnext_large": (CONVNEXT_LARGE_DIMS, CONVNEXT_LARGE_DEPTHS),
+}
 NUM_BACKBONE_CLASSES = 1000
 LATENT_DIMS = 12544          # model/config.yaml:4
 VAE_FLAT = 128 * 14 * 14     # genconvit_vae.py:36
@@ -23,15 +32,26 @@ VAE_FLAT = 128 * 14 * 14     # genconvit_vae.py:36
 
 def convnext_tiny_spec(prefix: str):
     """timm 0.6.5 ``convnext_tiny`` parameters under ``prefix`` (e.g. ``backbone.``)."""
+    return convnext_spec(prefix, "convnext_tiny")
+
+
+def convnext_large_spec(prefix: str):
+    """timm 0.6.5 ``convnext_large`` parameters under ``prefix`` (197 767 336 of them)."""
+    return convnext_spec(prefix, "convnext_large")
+
+
+def convnext_spec(prefix: str, backbone: str = "convnext_tiny"):
+    """timm 0.6.5 ConvNeXt parameters of ``backbone`` (a key of ``CONVNEXT_ARCHS``) under ``prefix``."""
+    dims, depths = CONVNEXT_ARCHS[backbone]
     out = []
     p = prefix
-    out.append((p + "stem.0.weight", (96, 3, 4, 4), "conv"))
-    out.append((p + "stem.0.bias", (96,), "bias"))
-    out.append((p + "stem.1.weight", (96,), "ln_w"))
-    out.append((p + "stem.1.bias", (96,), "bias"))
-    for i, (dim, depth) in enumerate(zip(CONVNEXT_DIMS, CONVNEXT_DEPTHS)):
+    out.append((p + "stem.0.weight", (dims[0], 3, 4, 4), "conv"))
+    out.append((p + "stem.0.bias", (dims[0],), "bias"))
+    out.append((p + "stem.1.weight", (dims[0],), "ln_w"))
+    out.append((p + "stem.1.bias", (dims[0],), "bias"))
+    for i, (dim, depth) in enumerate(zip(dims, depths)):
         if i > 0:
-            din = CONVNEXT_DIMS[i - 1]
+            din = dims[i - 1]
             out.append((p + f"stages.{i}.downsample.0.weight", (din,), "ln_w"))
             out.append((p + f"stages.{i}.downsample.0.bias", (din,), "bias"))
             out.append((p + f"stages.{i}.downsample.1.weight", (dim, din, 2, 2), "conv"))
@@ -47,15 +67,15 @@ def convnext_tiny_spec(prefix: str):
             out.append((b + "mlp.fc2.weight", (dim, 4 * dim), "linear"))
             out.append((b + "mlp.fc2.bias", (dim,), "bias"))
             out.append((b + "gamma", (dim,), "gamma"))
-    out.append((p + "head.norm.weight", (768,), "ln_w"))
-    out.append((p + "head.norm.bias", (768,), "bias"))
-    out.append((p + "head.fc.weight", (NUM_BACKBONE_CLASSES, 768), "linear"))
+    out.append((p + "head.norm.weight", (dims[3],), "ln_w"))
+    out.append((p + "head.norm.bias", (dims[3],), "bias"))
+    out.append((p + "head.fc.weight", (NUM_BACKBONE_CLASSES, dims[3]), "linear"))
     out.append((p + "head.fc.bias", (NUM_BACKBONE_CLASSES,), "bias"))
     return out
 
 
-def ed_spec():
-    """GenConViTED parameters that take part in forward (genconvit_ed.py:64-88)."""
+def ed_spec(backbone: str = "convnext_tiny"):
+    """GenConViTED parameters that take part in forward (genconvit_ed.py:64-88), with the ConvNeXt ``backbone``."""
     out = []
     chans = [3, 16, 32, 64, 128, 256]
     for li, idx in enumerate((0, 3, 6, 9, 12)):              # genconvit_ed.py:14-32
@@ -65,7 +85,7 @@ def ed_spec():
     for li, idx in enumerate((0, 2, 4, 6, 8)):               # genconvit_ed.py:44-57
         out.append((f"decoder.features.{idx}.weight", (dch[li], dch[li + 1], 2, 2), "convT"))
         out.append((f"decoder.features.{idx}.bias", (dch[li + 1],), "bias"))
-    out += convnext_tiny_spec("backbone.")
+    out += convnext_spec("backbone.", backbone)
     out.append(("fc.weight", (500, 2000), "linear"))          # genconvit_ed.py:72-74
     out.append(("fc.bias", (500,), "bias"))
     out.append(("fc2.weight", (2, 500), "linear"))
@@ -73,8 +93,8 @@ def ed_spec():
     return out
 
 
-def vae_spec(include_unused: bool = True):
-    """GenConViTVAE parameters (genconvit_vae.py:91-105).
+def vae_spec(include_unused: bool = True, backbone: str = "convnext_tiny"):
+    """GenConViTVAE parameters (genconvit_vae.py:91-105), with the ConvNeXt ``backbone``.
 
     ``include_unused`` adds ``encoder.fc1/fc2`` and ``fc3`` which exist in the
     checkpoints but never run in forward.
@@ -102,7 +122,7 @@ def vae_spec(include_unused: bool = True):
     for li, idx in enumerate((0, 2, 4, 6)):                  # genconvit_vae.py:68-78
         out.append((f"decoder.features.{idx}.weight", (dch[li], dch[li + 1], 2, 2), "convT"))
         out.append((f"decoder.features.{idx}.bias", (dch[li + 1],), "bias"))
-    out += convnext_tiny_spec("convnext_backbone.")
+    out += convnext_spec("convnext_backbone.", backbone)
     out.append(("fc.weight", (500, 2000), "linear"))          # :101
     out.append(("fc.bias", (500,), "bias"))
     out.append(("fc2.weight", (2, 500), "linear"))            # :103

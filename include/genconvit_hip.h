@@ -35,6 +35,8 @@ typedef struct gcv_handle gcv_handle;
 typedef void* gcv_stream;
 
 enum { GCV_F32 = 0, GCV_BF16 = 1, GCV_F16 = 2 };               /* storage dtype of a handle      */
+enum { GCV_CONVNEXT_TINY = 0, GCV_CONVNEXT_LARGE = 1 };        /* ConvNeXt backbone of a handle  */
+enum { GCV_LARGE_MAX_BATCH = 256 };                            /* max_batch cap of a Large handle */
 enum { GCV_ACT_NONE = 0, GCV_ACT_RELU = 1, GCV_ACT_GELU = 2, GCV_ACT_LEAKY = 3 };
 
 /* One named fp32 tensor of a reference state_dict (key names as in weight/{ed,vae}.pth,
@@ -51,6 +53,15 @@ const char* gcv_last_error(void);
 /* Handle lifetime.  Replaces GenConViT.__init__'s module construction + .to(device)/.half()
  * (model/genconvit.py:9-64, model/pred_func.py:50-62).  `max_batch` sizes the workspace arena. */
 int  gcv_create(gcv_handle** h, int device, int dtype, int max_batch);
+/* The same with the ConvNeXt backbone of both networks chosen: GCV_CONVNEXT_TINY (what gcv_create builds; timm
+ * convnext_tiny, model/config.yaml:2) or GCV_CONVNEXT_LARGE (timm convnext_large: dims 192/384/768/1536, depths
+ * 3/3/27/3), the config that prediction.py --s large writes (prediction.py:314-318, prediction_v2.py:421-423).  The
+ * checkpoint keys are the same with the wider shapes and stages.2.blocks.0..26.  A Large handle takes max_batch
+ * <= GCV_LARGE_MAX_BATCH (256): the ED network's stage-0 MLP hidden tensor at 512 frames passes 32-bit GEMM indexing.
+ * gcv_genconvit_forward / _explain refuse an ED and a VAE handle of different architectures. */
+int  gcv_create_arch(gcv_handle** h, int device, int dtype, int max_batch, int arch);
+/* the handle's GCV_CONVNEXT_* architecture (-1 for a null handle) */
+int  gcv_handle_arch(const gcv_handle* h);
 void gcv_destroy(gcv_handle* h);
 size_t gcv_workspace_bytes(const gcv_handle* h);
 
@@ -230,6 +241,10 @@ int gcv_k_gemm(int dtype, int a_mode, int epi, const gcv_gemm_args* a, gcv_strea
 int gcv_k_stem_ln(int dtype, const void* x, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* wp,
                   const float* bias, const float* lnw, const float* lnb, void* out, int nimg, int Ho, int Wo,
                   float eps, gcv_stream s);
+/* the stem at output width C: 96 (ConvNeXt-T, = gcv_k_stem_ln) or 192 (ConvNeXt-L); wp [48][C] */
+int gcv_k_stem_ln_c(int dtype, const void* x, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* wp,
+                    const float* bias, const float* lnw, const float* lnb, void* out, int nimg, int Ho, int Wo, int C,
+                    float eps, gcv_stream s);
 int gcv_k_dwconv7_ln(int dtype, const void* x, const float* wdw, const float* bdw, const float* lnw,
                      const float* lnb, void* y, int nimg, int H, int W, int C, float eps, gcv_stream s);
 int gcv_k_ln_patchify(int dtype, const void* x, const float* w, const float* b, void* out, int nimg, int H, int W,
