@@ -611,6 +611,16 @@ int gcv_k_dwconv7_ln(int dtype, const void* x, const float* wdw, const float* bd
   DISPATCH_DT(dtype, launch_dwconv7_ln<T>((const T*)x, wdw, bdw, lnw, lnb, (T*)y, nimg, H, W, C, eps, (hipStream_t)s));
 }
 
+int gcv_dw_plan(int dtype, int nimg, int H, int W, int C, int aligned, int* out5) {
+  GCV_REQUIRE(out5, "null out5");
+  DwPlan p;
+  auto put = [&](int rc) {
+    if (rc == 0) { out5[0] = (int)p.kind; out5[1] = p.grid; out5[2] = p.block; out5[3] = p.lds; out5[4] = p.band_rows; }
+    return rc;
+  };
+  DISPATCH_DT(dtype, put(dw_plan<T>(p, nimg, H, W, C, aligned != 0)));
+}
+
 int gcv_k_ln_patchify(int dtype, const void* x, const float* w, const float* b, void* out, int nimg, int H, int W,
                       int C, float eps, gcv_stream s) {
   DISPATCH_DT(dtype, launch_ln_patchify<T>((const T*)x, w, b, (T*)out, nimg, H, W, C, eps, (hipStream_t)s));

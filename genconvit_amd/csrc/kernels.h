@@ -19,14 +19,29 @@ namespace gcv {
 template <typename T> int launch_stem_ln(const T* x, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* wp,
                                          const float* bias, const float* lnw, const float* lnb, T* out, int nimg,
                                          int Ho, int Wo, float eps, hipStream_t s, int C = 96);
+// depthwise 7x7 + LayerNorm (dwconv_impl.h): the kernel that runs a launch of nimg H x W x C images and its grid, planned
+// in one place (dw_select); dw_plan returns the plan, or the launcher's error, without a HIP call.  The tile kinds are
+// compiled in the kern_*.hip translation units and launched from the plan by launch_dw_tile (kernels_impl.h)
+enum class DwKind { Tile, Tiny, TinyPair, Roll, Mfma, Pair };   // in this order: the `kind` of gcv_dw_plan
+struct DwPlan {
+  DwKind kind = DwKind::Tile;
+  int C = 0, n = 0;                   // template shape: C, and NS = W / 7 (Roll, Mfma, Pair) or S = H = W (Tiny, TinyPair)
+  int band_rows = 0;                  // Roll, Mfma, Pair: output rows per workgroup
+  int grid = 0, block = 0, lds = 0;   // workgroups, threads per workgroup, dynamic LDS bytes
+};
+template <typename T> int dw_plan(DwPlan& p, int nimg, int H, int W, int C, bool aligned);   // aligned: x, y 16-byte
 template <typename T> int launch_dwconv7_ln(const T* x, const float* wdw, const float* bdw, const float* lnw,
                                             const float* lnb, T* y, int nimg, int H, int W, int C, float eps,
                                             hipStream_t s);
-// rolling-strip variant (dwconv_roll.h): W % 7 == 0 shapes of ConvNeXt-T; `applicable` says whether it covers a shape
-template <typename T> bool dwconv_roll_applicable(int H, int W, int C);
-template <typename T> int launch_dwconv7_ln_roll(const T* x, const float* wdw, const float* bdw, const float* lnw,
-                                                 const float* lnb, T* y, int nimg, int H, int W, int C, float eps,
-                                                 hipStream_t s);
+template <typename T> int launch_dw_tile(const DwPlan& p, const T* x, const float* wdw, const float* bdw, const float* lnw,
+                                         const float* lnb, T* y, int nimg, int H, int W, float eps, hipStream_t s);
+// launches kernel with p's grid, block and dynamic LDS (raising the kernel's limit first where p needs more than 64 KiB)
+template <class K, class... A> int dw_launch(const DwPlan& p, K kernel, hipStream_t s, A... args) {
+  if (p.lds > 64 * 1024) GCV_ENSURE_LDS(kernel, p.lds);
+  hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), p.lds, s, args...);
+  GCV_CHECK_HIP(hipGetLastError());
+  return 0;
+}
 template <typename T> int launch_ln_patchify(const T* x, const float* w, const float* b, T* out, int nimg, int H,
                                              int W, int C, float eps, hipStream_t s);
 template <typename T> int launch_layernorm_rows(const T* x, const float* w, const float* b, T* out, int64_t rows,

@@ -45,57 +45,26 @@ int launch_stem_ln(const T* x, int64_t sb, int64_t sc, int64_t sy, int64_t sx, c
   return -3;
 }
 
-template <typename T, int C>
-static int launch_dw_c(const T* x, const float* wdw, const float* bdw, const float* lnw, const float* lnb, T* y,
-                       int nimg, int H, int W, float eps, hipStream_t s) {
-  constexpr int TILES = (C == 96) ? 2 : 1;
-  constexpr int TPB = C * TILES;
-  constexpr size_t LDS = (size_t)TILES * 49 * C * 4 + (size_t)TILES * 49 * 2 * 4;
-  if (LDS > 64 * 1024) GCV_ENSURE_LDS((dwconv7_ln_kernel<T, C>), LDS);
-  const int tiles = nimg * cdiv(H, 7) * cdiv(W, 7);
-  hipLaunchKernelGGL((dwconv7_ln_kernel<T, C>), dim3(cdiv(tiles, TILES)), dim3(TPB), LDS, s, x, wdw, bdw, lnw, lnb, y,
-                     nimg, H, W, eps);
-  GCV_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
+// The tile kinds of the dw7x7 + LayerNorm (dw_select, dwconv_impl.h): the generic kernel and the whole-map kernels of
+// S x S maps, launched with plan p
 template <typename T>
-int launch_dwconv7_ln(const T* x, const float* wdw, const float* bdw, const float* lnw, const float* lnb, T* y,
-                      int nimg, int H, int W, int C, float eps, hipStream_t s) {
-  GCV_REQUIRE(nimg > 0 && H > 0 && W > 0, "dwconv: empty");
-  // the rolling-strip kernel covers every ConvNeXt-T shape but the 3x3 map of the 112-px pass
-  // (GCV_DWCONV_GENERIC=1: A/B switch, the generic tile kernel everywhere)
-  static const bool generic = exp_env("GCV_DWCONV_GENERIC") != nullptr;
-  if (!generic && dwconv_roll_applicable<T>(H, W, C) &&
-      ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15u) == 0)
-    return launch_dwconv7_ln_roll<T>(x, wdw, bdw, lnw, lnb, y, nimg, H, W, C, eps, s);
-  if (!generic && C == 768 && H == W && H <= 4) {          // stage-3 maps of small inputs (3 x 3 in the 112-pixel pass)
-#define GCV_DW_TINY(S)                                                                                              \
-    if (H == S) {                                                                                                   \
-      hipLaunchKernelGGL((dwconv7_ln_tiny_kernel<T, 768, S>), dim3(nimg), dim3(768), 0, s, x, wdw, bdw, lnw, lnb, y, eps); \
-      GCV_CHECK_HIP(hipGetLastError());                                                                             \
-      return 0;                                                                                                     \
-    }
-    GCV_DW_TINY(1) GCV_DW_TINY(2) GCV_DW_TINY(3) GCV_DW_TINY(4)
-#undef GCV_DW_TINY
-  }
-  if (C == 1536 && H == W && H <= 4) {                      // ConvNeXt-L: two channels per lane (dwconv_pair.h)
-#define GCV_DW_TINY2(S)                                                                                              \
-    if (H == S) {                                                                                                   \
-      hipLaunchKernelGGL((dwconv7_ln_tiny2_kernel<T, 1536, S>), dim3(nimg), dim3(768), 0, s, x, wdw, bdw, lnw, lnb, y, eps); \
-      GCV_CHECK_HIP(hipGetLastError());                                                                             \
-      return 0;                                                                                                     \
-    }
-    GCV_DW_TINY2(1) GCV_DW_TINY2(2) GCV_DW_TINY2(3) GCV_DW_TINY2(4)
-#undef GCV_DW_TINY2
-  }
-  switch (C) {
-    case 96:  return launch_dw_c<T, 96>(x, wdw, bdw, lnw, lnb, y, nimg, H, W, eps, s);
-    case 192: return launch_dw_c<T, 192>(x, wdw, bdw, lnw, lnb, y, nimg, H, W, eps, s);
-    case 384: return launch_dw_c<T, 384>(x, wdw, bdw, lnw, lnb, y, nimg, H, W, eps, s);
-    case 768: return launch_dw_c<T, 768>(x, wdw, bdw, lnw, lnb, y, nimg, H, W, eps, s);
-  }
-  set_error("dwconv7_ln: C must be one of 96/192/384/768 (1536: 7-pixel-wide maps, or up to 4 x 4, only)");
+int launch_dw_tile(const DwPlan& p, const T* x, const float* wdw, const float* bdw, const float* lnw, const float* lnb,
+                   T* y, int nimg, int H, int W, float eps, hipStream_t s) {
+  auto tile = [&](auto k) { return dw_launch(p, k, s, x, wdw, bdw, lnw, lnb, y, nimg, H, W, eps); };
+  auto tiny = [&](auto k) { return dw_launch(p, k, s, x, wdw, bdw, lnw, lnb, y, eps); };
+  if (p.kind == DwKind::Tile && p.C == 96) return tile(dwconv7_ln_kernel<T, 96>);
+  if (p.kind == DwKind::Tile && p.C == 192) return tile(dwconv7_ln_kernel<T, 192>);
+  if (p.kind == DwKind::Tile && p.C == 384) return tile(dwconv7_ln_kernel<T, 384>);
+  if (p.kind == DwKind::Tile && p.C == 768) return tile(dwconv7_ln_kernel<T, 768>);
+  if (p.kind == DwKind::Tiny && p.n == 1) return tiny(dwconv7_ln_tiny_kernel<T, 768, 1>);
+  if (p.kind == DwKind::Tiny && p.n == 2) return tiny(dwconv7_ln_tiny_kernel<T, 768, 2>);
+  if (p.kind == DwKind::Tiny && p.n == 3) return tiny(dwconv7_ln_tiny_kernel<T, 768, 3>);
+  if (p.kind == DwKind::Tiny && p.n == 4) return tiny(dwconv7_ln_tiny_kernel<T, 768, 4>);
+  if (p.kind == DwKind::TinyPair && p.n == 1) return tiny(dwconv7_ln_tiny2_kernel<T, 1536, 1>);
+  if (p.kind == DwKind::TinyPair && p.n == 2) return tiny(dwconv7_ln_tiny2_kernel<T, 1536, 2>);
+  if (p.kind == DwKind::TinyPair && p.n == 3) return tiny(dwconv7_ln_tiny2_kernel<T, 1536, 3>);
+  if (p.kind == DwKind::TinyPair && p.n == 4) return tiny(dwconv7_ln_tiny2_kernel<T, 1536, 4>);
+  set_error("dwconv7_ln: not a tile-kind plan");
   return -3;
 }
 
@@ -287,8 +256,8 @@ template <typename T> int launch_preprocess(const unsigned char* u8, T* out, int
 #define GCV_INSTANTIATE_KERNELS(T)                                                                                    \
   template int launch_stem_ln<T>(const T*, int64_t, int64_t, int64_t, int64_t, const float*, const float*,            \
                                  const float*, const float*, T*, int, int, int, float, hipStream_t, int);             \
-  template int launch_dwconv7_ln<T>(const T*, const float*, const float*, const float*, const float*, T*, int, int,   \
-                                    int, int, float, hipStream_t);                                                    \
+  template int launch_dw_tile<T>(const DwPlan&, const T*, const float*, const float*, const float*, const float*, T*, \
+                                 int, int, int, float, hipStream_t);                                                  \
   template int launch_ln_patchify<T>(const T*, const float*, const float*, T*, int, int, int, int, float, hipStream_t); \
   template int launch_layernorm_rows<T>(const T*, const float*, const float*, T*, int64_t, int, float, hipStream_t);  \
   template int launch_pool_ln<T>(const T*, const float*, const float*, T*, int, int, int, float, hipStream_t, int, int, int); \

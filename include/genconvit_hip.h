@@ -247,6 +247,10 @@ int gcv_k_stem_ln_c(int dtype, const void* x, int64_t sb, int64_t sc, int64_t sy
                     float eps, gcv_stream s);
 int gcv_k_dwconv7_ln(int dtype, const void* x, const float* wdw, const float* bdw, const float* lnw,
                      const float* lnb, void* y, int nimg, int H, int W, int C, float eps, gcv_stream s);
+/* Test query: the kernel and grid that gcv_k_dwconv7_ln picks for nimg H x W x C images, x and y 16-byte aligned or not.
+ * out5 = {kind (0 tile, 1 tiny, 2 tiny-pair, 3 roll, 4 mfma, 5 pair), workgroups, threads per workgroup, dynamic LDS bytes,
+ * rows per band (roll, mfma, pair; else 0)}; or the launcher's error.  No HIP call: works without a GPU. */
+int gcv_dw_plan(int dtype, int nimg, int H, int W, int C, int aligned, int* out5);
 int gcv_k_ln_patchify(int dtype, const void* x, const float* w, const float* b, void* out, int nimg, int H, int W,
                       int C, float eps, gcv_stream s);
 int gcv_k_layernorm_rows(int dtype, const void* x, const float* w, const float* b, void* out, int64_t rows, int C,

@@ -99,10 +99,10 @@ def _ln2d(x, w, b, eps):
 
 
 # Launch-geometry thresholds of the HIP path that decide WHERE it rounds in 16-bit storage.  They are the oracle's own copy
-# (this file shares no table with the product); tests/test_host_cpu.py parses the product headers and asserts they agree.
+# (this file shares no table with the product); tests/test_host_cpu.py asserts they agree with the product.
 FUSED_LNP_MIN_TOKENS = 65536     # csrc/fused_mlp.h fused_mlp_res_applies: C = 96 launches of at least this many tokens run the
                                  # LDS-resident MLP, the only C = 96 kernel with the LayerNorm-patchify epilogue
-DW_MFMA_MIN_IMAGE_ROWS = 14 * 256   # csrc/dwconv_roll_impl.h long_bands: images x rows of a C = 96 / 56-pixel dw launch from
+DW_MFMA_MIN_IMAGE_ROWS = 14 * 256   # csrc/dwconv_impl.h kDwMfmaMinImageRows: images x rows of a C = 96 / 56-pixel dw launch from
                                     # which the taps run on the matrix pipe (as a 16-bit MFMA operand)
 
 

@@ -56,26 +56,84 @@ def test_product_never_imports_the_oracle():
                 assert not re.search(r"^\s*(from|import)\s+oracle\b", src, re.M), f"{f} imports the oracle"
 
 
-def test_oracle_dispatch_thresholds_equal_the_product_headers():
+DW_KINDS = ["tile", "tiny", "tiny_pair", "roll", "mfma", "pair"]    # gcv_dw_plan's kind codes (include/genconvit_hip.h)
+
+
+def _dw_plan(dt, nimg, H, W, C, aligned=1):
+    """gcv_dw_plan: (kind, grid, block, lds, band_rows) of a gcv_k_dwconv7_ln launch, or (rc, last error)."""
+    import ctypes
+    from genconvit_amd import _lib
+    dtype = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}[dt]
+    out = (ctypes.c_int * 5)()
+    rc = _lib.load().gcv_dw_plan(_lib.dtype_code(dtype), nimg, H, W, C, aligned, out)
+    if rc:
+        return rc, _lib.last_error()
+    return (DW_KINDS[out[0]],) + tuple(out[1:])
+
+
+def test_oracle_dispatch_thresholds_equal_the_product():
     """The same-dtype restatement rounds where the HIP path rounds, and two of those places depend on launch geometry:
-    the C = 96 LayerNorm-patchify epilogue (fused_mlp_res_applies) and the matrix-pipe depthwise taps (long_bands).  The
-    oracle keeps its own constants; this asserts they are what the product headers compute."""
+    the C = 96 LayerNorm-patchify epilogue (fused_mlp_res_applies) and the matrix-pipe depthwise taps.  The oracle keeps
+    its own constants; this asserts they are what the product computes."""
     from oracle import cpu_ref
     csrc = os.path.join(REPO, "genconvit_amd", "csrc")
     src = open(os.path.join(csrc, "fused_mlp.h")).read()
     m = re.search(r"fused_mlp_res_applies\(int C, int64_t M\)\s*\{\s*return C == 96 && M >= ([0-9 *]+);", src)
     assert m, "fused_mlp_res_applies changed shape: update the oracle's Launch rules with it"
     assert eval(m.group(1)) == cpu_ref.FUSED_LNP_MIN_TOKENS
-    src = open(os.path.join(csrc, "dwconv_roll_impl.h")).read()
-    m = re.search(r"const bool long_bands = \(int64_t\)nimg \* H >= ([0-9 *]+);", src)
-    assert m, "the long_bands rule changed shape"
-    assert eval(m.group(1)) == cpu_ref.DW_MFMA_MIN_IMAGE_ROWS
-    assert re.search(r"GCV_DWM\(96, 8\);\s*#ifdef GCV_DWM_ALL", src), "matrix-pipe dw kernel: only C = 96 / 56 px is dispatched"
+    # the matrix-pipe dw kernel runs 16-bit C = 96 / 56-pixel-wide launches of DW_MFMA_MIN_IMAGE_ROWS image rows (images x H)
+    # and more, and nothing else
+    for nimg in range(1, 130):
+        for H in (1, 28, 56, 57, 112):
+            for dt in ("f16", "bf16"):
+                want = nimg * H >= cpu_ref.DW_MFMA_MIN_IMAGE_ROWS
+                assert (_dw_plan(dt, nimg, H, 56, 96)[0] == "mfma") == want, (dt, nimg, H)
+            assert _dw_plan("f32", nimg, H, 56, 96)[0] != "mfma"
+        for dt in ("f32", "f16", "bf16"):
+            for C in (96, 192, 384, 768, 1536):
+                for H in (1, 3, 7, 14, 28, 56):
+                    if (C, H) != (96, 56):
+                        assert _dw_plan(dt, nimg, H, H, C)[0] != "mfma", (dt, nimg, C, H)
     # and the rules as the restatement applies them: ED's two passes are one launch (B = 11 -> 68 992 tokens: fused, B = 10
     # -> 62 720: not), the matrix-pipe taps need 64 images of 56 rows in one dw launch
     la = cpu_ref.Launch(2 * 11 * 3136, 22)
     assert la.stage0_tokens >= cpu_ref.FUSED_LNP_MIN_TOKENS > 2 * 10 * 3136
     assert 63 * 56 < cpu_ref.DW_MFMA_MIN_IMAGE_ROWS <= 64 * 56
+
+
+def test_dw_plan_table():
+    """The depthwise 7x7 + LayerNorm launch, pinned: kernel kind, workgroups, threads, dynamic LDS bytes and rows per band
+    of every dw launch of the ConvNeXt-T and ConvNeXt-L ED and VAE networks (both VAE schedules launch the same shapes) at
+    B = 1 ... 256, of the GPU kernel tests, of unaligned operands and of the error cases, as recorded from the launcher
+    before its choice moved into one plan (tests/golden/dw_plan.json)."""
+    import json
+    with open(os.path.join(REPO, "tests", "golden", "dw_plan.json")) as f:
+        table = {tuple(r[:6]): r[6:] for r in json.load(f)["rows"]}
+    need = set()
+    for dt in ("f32", "f16", "bf16"):
+        for widths in ((96, 192, 384, 768), (192, 384, 768, 1536)):
+            for B in (1, 32, 33, 64, 67, 128, 256):
+                for i, C in enumerate(widths):
+                    need |= {(dt, 2 * B, 56 >> i, 56 >> i, C, 1),      # ED: both passes in one launch
+                             (dt, B, 56 >> i, 56 >> i, C, 1),          # VAE: backbone(x), backbone(x_hat)
+                             (dt, B, 28 >> i, 28 >> i, C, 1)}
+        for C, H, n in [(96, 56, 2), (96, 28, 3), (192, 28, 2), (192, 14, 1), (384, 14, 2), (384, 7, 3), (768, 7, 2),
+                        (768, 3, 3), (768, 1, 5), (768, 2, 3), (768, 4, 2), (96, 56, 17), (384, 14, 70), (96, 56, 64),
+                        (96, 56, 100),                                   # test_kernels_gpu.py: test_dwconv7x7_layernorm
+                        (192, 56, 3), (384, 28, 3), (768, 14, 5), (1536, 7, 3), (1536, 7, 600), (1536, 3, 3),
+                        (1536, 1, 2), (1536, 4, 2)]:                     # test_large_gpu.py
+            need.add((dt, n, H, H, C, 1))
+    assert need <= set(table), sorted(need - set(table))[:5]
+    kinds = {r[1] for r in table.values()}
+    assert kinds == set(DW_KINDS) | {None}, kinds
+    for key, (rc, *want) in table.items():
+        got = _dw_plan(*key)
+        if rc:
+            assert got[0] == rc, (key, got)
+            if rc == -3:
+                assert "C must be one of" in got[1], got
+        else:
+            assert got == tuple(want), (key, got, want)
 
 
 def test_isa_report_checks_on_synthetic_assembly(tmp_path):
