@@ -58,6 +58,11 @@ SIGNATURES = {
     "gcv_vae_explain": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gcv_genconvit_explain": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p]),
+    "gcv_ed_explain_at": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gcv_vae_explain_at": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
+    "gcv_genconvit_explain_at": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_void_p]),
     "gcv_comm_available": (c_int, []),
     "gcv_comm_count": (c_int, [c_void_p]),
     "gcv_comm_unique_id": (c_int, [c_void_p]),
@@ -331,35 +336,46 @@ class Handle:
             raise GenConViTHipError(f"target must hold one class per frame ({B}), got {t.numel()}")
         return t
 
-    def ed_explain(self, x, target=None, upsample=True):
-        """ED forward + Grad-CAM.  Returns (logits (B,2), cam (B,2,7,7) fp32 [reconstruction pass, original pass],
-        cam224 (B,224,224) of the original pass or None)."""
+    def ed_explain(self, x, target=None, upsample=True, layer="s3"):
+        """ED forward + Grad-CAM.  Returns (logits (B,2), cam (B,2,7,7) fp32 [reconstruction pass, original pass] — (B,2,14,14)
+        at ``layer`` "s2" —, cam224 (B,224,224) of the original pass or None).  ``layer``: see ``explain_layer``."""
         import torch
         x = self._check_x(x)
         B = x.shape[0]
         t = self._target(target, B, x.device)
+        n, at = explain_layer(layer)
+        side = 7 if n == 3 else 14
         out = torch.empty((B, 2), dtype=torch.float32, device=x.device)
-        cam = torch.empty((B, 2, 7, 7), dtype=torch.float32, device=x.device)
+        cam = torch.empty((B, 2, side, side), dtype=torch.float32, device=x.device)
         up = torch.empty((B, 224, 224), dtype=torch.float32, device=x.device) if upsample else None
-        check(self.lib.gcv_ed_explain(self._h, x.data_ptr(), B, t.data_ptr() if t is not None else None, out.data_ptr(),
-                                      cam.data_ptr(), up.data_ptr() if up is not None else None,
-                                      current_stream_ptr(x.device)), "gcv_ed_explain")
+        tp, upp = t.data_ptr() if t is not None else None, up.data_ptr() if up is not None else None
+        if at:
+            check(self.lib.gcv_ed_explain_at(self._h, x.data_ptr(), B, tp, n, out.data_ptr(), cam.data_ptr(), upp,
+                                             current_stream_ptr(x.device)), "gcv_ed_explain_at")
+        else:
+            check(self.lib.gcv_ed_explain(self._h, x.data_ptr(), B, tp, out.data_ptr(), cam.data_ptr(), upp,
+                                          current_stream_ptr(x.device)), "gcv_ed_explain")
         return out, cam, up
 
-    def vae_explain(self, x, eps, target=None, upsample=True):
-        """VAE forward + Grad-CAM.  Returns (logits (B,2), cam (B,58) fp32 = [7x7 of x at 224 px, 3x3 of x_hat at 112 px],
-        cam224 (B,224,224) of x or None)."""
+    def vae_explain(self, x, eps, target=None, upsample=True, layer="s3"):
+        """VAE forward + Grad-CAM.  Returns (logits (B,2), cam (B,58) fp32 = [7x7 of x at 224 px, 3x3 of x_hat at 112 px] —
+        (B,245) = [14x14, 7x7] at ``layer`` "s2" —, cam224 (B,224,224) of x or None).  ``layer``: see ``explain_layer``."""
         import torch
         x = self._check_x(x)
         B = x.shape[0]
         eps = self._check_eps(eps, B)
         t = self._target(target, B, x.device)
+        n, at = explain_layer(layer)
         out = torch.empty((B, 2), dtype=torch.float32, device=x.device)
-        cam = torch.empty((B, 58), dtype=torch.float32, device=x.device)
+        cam = torch.empty((B, 58 if n == 3 else 245), dtype=torch.float32, device=x.device)
         up = torch.empty((B, 224, 224), dtype=torch.float32, device=x.device) if upsample else None
-        check(self.lib.gcv_vae_explain(self._h, x.data_ptr(), eps.data_ptr(), B, t.data_ptr() if t is not None else None,
-                                       out.data_ptr(), cam.data_ptr(), up.data_ptr() if up is not None else None,
-                                       current_stream_ptr(x.device)), "gcv_vae_explain")
+        tp, upp = t.data_ptr() if t is not None else None, up.data_ptr() if up is not None else None
+        if at:
+            check(self.lib.gcv_vae_explain_at(self._h, x.data_ptr(), eps.data_ptr(), B, tp, n, out.data_ptr(), cam.data_ptr(),
+                                              upp, current_stream_ptr(x.device)), "gcv_vae_explain_at")
+        else:
+            check(self.lib.gcv_vae_explain(self._h, x.data_ptr(), eps.data_ptr(), B, tp, out.data_ptr(), cam.data_ptr(), upp,
+                                           current_stream_ptr(x.device)), "gcv_vae_explain")
         return out, cam, up
 
     def _check_eps(self, eps, B):
@@ -411,9 +427,24 @@ def genconvit_forward(h_ed: "Handle", h_vae: "Handle", x, eps):
     return out
 
 
-def genconvit_explain(h_ed: "Handle", h_vae: "Handle", x, eps, target=None, upsample=True):
+EXPLAIN_LAYERS = {"s3": 3, "s2": 2}
+
+
+def explain_layer(layer):
+    """The ConvNeXt stage an explain call takes its maps at, as (stage number, whether the call goes through
+    ``gcv_*_explain_at``).  "s3" (the default): the last stage, through ``gcv_*_explain``; "s2": the output of stage 2,
+    14 x 14 cells; the integers 3 / 2 name the same stages and always go through ``gcv_*_explain_at``."""
+    if isinstance(layer, str) and layer in EXPLAIN_LAYERS:
+        return EXPLAIN_LAYERS[layer], layer != "s3"
+    if isinstance(layer, int) and not isinstance(layer, bool) and layer in (2, 3):
+        return layer, True
+    raise ValueError(f"unknown explain layer {layer!r}: accepted values are 's3' and 's2'")
+
+
+def genconvit_explain(h_ed: "Handle", h_vae: "Handle", x, eps, target=None, upsample=True, layer="s3"):
     """``genconvit_forward`` + Grad-CAM of both networks (``gcv_genconvit_explain``).  Returns (logits (2B,2),
-    cam_ed (B,2,7,7), cam_vae (B,58), cam224 (2B,224,224) or None) — cam224 rows in the logits' row order."""
+    cam_ed (B,2,7,7), cam_vae (B,58), cam224 (2B,224,224) or None) — cam224 rows in the logits' row order.  At ``layer``
+    "s2" (``explain_layer``): cam_ed (B,2,14,14), cam_vae (B,245)."""
     import torch
     x = h_ed._check_x(x)
     B = x.shape[0]
@@ -422,13 +453,19 @@ def genconvit_explain(h_ed: "Handle", h_vae: "Handle", x, eps, target=None, upsa
     eps = h_ed._check_eps(eps, B)
     t = h_ed._target(target, B, x.device)
     out = torch.empty((2 * B, 2), dtype=torch.float32, device=x.device)
-    cam = torch.empty((B * (98 + 58),), dtype=torch.float32, device=x.device)
+    n, at = explain_layer(layer)
+    side, ne, nv = (7, 98, 58) if n == 3 else (14, 392, 245)
+    cam = torch.empty((B * (ne + nv),), dtype=torch.float32, device=x.device)
     up = torch.empty((2 * B, 224, 224), dtype=torch.float32, device=x.device) if upsample else None
-    check(h_ed.lib.gcv_genconvit_explain(h_ed._h, h_vae._h, x.data_ptr(), eps.data_ptr(), B,
-                                         t.data_ptr() if t is not None else None, out.data_ptr(), cam.data_ptr(),
-                                         up.data_ptr() if up is not None else None, current_stream_ptr(x.device)),
-          "gcv_genconvit_explain")
-    return out, cam[:B * 98].view(B, 2, 7, 7), cam[B * 98:].view(B, 58), up
+    tp, upp = t.data_ptr() if t is not None else None, up.data_ptr() if up is not None else None
+    if at:
+        check(h_ed.lib.gcv_genconvit_explain_at(h_ed._h, h_vae._h, x.data_ptr(), eps.data_ptr(), B, tp, n, out.data_ptr(),
+                                                cam.data_ptr(), upp, current_stream_ptr(x.device)),
+              "gcv_genconvit_explain_at")
+    else:
+        check(h_ed.lib.gcv_genconvit_explain(h_ed._h, h_vae._h, x.data_ptr(), eps.data_ptr(), B, tp, out.data_ptr(),
+                                             cam.data_ptr(), upp, current_stream_ptr(x.device)), "gcv_genconvit_explain")
+    return out, cam[:B * ne].view(B, 2, side, side), cam[B * ne:].view(B, nv), up
 
 
 class Comm:

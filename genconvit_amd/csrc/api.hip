@@ -76,6 +76,7 @@ bool tap_name_known(const std::string& name, int arch) {
       const std::string p = std::string(net) + ".bb.";
       n.insert(p + "stem");
       n.insert(p + "pool");
+      n.insert(std::string(net) + ".explain.alpha2");   // explain at stage 2: alpha (2 passes, B, C2) fp32
       for (int i = 0; i < 4; ++i) {
         if (i > 0) n.insert(p + "s" + std::to_string(i) + ".down_in");
         for (int j = 0; j < depths[i]; ++j) n.insert(p + "s" + std::to_string(i) + ".b" + std::to_string(j));
@@ -342,22 +343,39 @@ int gcv_ed_forward(gcv_handle* h, const void* x_nchw, int batch, float* logits, 
   return h->net->ed_forward(x_nchw, batch, logits, (hipStream_t)stream);
 }
 
-int gcv_ed_explain(gcv_handle* h, const void* x_nchw, int batch, const int* target, float* logits, float* cam_raw,
-                   float* cam224, gcv_stream stream) {
+// floats of one frame's maps: ED two passes of one map size, VAE the 224-pixel and the 112-pixel pass
+static int cam_ld_ed(int layer) { return layer == 2 ? 2 * 196 : 2 * 49; }
+static int cam_ld_vae(int layer) { return layer == 2 ? 196 + 49 : 49 + 9; }
+#define GCV_REQUIRE_LAYER(layer) GCV_REQUIRE((layer) == 2 || (layer) == 3, "layer must be 2 (stage-2 output) or 3 (stage-3 output)")
+
+int gcv_ed_explain_at(gcv_handle* h, const void* x_nchw, int batch, const int* target, int layer, float* logits,
+                      float* cam_raw, float* cam224, gcv_stream stream) {
   GCV_REQUIRE(h, "null handle");
+  GCV_REQUIRE_LAYER(layer);
   DeviceGuard g(h->net->device);
   Explain ex;
-  ex.target = target; ex.cam = cam_raw; ex.cam_ld = 2 * 49; ex.cam224 = cam224;
+  ex.target = target; ex.cam = cam_raw; ex.cam_ld = cam_ld_ed(layer); ex.cam224 = cam224; ex.layer = layer;
   return h->net->ed_explain(x_nchw, batch, logits, ex, (hipStream_t)stream);
+}
+
+int gcv_ed_explain(gcv_handle* h, const void* x_nchw, int batch, const int* target, float* logits, float* cam_raw,
+                   float* cam224, gcv_stream stream) {
+  return gcv_ed_explain_at(h, x_nchw, batch, target, 3, logits, cam_raw, cam224, stream);
+}
+
+int gcv_vae_explain_at(gcv_handle* h, const void* x_nchw, const float* eps, int batch, const int* target, int layer,
+                       float* logits, float* cam_raw, float* cam224, gcv_stream stream) {
+  GCV_REQUIRE(h, "null handle");
+  GCV_REQUIRE_LAYER(layer);
+  DeviceGuard g(h->net->device);
+  Explain ex;
+  ex.target = target; ex.cam = cam_raw; ex.cam_ld = cam_ld_vae(layer); ex.cam224 = cam224; ex.layer = layer;
+  return h->net->vae_explain(x_nchw, eps, batch, logits, ex, (hipStream_t)stream);
 }
 
 int gcv_vae_explain(gcv_handle* h, const void* x_nchw, const float* eps, int batch, const int* target, float* logits,
                     float* cam_raw, float* cam224, gcv_stream stream) {
-  GCV_REQUIRE(h, "null handle");
-  DeviceGuard g(h->net->device);
-  Explain ex;
-  ex.target = target; ex.cam = cam_raw; ex.cam_ld = 49 + 9; ex.cam224 = cam224;
-  return h->net->vae_explain(x_nchw, eps, batch, logits, ex, (hipStream_t)stream);
+  return gcv_vae_explain_at(h, x_nchw, eps, batch, target, 3, logits, cam_raw, cam224, stream);
 }
 
 // gcv_genconvit_forward / gcv_genconvit_explain: ex_ed / ex_vae null for the plain forward
@@ -419,16 +437,24 @@ int gcv_genconvit_forward(gcv_handle* he, gcv_handle* hv, const void* x_nchw, co
   return genconvit_run(he, hv, x_nchw, eps, batch, logits, stream, nullptr, nullptr);
 }
 
-int gcv_genconvit_explain(gcv_handle* he, gcv_handle* hv, const void* x_nchw, const float* eps, int batch,
-                          const int* target, float* logits_2Bx2, float* cam_raw, float* cam224, gcv_stream stream) {
+int gcv_genconvit_explain_at(gcv_handle* he, gcv_handle* hv, const void* x_nchw, const float* eps, int batch,
+                             const int* target, int layer, float* logits_2Bx2, float* cam_raw, float* cam224,
+                             gcv_stream stream) {
   GCV_REQUIRE(cam_raw && batch >= 1, "null map output");
+  GCV_REQUIRE_LAYER(layer);
   Explain ee, ev;
   ee.target = ev.target = target;
-  ee.cam = cam_raw; ee.cam_ld = 2 * 49;
-  ev.cam = cam_raw + (size_t)batch * 2 * 49; ev.cam_ld = 49 + 9;
+  ee.layer = ev.layer = layer;
+  ee.cam = cam_raw; ee.cam_ld = cam_ld_ed(layer);
+  ev.cam = cam_raw + (size_t)batch * cam_ld_ed(layer); ev.cam_ld = cam_ld_vae(layer);
   ee.cam224 = cam224;
   ev.cam224 = cam224 ? cam224 + (size_t)batch * 224 * 224 : nullptr;
   return genconvit_run(he, hv, x_nchw, eps, batch, logits_2Bx2, stream, &ee, &ev);
+}
+
+int gcv_genconvit_explain(gcv_handle* he, gcv_handle* hv, const void* x_nchw, const float* eps, int batch,
+                          const int* target, float* logits_2Bx2, float* cam_raw, float* cam224, gcv_stream stream) {
+  return gcv_genconvit_explain_at(he, hv, x_nchw, eps, batch, target, 3, logits_2Bx2, cam_raw, cam224, stream);
 }
 
 int gcv_comm_available(void) {

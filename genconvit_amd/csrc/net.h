@@ -56,12 +56,14 @@ bool tap_name_known(const std::string& name, int arch);
 
 // ---- explain (gcv_*_explain, include/genconvit_hip.h) ---------------------------------------------------------------
 // Grad-CAM request of one network's forward: target (B) device ints or null (argmax), maps at cam + b * cam_ld (the
-// network's layout), cam224 (B, 224, 224) nullable.
+// network's layout), cam224 (B, 224, 224) nullable.  layer: the ConvNeXt stage whose output the maps are taken at: 3 (the
+// heads' backward alone, cam.h) or 2 (plus the backward of stage 3 and of the down-sampling in front of it, cam_bwd.h).
 struct Explain {
   const int* target = nullptr;
   float* cam = nullptr;
   int cam_ld = 0;
   float* cam224 = nullptr;
+  int layer = 3;
 };
 
 // ---- ConvNeXt backbone architecture (gcv_create_arch) ------------------------

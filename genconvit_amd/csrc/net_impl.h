@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "cam.h"
+#include "cam_bwd.h"
 #include "cnx_mlp.h"
 #include "gemm.h"
 #include "kernels.h"
@@ -108,6 +109,9 @@ template <typename T> struct CnxW {
   struct { float *ln_w, *ln_b, *b; T* w; } down[3];
   float *head_lnw, *head_lnb, *head_fc_b;
   T* head_fc_w;
+  // explain at stage 2 (cam_bwd.h): the transposes of stage 3's fc1 (C3, 4 C3) / fc2 (4 C3, C3) and of the stage 2 -> 3
+  // down-sampling weight (4 C2, C3), so that dY . W runs through the (N, K)-row GEMMs
+  T *bwd_w1t[3], *bwd_w2t[3], *bwd_downt;
 };
 template <typename T> struct HeadW {
   T* fc_w;        // (500, 2000)
@@ -136,6 +140,11 @@ template <typename T> struct VaeW {
   HeadW<T> head;
 };
 
+// explain at stage 2: a segment's stage-2 output and the inputs of its stage-3 blocks, kept instead of overwritten
+template <typename T> struct Stage3In {
+  const T* s2 = nullptr;
+  const T* x[3] = {nullptr, nullptr, nullptr};
+};
 template <typename T> struct Seg {
   const T* x;
   int64_t sb, sc, sy, sx;   // element strides of the (n,3,H,W) input view
@@ -145,6 +154,7 @@ template <typename T> struct Seg {
   int act;
   T* pre = nullptr;           // explain: the backbone logits before `act`, at pre + i*out_ld (else null)
   const T** s3 = nullptr;     // explain: receives this segment's stage-3 tokens (the pass then keeps its buffers)
+  Stage3In<T>* in3 = nullptr; // explain at stage 2: receives what stage 3 read (its blocks then write a buffer each)
 };
 
 template <typename T> struct NetImpl : NetBase {
@@ -330,6 +340,27 @@ template <typename T> struct NetImpl : NetBase {
     GCV_UP(dst, st, c);
     return 0;
   }
+  // nn.Linear weight (rows, cols) -> its transpose (cols, rows) in T
+  int up_cast_t(const TensorMap& w, const std::string& name, int rows, int cols, WeightStore& st, T*& dst) {
+    std::vector<float> v;
+    GCV_TRY(fetch(w, name, (int64_t)rows * cols, v));
+    std::vector<T> o((size_t)rows * cols);
+    for (int r = 0; r < rows; ++r)
+      for (int c = 0; c < cols; ++c) o[(size_t)c * rows + r] = host_cvt<T>(v[(size_t)r * cols + c]);
+    GCV_UP(dst, st, o);
+    return 0;
+  }
+  // Conv2d weight (Cout,Cin,2,2) -> ((ky,kx,ci), Cout) in T: the transpose of up_conv_gemm's pack
+  int up_conv_gemm_t(const TensorMap& w, const std::string& name, int cout, int cin, WeightStore& st, T*& dst) {
+    std::vector<float> v;
+    GCV_TRY(fetch(w, name, (int64_t)cout * cin * 4, v));
+    std::vector<T> o((size_t)cout * cin * 4);
+    for (int co = 0; co < cout; ++co)
+      for (int ci = 0; ci < cin; ++ci)
+        for (int q = 0; q < 4; ++q) o[((size_t)q * cin + ci) * cout + co] = host_cvt<T>(v[((size_t)co * cin + ci) * 4 + q]);
+    GCV_UP(dst, st, o);
+    return 0;
+  }
   // Conv2d weight (Cout,Cin,kh,kw) [* per-Cout scale] -> (Cout, (ky,kx,ci)) in T
   int up_conv_gemm(const TensorMap& w, const std::string& name, int cout, int cin, int kh, int kw,
                    const std::vector<float>* scale, WeightStore& st, T*& dst) {
@@ -430,6 +461,7 @@ template <typename T> struct NetImpl : NetBase {
         GCV_TRY(up_f32(w, d + "0.bias", Cp, st, o.down[i - 1].ln_b));
         GCV_TRY(up_conv_gemm(w, d + "1.weight", C, Cp, 2, 2, nullptr, st, o.down[i - 1].w));
         GCV_TRY(up_f32(w, d + "1.bias", C, st, o.down[i - 1].b));
+        if (i == 3) GCV_TRY(up_conv_gemm_t(w, d + "1.weight", C, Cp, st, o.bwd_downt));
       }
       for (int j = 0; j < A.depths[i]; ++j, ++bi) {
         const std::string b = p + "stages." + std::to_string(i) + ".blocks." + std::to_string(j) + ".";
@@ -453,6 +485,11 @@ template <typename T> struct NetImpl : NetBase {
         GCV_TRY(up_f32(w, b + "gamma", C, st, gamma));
         k.mlp = CnxMlpW<T>{mlp_kind(sizeof(T), C), w1, w2, b1, b2, gamma};
         GCV_TRY(pack_mlp(w, b + "mlp.fc2.weight", C, st, k.mlp));
+        if (i == 3) {
+          GCV_REQUIRE(j < 3, "stage 3 has at most 3 blocks");
+          GCV_TRY(up_cast_t(w, b + "mlp.fc1.weight", 4 * C, C, st, o.bwd_w1t[j]));
+          GCV_TRY(up_cast_t(w, b + "mlp.fc2.weight", C, 4 * C, st, o.bwd_w2t[j]));
+        }
       }
     }
     GCV_TRY(up_f32(w, p + "head.norm.weight", C3, st, o.head_lnw));
@@ -614,14 +651,25 @@ template <typename T> struct NetImpl : NetBase {
     const int C0 = A.dims[0], C3 = A.dims[3];
     // the widest GEMM operand is stage 0's (M, 4 C0) hidden tensor (and every later stage's is smaller)
     GCV_REQUIRE(M * 4 * C0 < (int64_t)1 << 31, "token count too large for 32-bit GEMM indexing");
-    bool saving = false;
-    for (int s = 0; s < nseg; ++s) saving = saving || segs[s].s3;
+    bool saving = false, save3 = false;
+    for (int s = 0; s < nseg; ++s) { saving = saving || segs[s].s3; save3 = save3 || segs[s].in3; }
+    for (int s = 0; s < nseg; ++s) GCV_REQUIRE(!save3 || (segs[s].in3 && segs[s].s3), "stage-3 inputs are kept for every segment or none");
+    GCV_REQUIRE(!save3 || A.depths[3] == 3, "stage 3 of three blocks");
     const size_t mk = arena.mark();
     T* X = arena.get<T>(M * C0);
     T* Y = arena.get<T>(M * C0);
     T* Hd = arena.get<T>(M * 4 * C0);
     T* Pool = arena.get<T>((int64_t)ntot * C3);
+    // explain at stage 2: the down-sampling GEMM and each stage-3 block write a buffer of their own, so that the stage-2
+    // output and every block's input outlive the pass (same kernels, same operands: only the output pointers differ)
+    T* X3[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (save3) {
+      int64_t M3 = 0;
+      for (int s = 0; s < nseg; ++s) M3 += (int64_t)segs[s].n * (h[s] / 8) * (wd[s] / 8);
+      for (int j = 0; j < 4; ++j) X3[j] = arena.get<T>(M3 * C3);
+    }
     if (!arena.dry && arena.overflow) { set_error("workspace arena too small: batch exceeds max_batch"); return -6; }
+    T* Xc = X;                    // the residual stream
 
     for (int s = 0; s < nseg; ++s) {
       const Seg<T>& g = segs[s];
@@ -657,6 +705,8 @@ template <typename T> struct NetImpl : NetBase {
             }));
           s = e;
         }
+        if (save3 && i == 3)
+          for (int s = 0; s < nseg; ++s) segs[s].in3->s2 = X + moff[s] * Cp;
         for (int s = 0; s < nseg; ++s) {
           h[s] /= 2;
           wd[s] /= 2;
@@ -665,7 +715,8 @@ template <typename T> struct NetImpl : NetBase {
         }
         M = newM;
         GemmArgs g{};
-        g.A = lnp_fused ? Hd : Y; g.lda = 4 * Cp; g.Wt = w.down[i - 1].w; g.C = X; g.ldc = C; g.bias = w.down[i - 1].b;
+        if (save3 && i == 3) Xc = X3[0];
+        g.A = lnp_fused ? Hd : Y; g.lda = 4 * Cp; g.Wt = w.down[i - 1].w; g.C = Xc; g.ldc = C; g.bias = w.down[i - 1].b;
         lnp_fused = false;
         g.M = (int)M; g.N = C; g.K = 4 * Cp; g.act = ACT_NONE; g.splitk = 1;
         if (tp) GCV_TRY(tap_bb(*tp, nseg, "s" + std::to_string(i) + ".down_in", 2, i, (const T*)g.A));
@@ -673,10 +724,15 @@ template <typename T> struct NetImpl : NetBase {
       }
       // the residual stream after block j, unless its epilogue went straight to the stage boundary (lnp_fused)
       auto tap_block = [&](int j) {
-        return tp && !lnp_fused ? tap_bb(*tp, nseg, "s" + std::to_string(i) + ".b" + std::to_string(j), 1, i, X) : 0;
+        return tp && !lnp_fused ? tap_bb(*tp, nseg, "s" + std::to_string(i) + ".b" + std::to_string(j), 1, i, Xc) : 0;
       };
       for (int j = 0; j < A.depths[i]; ++j, ++bi) {
         const CnxBlockW<T>& k = w.blk[bi];
+        T* Xn = Xc;               // the block's output: in place, unless its input is kept
+        if (save3 && i == 3) {
+          for (int s = 0; s < nseg; ++s) segs[s].in3->x[j] = Xc + moff[s] * C;
+          Xn = X3[j + 1];
+        }
         for (int s = 0; s < nseg;) {
           // neighbouring segments of one geometry (ED: reconstruction + original pass) are contiguous in the token
           // buffer: one launch over all their images (256 images fill the 256 CUs with whole-image row bands)
@@ -684,7 +740,7 @@ template <typename T> struct NetImpl : NetBase {
           int64_t mm = m[s];
           while (e < nseg && h[e] == h[s] && wd[e] == wd[s]) { nimg += segs[e].n; mm += m[e]; ++e; }
           GCV_TRY(run("cnx.dwconv7_ln", 2.0 * 49 * mm * C, 2.0 * sizeof(T) * (double)mm * C + 49.0 * C * 4, [&] {
-            return launch_dwconv7_ln<T>(X + moff[s] * C, k.dw_w, k.dw_b, k.ln_w, k.ln_b, Y + moff[s] * C, nimg, h[s],
+            return launch_dwconv7_ln<T>(Xc + moff[s] * C, k.dw_w, k.dw_b, k.ln_w, k.ln_b, Y + moff[s] * C, nimg, h[s],
                                         wd[s], C, 1e-6f, cur);
           }));
           s = e;
@@ -694,7 +750,8 @@ template <typename T> struct NetImpl : NetBase {
         LnpSpec l;
         const bool fuse = j == A.depths[i] - 1 && i < 3 && lnp_plan(l, k.mlp.kind, C, M, nseg, segn, h, wd);
         if (fuse) { l.w = w.down[i].ln_w; l.b = w.down[i].ln_b; l.eps = 1e-6f; }
-        GCV_TRY(launch_cnx_mlp<T>(*this, k.mlp, C, Y, X, fuse ? Hd : X, Hd, (int)M, fuse ? &l : nullptr, cur));
+        GCV_TRY(launch_cnx_mlp<T>(*this, k.mlp, C, Y, Xc, fuse ? Hd : Xn, Hd, (int)M, fuse ? &l : nullptr, cur));
+        Xc = Xn;
         lnp_fused = fuse;
         GCV_TRY(tap_block(j));
       }
@@ -715,9 +772,9 @@ template <typename T> struct NetImpl : NetBase {
         while (e < nseg && h[e] * wd[e] == h[s] * wd[s]) { nimg += segs[e].n; mm += m[e]; ++e; }
         GCV_TRY(run("cnx.pool_ln", 2.0 * mm * C3, sizeof(T) * (double)mm * C3, [&] {
           if (one_fc)
-            return launch_pool_ln<T>(X + moff[s] * C3, w.head_lnw, w.head_lnb, Pool, nimg, h[s] * wd[s], C3, 1e-6f, cur,
+            return launch_pool_ln<T>(Xc + moff[s] * C3, w.head_lnw, w.head_lnb, Pool, nimg, h[s] * wd[s], C3, 1e-6f, cur,
                                      segs[0].n, nseg, s);
-          return launch_pool_ln<T>(X + moff[s] * C3, w.head_lnw, w.head_lnb, Pool + (int64_t)no * C3, nimg, h[s] * wd[s],
+          return launch_pool_ln<T>(Xc + moff[s] * C3, w.head_lnw, w.head_lnb, Pool + (int64_t)no * C3, nimg, h[s] * wd[s],
                                    C3, 1e-6f, cur);
         }));
       }
@@ -746,7 +803,7 @@ template <typename T> struct NetImpl : NetBase {
     }
     // explain: stage 3 has no LayerNorm-patchify epilogue, so its last block always leaves its output in X
     for (int s = 0; s < nseg; ++s)
-      if (segs[s].s3) *segs[s].s3 = X + moff[s] * C3;
+      if (segs[s].s3) *segs[s].s3 = Xc + moff[s] * C3;
     if (!keep && !saving) arena.release(mk);
     return 0;
   }
@@ -775,7 +832,8 @@ template <typename T> struct NetImpl : NetBase {
   // tokens of pass p (hw[p] = side[p]^2 per image), their map at ex.cam + b * ex.cam_ld + off[p]
   int explain_tail(const CnxW<T>& bw, const HeadW<T>& hw, int act, int B, const float* part, const T* bbpre,
                    const float* logits, const T* const s3[2], const int hwp[2], const int side[2], const int off[2],
-                   int up_pass, const Explain& ex) {
+                   int up_pass, const Explain& ex, const Stage3In<T>* in3 = nullptr, const int* side2 = nullptr,
+                   const char* net = nullptr) {
     const int C3 = cnx_arch(arch).dims[3];
     float* dfeat = arena.get<float>((int64_t)B * 2000);
     float* dpool = arena.get<float>((int64_t)B * 2 * C3);
@@ -785,12 +843,109 @@ template <typename T> struct NetImpl : NetBase {
                 [&] { return launch_head_bwd<T>(ha, cur); }));
     GCV_TRY(run("explain.bb_fc_bwd", 2.0 * 2 * B * 1000 * C3, sizeof(T) * 1000.0 * C3 + 4.0 * B * (2000 + 2 * C3),
                 [&] { return launch_bb_bwd<T>(dfeat, bw.head_fc_w, dpool, 2 * B, C3, cur); }));
+    if (ex.layer == 2) return explain_tail_s2(bw, B, dpool, s3, side, side2, up_pass, ex, in3, net);
     CamArgs ca{};
     for (int q = 0; q < 2; ++q) { ca.A[q] = s3[q]; ca.hw[q] = hwp[q]; ca.side[q] = side[q]; ca.cam_off[q] = off[q]; }
     ca.npass = 2; ca.cam_ld = ex.cam_ld; ca.up_pass = up_pass; ca.lnw = bw.head_lnw; ca.dpool = dpool;
     ca.cam = ex.cam; ca.cam224 = ex.cam224; ca.eps = 1e-6f; ca.B = B;
     GCV_TRY(run("explain.cam", 4.0 * B * (hwp[0] + hwp[1]) * C3, sizeof(T) * (double)B * (hwp[0] + hwp[1]) * C3 +
                 (ex.cam224 ? 4.0 * B * 224 * 224 : 0.0), [&] { return launch_cam<T>(ca, C3, cur); }));
+    return 0;
+  }
+
+  // Grad-CAM at the output of stage 2 (cam_bwd.h): dpool (B, 2, C3) -> backward through pool + LayerNorm, stage 3's blocks
+  // and the down-sampling -> d A2 -> alpha, maps.  side3[p] / side2[p]: stage-3 / stage-2 map side of pass p; in3[p]: what
+  // the pass kept.  Gradient rows: pass 0's tokens, then pass 1's.  Maps of (b, p) at ex.cam + b * ex.cam_ld + (p ? side2[0]^2 : 0).
+  int explain_tail_s2(const CnxW<T>& bw, int B, const float* dpool, const T* const s3[2], const int side3[2],
+                      const int side2[2], int up_pass, const Explain& ex, const Stage3In<T>* in3, const char* net) {
+    const CnxArch& A = cnx_arch(arch);
+    const int C3 = A.dims[3], C2 = A.dims[2], nb = A.depths[3];
+    GCV_REQUIRE(in3 && side2 && net && nb == 3, "stage-3 inputs were not kept");
+    int hw3[2], tok0[2];
+    int64_t M = 0, M2 = 0, tok2[2];
+    for (int p = 0; p < 2; ++p) {
+      GCV_REQUIRE(side2[p] / 2 == side3[p], "stage-2 / stage-3 map sides");
+      hw3[p] = side3[p] * side3[p];
+      tok0[p] = (int)M; tok2[p] = M2;
+      M += (int64_t)B * hw3[p];
+      M2 += (int64_t)B * side2[p] * side2[p];
+    }
+    GCV_REQUIRE(M * 4 * C3 < (int64_t)1 << 31, "token count too large for 32-bit GEMM indexing");
+    float* G = arena.get<float>(M * C3);             // d logit / d (block output), then d (block input), in place
+    T* Gt = arena.get<T>(M * C3);                    // its row-scaled copy in T: the GEMM operand
+    float* invA = arena.get<float>(M + 8);
+    float* invB = arena.get<float>(M + 8);
+    float* Dh = arena.get<float>(M * 4 * C3);        // dz . W2 (M, 4 C3); later dx0 . W_down (M, 4 C2)
+    T* Pre = arena.get<T>(M * 4 * C3);               // hidden pre-activation, then dh * GELU' in place
+    T* Yb = arena.get<T>(M * C3);                    // the block's LayerNorm output, recomputed
+    float* Dl = arena.get<float>(M * C3);            // dpre . W1
+    float* Dw = arena.get<float>(M * C3);            // d (raw depthwise output)
+    float* dA2 = arena.get<float>(M2 * C2);
+    float* alpha = arena.get<float>((int64_t)2 * B * C2);
+    if (!arena.dry && arena.overflow) { set_error("workspace arena too small"); return -6; }
+
+    PoolLnBwdArgs pa{};
+    for (int p = 0; p < 2; ++p) { pa.A[p] = s3[p]; pa.hw[p] = hw3[p]; pa.tok0[p] = tok0[p]; }
+    pa.npass = 2; pa.B = B; pa.lnw = bw.head_lnw; pa.dpool = dpool; pa.dA = G; pa.eps = 1e-6f;
+    GCV_TRY(run("explain2.pool_ln_bwd", 4.0 * M * C3, (sizeof(T) + 4.0) * (double)M * C3,
+                [&] { return launch_pool_ln_bwd<T>(pa, C3, cur); }));
+    auto dgemm = [&](const char* tag, const T* a, const T* wt, float* out, int N, int K) {
+      GemmArgs g{};
+      g.A = a; g.lda = K; g.Wt = wt; g.partial = out; g.M = (int)M; g.N = N; g.K = K; g.act = ACT_NONE;
+      g.splitk = 1; g.k_per_split = K;
+      return gemm(tag, g, A_PLAIN, EPI_SPLITK);
+    };
+    int bi = A.nblocks() - nb;
+    for (int j = nb - 1; j >= 0; --j) {
+      const CnxBlockW<T>& k = bw.blk[bi + j];
+      GCV_TRY(run("explain2.scale_rows", 2.0 * M * C3, (sizeof(T) + 4.0) * (double)M * C3,
+                  [&] { return launch_scale_rows<T>(G, k.mlp.gamma, Gt, invA, (int)M, C3, cur); }));
+      GCV_TRY(dgemm("explain2.dz_w2", Gt, bw.bwd_w2t[j], Dh, 4 * C3, C3));
+      // the forward keeps neither the LayerNorm output nor the hidden pre-activation: the forward's own kernels again,
+      // in the forward's launch shape (both passes in one launch where their tokens are neighbours of one geometry)
+      const bool one = side3[0] == side3[1] && in3[1].x[j] == in3[0].x[j] + (int64_t)B * hw3[0] * C3;
+      for (int p = 0; p < (one ? 1 : 2); ++p) {
+        const int nimg = one ? 2 * B : B;
+        GCV_TRY(run("explain2.dwconv7_ln", 2.0 * 49 * nimg * hw3[p] * C3, 2.0 * sizeof(T) * (double)nimg * hw3[p] * C3, [&] {
+          return launch_dwconv7_ln<T>(in3[p].x[j], k.dw_w, k.dw_b, k.ln_w, k.ln_b, Yb + (int64_t)tok0[p] * C3, nimg, side3[p],
+                                      side3[p], C3, 1e-6f, cur);
+        }));
+      }
+      {
+        GemmArgs g{};
+        g.A = Yb; g.lda = C3; g.Wt = k.mlp.w1; g.C = Pre; g.ldc = 4 * C3; g.bias = k.mlp.b1;
+        g.M = (int)M; g.N = 4 * C3; g.K = C3; g.act = ACT_NONE; g.splitk = 1;
+        GCV_TRY(gemm("explain2.pw1_pre", g, A_PLAIN, EPI_BIAS_ACT));
+      }
+      GCV_TRY(run("explain2.gelu_bwd", 12.0 * M * 4 * C3, (2.0 * sizeof(T) + 4.0) * (double)M * 4 * C3,
+                  [&] { return launch_gelu_bwd<T>(Dh, invA, Pre, invB, (int)M, 4 * C3, cur); }));
+      GCV_TRY(dgemm("explain2.dpre_w1", Pre, bw.bwd_w1t[j], Dl, C3, 4 * C3));
+      for (int p = 0; p < 2; ++p) {
+        DwLnBwdArgs da{in3[p].x[j], k.dw_w, k.dw_b, k.ln_w, Dl + (int64_t)tok0[p] * C3, invB + tok0[p],
+                       Dw + (int64_t)tok0[p] * C3, B, side3[p], 1e-6f};
+        GCV_TRY(run("explain2.dw_ln_bwd", 2.0 * 49 * B * hw3[p] * C3, (sizeof(T) + 8.0) * (double)B * hw3[p] * C3,
+                    [&] { return launch_dw_ln_bwd<T>(da, C3, cur); }));
+        GCV_TRY(run("explain2.dw_dgrad_res", 2.0 * 49 * B * hw3[p] * C3, 12.0 * (double)B * hw3[p] * C3, [&] {
+          return launch_dw_dgrad_res(Dw + (int64_t)tok0[p] * C3, k.dw_w, G + (int64_t)tok0[p] * C3, B, side3[p], C3, cur);
+        }));
+      }
+    }
+    GCV_TRY(run("explain2.scale_rows", 2.0 * M * C3, (sizeof(T) + 4.0) * (double)M * C3,
+                [&] { return launch_scale_rows<T>(G, nullptr, Gt, invA, (int)M, C3, cur); }));
+    GCV_TRY(dgemm("explain2.dx_wdown", Gt, bw.bwd_downt, Dh, 4 * C2, C3));
+    Cam2Args ca{};
+    for (int p = 0; p < 2; ++p) {
+      DownLnBwdArgs da{in3[p].s2, bw.down[2].ln_w, Dh + (int64_t)tok0[p] * 4 * C2, invA + tok0[p], dA2 + tok2[p] * C2, B,
+                       side2[p], 1e-6f};
+      GCV_TRY(run("explain2.down_ln_bwd", 10.0 * B * side2[p] * side2[p] * C2, (sizeof(T) + 8.0) * (double)B * side2[p] * side2[p] * C2,
+                  [&] { return launch_down_ln_bwd<T>(da, C2, cur); }));
+      ca.A[p] = in3[p].s2; ca.dA2[p] = dA2 + tok2[p] * C2; ca.side[p] = side2[p];
+      ca.cam_off[p] = p ? side2[0] * side2[0] : 0;
+    }
+    ca.npass = 2; ca.cam_ld = ex.cam_ld; ca.up_pass = up_pass; ca.B = B; ca.cam = ex.cam; ca.cam224 = ex.cam224; ca.alpha = alpha;
+    GCV_TRY(run("explain2.cam", 4.0 * M2 * C2, (sizeof(T) + 4.0) * (double)M2 * C2 + (ex.cam224 ? 4.0 * B * 224 * 224 : 0.0),
+                [&] { return launch_cam2<T>(ca, C2, cur); }));
+    if (!taps.empty()) GCV_TRY(tap_net((std::string(net) + ".explain.alpha2").c_str(), alpha, (size_t)2 * B * C2 * sizeof(float)));
     return 0;
   }
 
@@ -813,6 +968,7 @@ template <typename T> struct NetImpl : NetBase {
       GCV_REQUIRE(xv && logits, "null input/output");
       GCV_REQUIRE(!ex || ex->cam, "null map output");
     }
+    GCV_REQUIRE(!ex || ex->layer == 2 || ex->layer == 3, "explain layer must be 2 or 3");
     cur = s;
     const T* x = (const T*)xv;
     if (!taps.empty()) tap_reset("ed");
@@ -872,16 +1028,21 @@ template <typename T> struct NetImpl : NetBase {
     segs[0] = Seg<T>{rec, (int64_t)224 * 224 * 3, 1, 224 * 3, 3, B, 224, 224, feat, 2000, ACT_GELU};
     segs[1] = Seg<T>{x, (int64_t)3 * 224 * 224, 224 * 224, 224, 1, B, 224, 224, feat + 1000, 2000, ACT_GELU};
     const T* s3[2] = {nullptr, nullptr};
+    Stage3In<T> in3[2];
     const float* head_part = nullptr;
     if (ex)
-      for (int q = 0; q < 2; ++q) { segs[q].pre = bbpre + 1000 * q; segs[q].s3 = &s3[q]; }
+      for (int q = 0; q < 2; ++q) {
+        segs[q].pre = bbpre + 1000 * q; segs[q].s3 = &s3[q];
+        if (ex->layer == 2) segs[q].in3 = &in3[q];
+      }
     const TapPass tp{"ed", 2, 0, {B, B}, {224, 224}, {224, 224}};
     GCV_TRY(run_convnext(bb_ed, segs, 2, false, taps.empty() ? nullptr : &tp));
     GCV_TRY(run_head(ed.head, feat, B, ACT_GELU, logits, ex ? &head_part : nullptr));
     if (ex) {
       // maps [b][pass][7][7], passes in cat order (reconstruction, original); the original frame's map is upsampled
-      const int hwp[2] = {49, 49}, side[2] = {7, 7}, off[2] = {0, 49};
-      GCV_TRY(explain_tail(bb_ed, ed.head, ACT_GELU, B, head_part, bbpre, logits, s3, hwp, side, off, 1, *ex));
+      // (at stage 2: [b][pass][14][14])
+      const int hwp[2] = {49, 49}, side[2] = {7, 7}, off[2] = {0, 49}, side2[2] = {14, 14};
+      GCV_TRY(explain_tail(bb_ed, ed.head, ACT_GELU, B, head_part, bbpre, logits, s3, hwp, side, off, 1, *ex, in3, side2, "ed"));
     }
     if (!taps.empty()) {
       const T* et[5] = {e1, e2, e3, e4, e5};
@@ -913,6 +1074,7 @@ template <typename T> struct NetImpl : NetBase {
       GCV_REQUIRE(!kl || vae.var_w, "KL requested but encoder.var weights were not loaded");
       GCV_REQUIRE(!ex || ex->cam, "null map output");
     }
+    GCV_REQUIRE(!ex || ex->layer == 2 || ex->layer == 3, "explain layer must be 2 or 3");
     cur = s;
     const T* x = (const T*)xv;
     if (!taps.empty()) tap_reset("vae");
@@ -943,9 +1105,13 @@ template <typename T> struct NetImpl : NetBase {
     segs[0] = Seg<T>{x, (int64_t)3 * 224 * 224, 224 * 224, 224, 1, B, 224, 224, feat, 2000, ACT_RELU};
     segs[1] = Seg<T>{xhat, (int64_t)112 * 112 * 3, 1, 112 * 3, 3, B, 112, 112, feat + 1000, 2000, ACT_RELU};
     const T* s3[2] = {nullptr, nullptr};
+    Stage3In<T> in3[2];
     const float* head_part = nullptr;
     if (ex)
-      for (int q = 0; q < 2; ++q) { segs[q].pre = bbpre + 1000 * q; segs[q].s3 = &s3[q]; }
+      for (int q = 0; q < 2; ++q) {
+        segs[q].pre = bbpre + 1000 * q; segs[q].s3 = &s3[q];
+        if (ex->layer == 2) segs[q].in3 = &in3[q];
+      }
     const bool split = (vae_split_env >= 0 ? vae_split_env != 0 : !in_ensemble) && !prof.enabled;   // (profiled steps stay on one stream: serial per-kernel times)
     const TapPass tp0{"vae", 2, 0, {B, B}, {224, 112}, {224, 112}}, tp1{"vae", 2, 1, {B, B}, {224, 112}, {224, 112}};
     const bool tapping = !taps.empty();
@@ -1021,8 +1187,9 @@ template <typename T> struct NetImpl : NetBase {
     GCV_TRY(run_head(vae.head, feat, B, ACT_RELU, logits, ex ? &head_part : nullptr));
     if (ex) {
       // maps [b][7 x 7 of the original frame, 3 x 3 of x_hat at 112]; the original frame's map is upsampled
-      const int hwp[2] = {49, 9}, side[2] = {7, 3}, off[2] = {0, 49};
-      GCV_TRY(explain_tail(bb_vae, vae.head, ACT_RELU, B, head_part, bbpre, logits, s3, hwp, side, off, 0, *ex));
+      // (at stage 2: [b][14 x 14, 7 x 7])
+      const int hwp[2] = {49, 9}, side[2] = {7, 3}, off[2] = {0, 49}, side2[2] = {14, 7};
+      GCV_TRY(explain_tail(bb_vae, vae.head, ACT_RELU, B, head_part, bbpre, logits, s3, hwp, side, off, 0, *ex, in3, side2, "vae"));
     }
     if (recon224 || mse) {
       GCV_TRY(run("vae.resize_mse", 30.0 * B * 224 * 224, sizeof(T) * (double)B * (3 * 112 * 112 + 6 * 224 * 224), [&] {
@@ -1057,12 +1224,17 @@ template <typename T> struct NetImpl : NetBase {
     arena.dry = true;
     arena.off = arena.peak = 0;
     // the explain variants keep the head's inputs alive on top of the forward's buffers: the arena holds them too
-    const Explain ex;
-    int rc = ed_run(nullptr, max_batch, nullptr, nullptr, &ex);
-    if (!rc) rc = vae_run(nullptr, nullptr, max_batch, nullptr, nullptr, nullptr, nullptr, nullptr, &ex);
-    in_ensemble = true;                    // both VAE schedules (see vae_split_env): the arena holds the larger footprint
-    if (!rc) rc = vae_run(nullptr, nullptr, max_batch, nullptr, nullptr, nullptr, nullptr, nullptr, &ex);
-    in_ensemble = false;
+    // (at either layer: stage 2's keeps stage 3's inputs and the backward's gradient buffers as well)
+    int rc = 0;
+    for (int layer = 3; layer >= 2 && !rc; --layer) {
+      Explain ex;
+      ex.layer = layer;
+      rc = ed_run(nullptr, max_batch, nullptr, nullptr, &ex);
+      if (!rc) rc = vae_run(nullptr, nullptr, max_batch, nullptr, nullptr, nullptr, nullptr, nullptr, &ex);
+      in_ensemble = true;                  // both VAE schedules (see vae_split_env): the arena holds the larger footprint
+      if (!rc) rc = vae_run(nullptr, nullptr, max_batch, nullptr, nullptr, nullptr, nullptr, nullptr, &ex);
+      in_ensemble = false;
+    }
     if (!rc) rc = swin_forward(nullptr, max_batch, nullptr, nullptr);
     arena.dry = false;
     if (rc) return rc;

@@ -89,7 +89,7 @@ class GenConViT(nn.Module):
         return out
 
     @torch.no_grad()
-    def explain(self, x, eps=None, target=None, upsample=True):
+    def explain(self, x, eps=None, target=None, upsample=True, layer="s3"):
         """``forward`` plus Grad-CAM evidence maps of every frame's real / fake decision at the last ConvNeXt stage of each
         network (include/genconvit_hip.h, gcv_*_explain).  ``target``: None (each frame's argmax, per network), a class
         (0 / 1) or one class per frame.  Returns ``(logits, cams)``; the logits are ``forward``'s (fp32, same rows), and
@@ -98,21 +98,25 @@ class GenConViT(nn.Module):
           'vae'       (B,7,7)    VAE backbone(x)                                (net 'vae' and 'genconvit')
           'vae_xhat'  (B,3,3)    VAE backbone(x_hat) at 112 px
           'upsampled' (rows of the logits, 224, 224): each row's original-frame map resized like
-                      F.interpolate(mode='bilinear', align_corners=False), or None when ``upsample`` is False"""
+                      F.interpolate(mode='bilinear', align_corners=False), or None when ``upsample`` is False
+        ``layer``: "s3" (the default, above) or "s2": the maps at the output of ConvNeXt stage 2 (gcv_*_explain_at), 16-pixel
+        cells — 'ed' (B,2,14,14), 'vae' (B,14,14), 'vae_xhat' (B,7,7), 'upsampled' as above.  Any other value raises
+        ValueError."""
+        sa, sb = (7, 3) if _lib.explain_layer(layer)[0] == 3 else (14, 7)
         if self.net == "ed":
-            return self.model_ed.explain(x, target=target, upsample=upsample)
+            return self.model_ed.explain(x, target=target, upsample=upsample, layer=layer)
         if self.net == "vae":
-            return self.model_vae.explain(x, eps=eps, target=target, upsample=upsample)
+            return self.model_vae.explain(x, eps=eps, target=target, upsample=upsample, layer=layer)
         if not (self.concurrent and next(self.model_ed.parameters()).is_cuda):
-            le, ce = self.model_ed.explain(x, target=target, upsample=upsample)
-            lv, cv = self.model_vae.explain(x, eps=eps, target=target, upsample=upsample)
+            le, ce = self.model_ed.explain(x, target=target, upsample=upsample, layer=layer)
+            lv, cv = self.model_vae.explain(x, eps=eps, target=target, upsample=upsample, layer=layer)
             up = torch.cat((ce["upsampled"], cv["upsampled"])) if upsample else None
             return torch.cat((le, lv)), {"ed": ce["ed"], "vae": cv["vae"], "vae_xhat": cv["vae_xhat"], "upsampled": up}
         x = self.model_ed._prep_input(x)
         B = x.shape[0]
         if B == 0:
             z = lambda *s: torch.empty(s, dtype=torch.float32, device=x.device)
-            return z(0, 2), {"ed": z(0, 2, 7, 7), "vae": z(0, 7, 7), "vae_xhat": z(0, 3, 3),
+            return z(0, 2), {"ed": z(0, 2, sa, sa), "vae": z(0, sa, sa), "vae_xhat": z(0, sb, sb),
                              "upsampled": z(0, 224, 224) if upsample else None}
         if eps is None:
             eps = torch.randn((B, self.model_vae.latent_dims), dtype=torch.float32, device=x.device,
@@ -120,14 +124,14 @@ class GenConViT(nn.Module):
         else:
             eps = eps.to(device=x.device, dtype=torch.float32)
         parts = [_lib.genconvit_explain(self.model_ed._get_handle(hi - lo), self.model_vae._get_handle(hi - lo), x[lo:hi],
-                                        eps[lo:hi], self.model_ed._target_chunk(target, lo, hi), upsample)
+                                        eps[lo:hi], self.model_ed._target_chunk(target, lo, hi), upsample, layer)
                  for lo, hi in self.model_ed._chunks(B)]
         half = lambda t: (t[:t.shape[0] // 2], t[t.shape[0] // 2:])
         logits = torch.cat([half(p[0])[0] for p in parts] + [half(p[0])[1] for p in parts])
         vae = torch.cat([p[2] for p in parts])
         up = torch.cat([half(p[3])[0] for p in parts] + [half(p[3])[1] for p in parts]) if upsample else None
-        return logits, {"ed": torch.cat([p[1] for p in parts]), "vae": vae[:, :49].reshape(B, 7, 7),
-                        "vae_xhat": vae[:, 49:].reshape(B, 3, 3), "upsampled": up}
+        return logits, {"ed": torch.cat([p[1] for p in parts]), "vae": vae[:, :sa * sa].reshape(B, sa, sa),
+                        "vae_xhat": vae[:, sa * sa:].reshape(B, sb, sb), "upsampled": up}
 
     def _forward_fp32(self, x, eps=None):
         if self.net == "ed":

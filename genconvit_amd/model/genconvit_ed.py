@@ -40,22 +40,24 @@ class GenConViTED(HipModule):
         return self._get_handle(images.shape[0]).ed_forward(images)
 
     @torch.no_grad()
-    def explain(self, images, eps=None, target=None, upsample=True):
-        """Forward + Grad-CAM of the real / fake decision at the last ConvNeXt stage (``gcv_ed_explain``).  ``target``:
+    def explain(self, images, eps=None, target=None, upsample=True, layer="s3"):
+        """Forward + Grad-CAM of the real / fake decision at the last ConvNeXt stage (``gcv_ed_explain``), or with
+        ``layer="s2"`` at the output of stage 2 (``gcv_ed_explain_at``: ``cams['ed']`` is then (B,2,14,14)).  ``target``:
         None (each frame's argmax), a class (0 / 1) or one class per frame.  Returns ``(logits, cams)``: the logits equal
         ``forward``'s; ``cams['ed']`` (B,2,7,7) fp32 maps of the [reconstruction, original] passes (not normalised) and
         ``cams['upsampled']`` (B,224,224) the original pass's map resized like ``F.interpolate(mode='bilinear')``, or None.
         ``eps`` is accepted for a signature shared with the VAE and ignored."""
+        side = 7 if _lib.explain_layer(layer)[0] == 3 else 14
         images = self._prep_input(images)
         B = images.shape[0]
         if B > self._cap:
-            parts = [self._get_handle(hi - lo).ed_explain(images[lo:hi], self._target_chunk(target, lo, hi), upsample)
+            parts = [self._get_handle(hi - lo).ed_explain(images[lo:hi], self._target_chunk(target, lo, hi), upsample, layer)
                      for lo, hi in self._chunks(B)]
         else:
-            parts = [self._get_handle(B).ed_explain(images, target, upsample)] if B else []
+            parts = [self._get_handle(B).ed_explain(images, target, upsample, layer)] if B else []
         if not parts:
             z = lambda *s: torch.empty(s, dtype=torch.float32, device=images.device)
-            return z(0, 2), {"ed": z(0, 2, 7, 7), "upsampled": z(0, 224, 224) if upsample else None}
+            return z(0, 2), {"ed": z(0, 2, side, side), "upsampled": z(0, 224, 224) if upsample else None}
         cat = lambda i: torch.cat([p[i] for p in parts]) if parts[0][i] is not None else None
         return cat(0), {"ed": cat(1), "upsampled": cat(2)}
 

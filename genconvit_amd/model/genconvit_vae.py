@@ -65,25 +65,29 @@ class GenConViTVAE(HipModule):
         return logits, recon
 
     @torch.no_grad()
-    def explain(self, x, eps=None, target=None, upsample=True):
+    def explain(self, x, eps=None, target=None, upsample=True, layer="s3"):
         """Forward + Grad-CAM of the real / fake decision at the last ConvNeXt stage (``gcv_vae_explain``); ``eps`` and
         ``target`` as in ``forward`` / ``GenConViTED.explain``.  Returns ``(logits, cams)``: ``cams['vae']`` (B,7,7) the map
         of backbone(x), ``cams['vae_xhat']`` (B,3,3) that of backbone(x_hat) at 112 px, ``cams['upsampled']`` (B,224,224)
-        the first one resized, or None."""
+        the first one resized, or None.  ``layer="s2"``: at the output of stage 2 (``gcv_vae_explain_at``), (B,14,14) and
+        (B,7,7)."""
+        sa, sb = (7, 3) if _lib.explain_layer(layer)[0] == 3 else (14, 7)
         x = self._prep_input(x)
         B = x.shape[0]
         z = lambda *s: torch.empty(s, dtype=torch.float32, device=x.device)
         if B == 0:
-            return z(0, 2), {"vae": z(0, 7, 7), "vae_xhat": z(0, 3, 3), "upsampled": z(0, 224, 224) if upsample else None}
+            return z(0, 2), {"vae": z(0, sa, sa), "vae_xhat": z(0, sb, sb), "upsampled": z(0, 224, 224) if upsample else None}
         if eps is None:
             eps = torch.randn((B, self.latent_dims), dtype=torch.float32, device=x.device, generator=self._generator)
         else:
             eps = eps.to(device=x.device, dtype=torch.float32)
-        parts = [self._get_handle(hi - lo).vae_explain(x[lo:hi], eps[lo:hi], self._target_chunk(target, lo, hi), upsample)
+        parts = [self._get_handle(hi - lo).vae_explain(x[lo:hi], eps[lo:hi], self._target_chunk(target, lo, hi), upsample,
+                                                       layer)
                  for lo, hi in self._chunks(B)]
         cat = lambda i: torch.cat([p[i] for p in parts]) if parts[0][i] is not None else None
         cam = cat(1)
-        return cat(0), {"vae": cam[:, :49].reshape(B, 7, 7), "vae_xhat": cam[:, 49:].reshape(B, 3, 3), "upsampled": cat(2)}
+        return cat(0), {"vae": cam[:, :sa * sa].reshape(B, sa, sa), "vae_xhat": cam[:, sa * sa:].reshape(B, sb, sb),
+                        "upsampled": cat(2)}
 
     def backbone_forward(self, images):
         images = self._prep_input(images)

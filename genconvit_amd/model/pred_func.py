@@ -60,15 +60,16 @@ def pred_vid(df, model):
         return max_prediction_value(torch.sigmoid(model(df).squeeze()))
 
 
-def pred_vid_explain(df, model, target=None):
+def pred_vid_explain(df, model, target=None, layer="s3"):
     """``pred_vid`` with evidence maps: returns ``((y, y_val), maps)`` where ``(y, y_val)`` is what ``pred_vid(df, model)``
     returns for the same logits and ``maps`` is the model's per-frame Grad-CAM maps upsampled to 224 x 224 and scaled to
     [0, 1] per map, in the logits' row order ((2n, 224, 224) for the ensemble: ED rows, then VAE rows).  ``target``: as in
-    ``GenConViT.explain`` (default: each frame's own decision)."""
+    ``GenConViT.explain`` (default: each frame's own decision); ``layer``: "s3" (7 x 7 maps of the last ConvNeXt stage) or
+    "s2" (14 x 14 maps of the stage before it), as in ``GenConViT.explain``."""
     p = next(model.parameters())
     if df.device != p.device:
         df = df.to(p.device)
-    logits, cams = model.explain(df, target=target, upsample=True)
+    logits, cams = model.explain(df, target=target, upsample=True, layer=layer)
     out = logits.to(p.dtype) if getattr(model, "reference_logits_dtype", False) else logits
     return max_prediction_value(torch.sigmoid(out.squeeze())), normalize_cams(cams["upsampled"])
 

@@ -134,6 +134,34 @@ int gcv_vae_explain(gcv_handle* h, const void* x_nchw, const float* eps, int bat
 int gcv_genconvit_explain(gcv_handle* h_ed, gcv_handle* h_vae, const void* x_nchw, const float* eps, int batch,
                           const int* target, float* logits_2Bx2, float* cam_raw, float* cam224, gcv_stream stream);
 
+/* ---- explain at a chosen ConvNeXt stage ----
+ * The entries above with one more argument, `layer`: the stage whose output the maps are taken at.
+ *   layer = 3  exactly gcv_*_explain: the same launches, outputs and layouts.
+ *   layer = 2  Grad-CAM at the output of stage 2, the residual stream after the stage's last block (tap <net>.bb.s2.b8 on
+ *              ConvNeXt-T, <net>.bb.s2.b26 on -L): 14 x 14 cells of 16 pixels over a 224-pixel crop (7 x 7 for the VAE's
+ *              112-pixel pass).  The gradient is no longer constant over the map, so the call continues the backward above
+ *              through the pooled LayerNorm2d and the average pool, stage 3's three blocks (layer scale, fc2^T, exact-erf
+ *              GELU' at the recomputed hidden pre-activation, fc1^T, LayerNorm backward at the recomputed depthwise output,
+ *              the depthwise 7 x 7 data gradient, the residual) and the stage 2 -> 3 down-sampling (conv^T as a GEMM,
+ *              depth-to-space, LayerNorm2d backward), all gradient math in fp32, and then
+ *                alpha_c   = mean over (h, w) of d logit_target / d A2_c(h, w)
+ *                CAM(h, w) = ReLU(sum_c alpha_c A2_c(h, w))        (fp32, not normalised)
+ *              cam_raw  ED : [B][2][14][14] (pass order as above)       VAE: [B][14*14 + 7*7]
+ *                       ensemble: the ED block (B x 392 floats) followed by the VAE block (B x 245 floats)
+ *              cam224   as above, from the 14 x 14 map of backbone(x)
+ *              An odd last row / column of a stage-2 map (the 7 x 7 one) takes no part in the down-sampling and has zero
+ *              gradient.  In this mode the forward keeps the stage-2 output and the inputs of stage 3's blocks instead of
+ *              overwriting them (same kernels, same operands: the logits stay bit-identical to the plain forward's).
+ * Any other `layer` is an error (gcv_last_error()).  target, eps, streams, chunking rules and "no allocation, copy or
+ * synchronisation inside a call" are those of gcv_*_explain; the handle's arena is sized for either layer at max_batch. */
+int gcv_ed_explain_at(gcv_handle* h, const void* x_nchw, int batch, const int* target, int layer, float* logits,
+                      float* cam_raw, float* cam224, gcv_stream stream);
+int gcv_vae_explain_at(gcv_handle* h, const void* x_nchw, const float* eps, int batch, const int* target, int layer,
+                       float* logits, float* cam_raw, float* cam224, gcv_stream stream);
+int gcv_genconvit_explain_at(gcv_handle* h_ed, gcv_handle* h_vae, const void* x_nchw, const float* eps, int batch,
+                             const int* target, int layer, float* logits_2Bx2, float* cam_raw, float* cam224,
+                             gcv_stream stream);
+
 /* timm convnext_tiny forward alone (call sites model/genconvit_ed.py:82-83,
  * model/genconvit_vae.py:111-112): which = 0 the ED backbone, 1 the VAE backbone;
  * x (B,3,res,res) -> logits1000 (B,1000) in the handle dtype. */
