@@ -647,6 +647,8 @@ int gcv_dw_plan(int dtype, int nimg, int H, int W, int C, int aligned, int* out5
   DISPATCH_DT(dtype, put(dw_plan<T>(p, nimg, H, W, C, aligned != 0)));
 }
 
+int gcv_convnext_res_ok(int arch, int res) { return cnx_res_ok(arch, res) ? 1 : 0; }
+
 int gcv_k_ln_patchify(int dtype, const void* x, const float* w, const float* b, void* out, int nimg, int H, int W,
                       int C, float eps, gcv_stream s) {
   DISPATCH_DT(dtype, launch_ln_patchify<T>((const T*)x, w, b, (T*)out, nimg, H, W, C, eps, (hipStream_t)s));

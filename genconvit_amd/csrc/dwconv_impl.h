@@ -36,7 +36,10 @@ template <DwKind K, int C_ = 0, int N_ = 0> struct DwShape {
 //   3. Tile, the generic tile kernel, at C <= 768.
 // Every kernel is reachable: gcv_convnext_forward takes res = 32 ... 224 in steps of 4, so the stage-3 map can be 1 x 1 to
 // 4 x 4 (all four S of Tiny and TinyPair), and maps whose width is not a multiple of 7 (res 160: 5 x 5 at stage 3) or
-// unaligned operands reach Tile.  Calls f(plan, DwShape) and returns its value, or sets the launcher's error.
+// unaligned operands reach Tile.  There is no Tile kernel at C = 1536: a 5- or 6-pixel map there (ConvNeXt-L at res
+// 160 ... 220) is this function's error, which is why cnx_res_ok (net.h) refuses those resolutions before the pass starts.
+// Every (kind, C, NS or S) returned here has a GPU parity case (tests/dwcases.py; tests/test_host_cpu.py checks the set).
+// Calls f(plan, DwShape) and returns its value, or sets the launcher's error.
 template <typename T, class F> int dw_select(int nimg, int H, int W, int C, bool aligned, F&& f) {
   GCV_REQUIRE(nimg > 0 && H > 0 && W > 0, "dwconv: empty");
   const int ns = W % 7 == 0 ? W / 7 : 0;

@@ -78,6 +78,21 @@ inline const CnxArch& cnx_arch(int arch) {       // arch: GCV_CONVNEXT_TINY (0) 
   static const CnxArch tiny{{96, 192, 384, 768}, {3, 3, 9, 3}}, large{{192, 384, 768, 1536}, {3, 3, 27, 3}};
   return arch == 1 ? large : tiny;
 }
+// The resolutions gcv_convnext_forward runs (gcv_convnext_res_ok): multiples of 4 in [32, 224] whose four maps all have a
+// depthwise kernel (dw_select, dwconv_impl.h).  The maps are res / 4 pixels wide, halved with floor at each stage boundary:
+// the stage-3 map is res / 32.  ConvNeXt-T has the generic tile kernel at every width; at ConvNeXt-L's C = 1536 there are
+// kernels for maps up to 4 x 4 and for 7 x 7 only, so a 5- or 6-pixel stage-3 map (res 160 ... 220) is refused before
+// anything is launched.
+inline bool cnx_res_ok(int arch, int res) {
+  if (res % 4 != 0 || res < 32 || res > 224) return false;
+  const int s3 = res / 32;
+  return arch != 1 || s3 <= 4 || s3 == 7;
+}
+inline const char* cnx_res_rule(int arch) {
+  return arch == 1 ? "resolution must be a multiple of 4 in [32,156], or 224, on a ConvNeXt-L handle (no C = 1536 depthwise "
+                     "kernel for the 5- and 6-pixel stage-3 maps of 160 ... 220)"
+                   : "resolution must be a multiple of 4 in [32,224]";
+}
 
 // ---- abstract network (dtype erased) ----------------------------------------
 struct NetBase {

@@ -78,12 +78,17 @@ struct Arena {
   }
   template <typename U> U* get(int64_t n) { return (U*)alloc((size_t)n * sizeof(U)); }
 };
-// releases an arena mark on every exit path of a forward (an error return included)
+// releases an arena mark on every exit path of a forward (an error return included); `overflow` says that a live
+// allocation reaches past the arena, so it ends with the scope that gives the arena back: a forward that was refused for
+// its size leaves the handle as it found it
 struct ArenaScope {
   Arena& a;
   const size_t m;
   explicit ArenaScope(Arena& a_) : a(a_), m(a_.mark()) {}
-  ~ArenaScope() { a.release(m); }
+  ~ArenaScope() {
+    a.release(m);
+    if (a.off <= a.cap) a.overflow = false;
+  }
 };
 
 // device-side permute+cast for the 25088x12544 mu/var matrices: columns c*196+hw -> hw*128+c so the
@@ -1203,8 +1208,9 @@ template <typename T> struct NetImpl : NetBase {
   int convnext_forward(int which, const void* xv, int B, int res, void* logits1000, hipStream_t s) override {
     GCV_REQUIRE(which == 0 ? has_ed : has_vae, "backbone weights not loaded");
     GCV_TRY(check_batch(B));
-    GCV_REQUIRE(res % 4 == 0 && res >= 32 && res <= 224, "resolution must be a multiple of 4 in [32,224]");
+    GCV_REQUIRE(cnx_res_ok(arch, res), cnx_res_rule(arch));
     cur = s;
+    const ArenaScope scope(arena);
     Seg<T> seg{(const T*)xv, (int64_t)3 * res * res, (int64_t)res * res, res, 1, B, res, res, (T*)logits1000, 1000, ACT_NONE};
     return run_convnext(which == 0 ? bb_ed : bb_vae, &seg, 1);
   }
@@ -1216,6 +1222,7 @@ template <typename T> struct NetImpl : NetBase {
     }
     cur = s;
     if (!arena.dry) GCV_REQUIRE(xv && logits1000, "null input/output");
+    const ArenaScope scope(arena);
     return run_swin<T>(*this, swin, (const T*)xv, B, (T*)logits1000);
   }
 

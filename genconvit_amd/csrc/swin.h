@@ -83,8 +83,7 @@ template <typename T, typename Net> int run_swin(Net& net, const SwinW<T>& w, co
   hipStream_t cur = net.cur;
   int H = 56;
   int64_t M = (int64_t)B * H * H;
-  const size_t mk = ar.mark();
-  T* X = ar.template get<T>(M * 96);
+  T* X = ar.template get<T>(M * 96);                  // released by the caller's ArenaScope (swin_forward), on every path
   T* Y = ar.template get<T>(M * 96);
   T* QKV = ar.template get<T>(M * 288);
   T* ATT = ar.template get<T>(M * 96);
@@ -146,7 +145,6 @@ template <typename T, typename Net> int run_swin(Net& net, const SwinW<T>& w, co
   hd.A = Pool; hd.lda = 768; hd.Wt = w.head_w; hd.C = logits1000; hd.ldc = 1000; hd.bias = w.head_b;
   hd.M = B; hd.N = 1000; hd.K = 768; hd.act = ACT_NONE; hd.splitk = 1;
   GCV_TRY(net.gemm("swin.head_gemm", hd, A_PLAIN, EPI_BIAS_ACT));
-  ar.release(mk);
   return 0;
 }
 

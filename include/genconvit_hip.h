@@ -164,7 +164,11 @@ int gcv_genconvit_explain_at(gcv_handle* h_ed, gcv_handle* h_vae, const void* x_
 
 /* timm convnext_tiny forward alone (call sites model/genconvit_ed.py:82-83,
  * model/genconvit_vae.py:111-112): which = 0 the ED backbone, 1 the VAE backbone;
- * x (B,3,res,res) -> logits1000 (B,1000) in the handle dtype. */
+ * x (B,3,res,res) -> logits1000 (B,1000) in the handle dtype.
+ * res: a multiple of 4 in [32, 224].  A ConvNeXt-L handle (GCV_CONVNEXT_LARGE) takes [32, 156] and 224 only: at 160 ... 220
+ * the last stage's map is 5 or 6 pixels wide, for which there is no C = 1536 depthwise kernel.  Any other res is refused
+ * (gcv_last_error() names the range) before anything is launched; a refused or failed call leaves the handle's workspace
+ * as it found it. */
 int gcv_convnext_forward(gcv_handle* h, int which, const void* x_nchw, int batch, int res,
                          void* logits1000, gcv_stream stream);
 
@@ -279,6 +283,9 @@ int gcv_k_dwconv7_ln(int dtype, const void* x, const float* wdw, const float* bd
  * out5 = {kind (0 tile, 1 tiny, 2 tiny-pair, 3 roll, 4 mfma, 5 pair), workgroups, threads per workgroup, dynamic LDS bytes,
  * rows per band (roll, mfma, pair; else 0)}; or the launcher's error.  No HIP call: works without a GPU. */
 int gcv_dw_plan(int dtype, int nimg, int H, int W, int C, int aligned, int* out5);
+/* Test query: 1 if gcv_convnext_forward on a handle of backbone `arch` (GCV_CONVNEXT_TINY / _LARGE) runs resolution `res`,
+ * 0 if it refuses it (the rule it applies itself).  No HIP call: works without a GPU. */
+int gcv_convnext_res_ok(int arch, int res);
 int gcv_k_ln_patchify(int dtype, const void* x, const float* w, const float* b, void* out, int nimg, int H, int W,
                       int C, float eps, gcv_stream s);
 int gcv_k_layernorm_rows(int dtype, const void* x, const float* w, const float* b, void* out, int64_t rows, int C,

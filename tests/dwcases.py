@@ -1,0 +1,58 @@
+"""The (C, H, W, n) shapes of the GPU parity tests of the depthwise 7x7 + LayerNorm (gcv_k_dwconv7_ln), in one place: the
+GPU tests parametrise over these lists, and tests/test_host_cpu.py asks gcv_dw_plan, without a GPU, which kernel each of
+them runs — every kernel dw_select (csrc/dwconv_impl.h) can return must be the plan of at least one shape here."""
+
+# tests/test_kernels_gpu.py: test_dwconv7x7_layernorm (square maps, (C, H, n))
+SQUARE = [(96, 56, 2), (96, 28, 3), (192, 28, 2), (192, 14, 1), (384, 14, 2), (384, 7, 3),
+          (768, 7, 2), (768, 3, 3),
+          (768, 1, 5), (768, 2, 3), (768, 4, 2),      # whole-map kernel of the tiny stage-3 maps (with (768, 3, 3))
+          # launches of more than 128 seven-row bands keep seven-row bands (the large-batch rule);
+          # the few-image cases above run the two- to four-row bands of small launches
+          (96, 56, 17), (384, 14, 70),
+          # 16-bit storage, 56-pixel C = 96 maps in bands of 14 rows and more: the matrix-pipe kernel
+          # (dwconv_mfma.h; fp32 storage stays on the VALU kernel): four 14-row bands, ragged 19/19/18
+          (96, 56, 64), (96, 56, 100)]
+
+# tests/test_large_gpu.py: test_dwconv7x7_layernorm_large_shapes ((C, H, n); (1536, 2, n): TinyPair S = 2, ConvNeXt-L at
+# res 64 ... 92)
+LARGE = [(192, 56, 3), (384, 28, 3), (768, 14, 5), (1536, 7, 3), (1536, 7, 600),
+         (1536, 3, 3), (1536, 1, 2), (1536, 4, 2), (1536, 2, 3)]
+
+# The generic tile kernel (DwKind::Tile, dwconv7_ln_kernel<T, C>): maps whose width is not 7 NS of a band kernel.
+# (C, H, W, n): 5, 6, 10, 20, 40 are the maps of a res-160 pass; 9 and 25 are odd with ragged right / bottom 7x7 tiles (2 x 2
+# and 4 x 4 tiles); one non-square map and one single-row map.
+TILE = [(C, H, W, n) for C in (96, 192, 384, 768)
+        for H, W, n in [(5, 5, 3), (6, 6, 2), (10, 10, 2), (20, 20, 2), (40, 40, 2), (9, 9, 2), (25, 25, 1), (10, 25, 2),
+                        (1, 13, 3)]]
+TILE += [(96, 14, 14, 2),      # res 56 at C = 96: 14 = 7 * 2 but there is no two-strip kernel at 96 channels
+         (96, 9, 9, 1),        # C = 96 packs two tiles per workgroup: 4 tiles, both slots busy in both workgroups
+         (96, 25, 25, 3)]      # 48 tiles
+# at C = 96 an odd tile count leaves the second tile slot of the last workgroup idle (tile_ok == false): (96, 5, 5, 3) above
+# is 3 tiles; these are 1, 3 (non-square) and 9
+TILE_ODD = [(96, 5, 5, 1), (96, 5, 15, 1), (96, 20, 20, 1)]
+
+# Band kernels (Roll / Mfma / Pair) away from squares: H != W, H < 7, H not a multiple of the band.  (C, H, W, n)
+BANDS = [(96, 1, 56, 3), (96, 5, 56, 2), (96, 57, 56, 2),      # Roll<96, 8>
+         (96, 57, 56, 63),      # 3 591 image rows: Mfma<96, 8> in 16-bit storage (8-row bands, the last band one row)
+         (96, 5, 56, 717),      # 3 585 image rows of 5-row images: Mfma with a band shorter than the 7 tap rows
+         (96, 9, 28, 3), (192, 3, 28, 2), (192, 30, 14, 2), (384, 15, 14, 3), (384, 2, 7, 4), (768, 10, 7, 3),   # other Roll shapes
+         (192, 30, 56, 2), (384, 13, 28, 2), (768, 9, 14, 3), (1536, 5, 7, 3), (1536, 16, 7, 2)]      # Pair, H != W
+
+
+def all_cases():
+    """every (C, H, W, n) above"""
+    sq = [(C, H, H, n) for C, H, n in SQUARE + LARGE]
+    return sq + TILE + TILE_ODD + BANDS
+
+
+# the kernels dw_select can return, as (kind, C, NS or S) — kind as tests/test_host_cpu.py names gcv_dw_plan's codes
+ROLL = {("roll", 96, 8), ("roll", 96, 4), ("roll", 192, 4), ("roll", 192, 2), ("roll", 384, 2), ("roll", 384, 1),
+        ("roll", 768, 1)}
+MFMA = {("mfma", 96, 8)}                               # 16-bit storage only
+PAIR = {("pair", 192, 8), ("pair", 384, 4), ("pair", 768, 2), ("pair", 1536, 1)}
+TINY = {("tiny", 768, s) for s in (1, 2, 3, 4)} | {("tiny_pair", 1536, s) for s in (1, 2, 3, 4)}
+TILES = {("tile", C, 0) for C in (96, 192, 384, 768)}
+
+
+def reachable(dt):
+    return ROLL | PAIR | TINY | TILES | (MFMA if dt != "f32" else set())

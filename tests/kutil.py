@@ -43,3 +43,16 @@ def tol(dtype, scale=1.0):
 def rnd(shape, seed, scale=1.0):
     g = torch.Generator().manual_seed(seed)
     return (torch.rand(shape, generator=g) * 2 - 1) * scale
+
+
+def frames_at(res, n, name="cnxres"):
+    """n seeded frames (synth.make_frames) brought to res x res on the CPU: average pooling where res divides 224, else
+    antialiased bilinear interpolation.  (B, 3, res, res) fp32."""
+    import torch.nn.functional as F
+    from genconvit_amd import synth
+    x = synth.make_frames(n, name=name)
+    if res == 224:
+        return x
+    if 224 % res == 0:
+        return F.avg_pool2d(x, 224 // res)
+    return F.interpolate(x, size=(res, res), mode="bilinear", align_corners=False, antialias=True).contiguous()

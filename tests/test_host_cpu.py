@@ -107,6 +107,7 @@ def test_dw_plan_table():
     B = 1 ... 256, of the GPU kernel tests, of unaligned operands and of the error cases, as recorded from the launcher
     before its choice moved into one plan (tests/golden/dw_plan.json)."""
     import json
+    from tests import dwcases
     with open(os.path.join(REPO, "tests", "golden", "dw_plan.json")) as f:
         table = {tuple(r[:6]): r[6:] for r in json.load(f)["rows"]}
     need = set()
@@ -117,12 +118,9 @@ def test_dw_plan_table():
                     need |= {(dt, 2 * B, 56 >> i, 56 >> i, C, 1),      # ED: both passes in one launch
                              (dt, B, 56 >> i, 56 >> i, C, 1),          # VAE: backbone(x), backbone(x_hat)
                              (dt, B, 28 >> i, 28 >> i, C, 1)}
-        for C, H, n in [(96, 56, 2), (96, 28, 3), (192, 28, 2), (192, 14, 1), (384, 14, 2), (384, 7, 3), (768, 7, 2),
-                        (768, 3, 3), (768, 1, 5), (768, 2, 3), (768, 4, 2), (96, 56, 17), (384, 14, 70), (96, 56, 64),
-                        (96, 56, 100),                                   # test_kernels_gpu.py: test_dwconv7x7_layernorm
-                        (192, 56, 3), (384, 28, 3), (768, 14, 5), (1536, 7, 3), (1536, 7, 600), (1536, 3, 3),
-                        (1536, 1, 2), (1536, 4, 2)]:                     # test_large_gpu.py
-            need.add((dt, n, H, H, C, 1))
+        for C, H, W, n in dwcases.all_cases():       # the shapes the GPU parity tests run (tests/dwcases.py)
+            need.add((dt, n, H, W, C, 1))
+        need.add((dt, 2, 56, 56, 96, 0))              # ... and their unaligned 56 x 56 launch, which the launcher sends to Tile
     assert need <= set(table), sorted(need - set(table))[:5]
     kinds = {r[1] for r in table.values()}
     assert kinds == set(DW_KINDS) | {None}, kinds
@@ -134,6 +132,67 @@ def test_dw_plan_table():
                 assert "C must be one of" in got[1], got
         else:
             assert got == tuple(want), (key, got, want)
+
+
+def test_every_dw_kernel_has_a_gpu_parity_case():
+    """Per storage dtype, the kernels that gcv_dw_plan picks for the shapes of the GPU parity tests (tests/dwcases.py) are ALL
+    the kernels dw_select (csrc/dwconv_impl.h) can return: as (kind, C, NS) for the band kernels, (kind, C, S) for the
+    whole-map kernels, (tile, C, 0).  A kernel added to dw_select without a GPU case — or a case that stops reaching its
+    kernel — fails here, without a GPU."""
+    from tests import dwcases
+    src = open(os.path.join(REPO, "genconvit_amd", "csrc", "dwconv_impl.h")).read()
+    # the band kernels dw_select names, read from its source: the expected set above is the whole of them
+    named = {(k.lower(), int(c), int(n)) for k, c, n in re.findall(r"go\(DwShape<DwKind::(Roll|Mfma|Pair), (\d+), (\d+)>\{\}\)", src)}
+    assert named == dwcases.ROLL | dwcases.MFMA | dwcases.PAIR, named ^ (dwcases.ROLL | dwcases.MFMA | dwcases.PAIR)
+    for dt in ("f32", "f16", "bf16"):
+        got = set()
+        for C, H, W, n in dwcases.all_cases():
+            plan = _dw_plan(dt, n, H, W, C)
+            assert isinstance(plan[0], str), (dt, C, H, W, n, plan)
+            kind = plan[0]
+            got.add((kind, C, W // 7 if kind in ("roll", "mfma", "pair") else H if kind in ("tiny", "tiny_pair") else 0))
+        assert got == dwcases.reachable(dt), (dt, sorted(got ^ dwcases.reachable(dt)))
+        # the unaligned launch of the GPU tests is the tile kernel's
+        assert _dw_plan(dt, 2, 56, 56, 96, aligned=0)[0] == "tile"
+    # the intent of each list: what it was written to reach
+    for dt in ("f32", "f16", "bf16"):
+        for C, H, W, n in dwcases.TILE + dwcases.TILE_ODD:
+            assert _dw_plan(dt, n, H, W, C)[0] == "tile", (dt, C, H, W, n)
+        for C, H, W, n in dwcases.TILE_ODD:
+            assert (n * -(-H // 7) * -(-W // 7)) % 2 == 1
+            assert _dw_plan(dt, n, H, W, C)[1] == (n * -(-H // 7) * -(-W // 7) + 1) // 2
+        kinds = {_dw_plan(dt, n, H, W, C)[0] for C, H, W, n in dwcases.BANDS}
+        assert kinds == ({"roll", "pair"} if dt == "f32" else {"roll", "pair", "mfma"}), (dt, kinds)
+
+
+_ARCH_DIMS = {0: (96, 192, 384, 768), 1: (192, 384, 768, 1536)}      # GCV_CONVNEXT_TINY / _LARGE (csrc/net.h)
+
+
+def test_every_accepted_resolution_has_a_dw_plan_at_every_stage():
+    """gcv_convnext_forward takes res = 32 ... 224 in steps of 4.  The four maps of a pass are res / 4 pixels wide, halved
+    with floor at each stage boundary; gcv_dw_plan must have a kernel for each of them at any batch (16-byte aligned: the
+    pass's token buffers are 256-byte aligned arena blocks, and a segment starts a whole number of C-channel tokens in) — or
+    gcv_convnext_res_ok, the rule convnext_forward itself applies before it launches anything, refuses the resolution.
+    Both directions: a resolution with all four plans is not refused."""
+    from genconvit_amd import _lib
+    lib = _lib.load()
+    refused = {0: [], 1: []}
+    for arch, dims in _ARCH_DIMS.items():
+        for res in range(32, 228, 4):
+            w, planned = res // 4, True
+            for C in dims:
+                for dt in ("f32", "f16", "bf16"):
+                    for B in (1, 3, 256):
+                        planned = planned and isinstance(_dw_plan(dt, B, w, w, C)[0], str)
+                w //= 2
+            ok = lib.gcv_convnext_res_ok(arch, res) == 1
+            assert ok == planned, (arch, res, ok, planned)
+            if not ok:
+                refused[arch].append(res)
+    assert refused[0] == [] and refused[1] == list(range(160, 224, 4)), refused
+    for arch in (0, 1):
+        for res in (0, 28, 30, 33, 34, 226, 228, 448, -32):
+            assert lib.gcv_convnext_res_ok(arch, res) == 0, (arch, res)
 
 
 def test_isa_report_checks_on_synthetic_assembly(tmp_path):

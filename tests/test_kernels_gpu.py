@@ -9,7 +9,7 @@ import torch
 import torch.nn.functional as F
 
 from genconvit_amd import _lib
-from tests import kutil
+from tests import dwcases, kutil
 from tests.kutil import DTYPES, dev, gemm, ptr, rnd, tol
 
 pytestmark = pytest.mark.gpu
@@ -198,16 +198,43 @@ def test_stem_conv4x4_layernorm(dt, layout, res):
     assert_close(out, want, tol(dtype, 3.0), "stem")
 
 
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+@pytest.mark.parametrize("C", [96, 192])
+@pytest.mark.parametrize("layout", ["nchw", "nhwc"])
+@pytest.mark.parametrize("path", ["out+8B", "x+1elem"])
+def test_stem_valu_kernel_in_16bit_storage(dt, C, layout, path):
+    """stem_ln_kernel<T, C> in 16-bit storage, which aligned operands never reach (they take stem_ln_mfma_kernel):
+    launch_stem_ln_c's `al` test sends a launch there when x is not 8-byte or `out` not 16-byte aligned.
+      out+8B : `out` 8 bytes off a 16-byte boundary, x aligned -> the kernel's 8-byte patch staging (its own `al` looks at x
+               and the strides only); the output is written one element at a time (`o[i] = from_f<T>(...)`).
+      x+1elem: x one element off -> the per-element staging (`to_f(x[...])`); `out` aligned.
+    res 36: 9 x 9 tokens per image, so the last workgroup's token tile is ragged.  Sentinels in front of and behind `out`."""
+    dtype = DTYPES[dt]
+    n, res = 3, 36
+    xs, os_ = (0, 4) if path == "out+8B" else (1, 0)
+    x = q(rnd((n, 3, res, res), 1, 2.0), dtype)
+    w = q(rnd((C, 3, 4, 4), 2, 0.2), dtype)
+    b, lw, lb = rnd((C,), 3, 0.1), rnd((C,), 4, 0.5) + 1.0, rnd((C,), 5, 0.1)
+    want = F.layer_norm(F.conv2d(x, w, b, stride=4).permute(0, 2, 3, 1), (C,), lw, lb, 1e-6)
+    wp = w.reshape(C, 48).t().contiguous().to(dev())
+    if layout == "nchw":
+        flat, st = x, (3 * res * res, res * res, res, 1)
+    else:
+        flat, st = x.permute(0, 2, 3, 1).contiguous(), (res * res * 3, 1, res * 3, 3)
+    xbuf = torch.zeros((xs + flat.numel(),), dtype=dtype, device=dev())
+    xbuf[xs:] = flat.reshape(-1).to(dev(), dtype)
+    T = n * (res // 4) ** 2
+    obuf = torch.full((os_ + (T + 8) * C,), 7.0, dtype=dtype, device=dev())
+    out = obuf[os_:]
+    assert xbuf[xs:].data_ptr() % 8 == 2 * xs and out.data_ptr() % 16 == 2 * os_
+    kutil.call("gcv_k_stem_ln_c", _lib.dtype_code(dtype), ptr(xbuf[xs:]), *st, ptr(wp), ptr(D(b)), ptr(D(lw)), ptr(D(lb)),
+               ptr(out), n, res // 4, res // 4, C, 1e-6)
+    assert (obuf[:os_].float() == 7.0).all() and (out[T * C:].float() == 7.0).all(), "written outside the T tokens"
+    assert_close(out[:T * C].reshape(n, res // 4, res // 4, C), want, tol(dtype, 3.0), "stem (VALU kernel)")
+
+
 @pytest.mark.parametrize("dt", ALL)
-@pytest.mark.parametrize("C,H,n", [(96, 56, 2), (96, 28, 3), (192, 28, 2), (192, 14, 1), (384, 14, 2), (384, 7, 3),
-                                   (768, 7, 2), (768, 3, 3),
-                                   (768, 1, 5), (768, 2, 3), (768, 4, 2),      # whole-map kernel of the tiny stage-3 maps (with (768, 3, 3))
-                                   # launches of more than 128 seven-row bands keep seven-row bands (the large-batch rule);
-                                   # the few-image cases above run the two- to four-row bands of small launches
-                                   (96, 56, 17), (384, 14, 70),
-                                   # 16-bit storage, 56-pixel C = 96 maps in bands of 14 rows and more: the matrix-pipe kernel
-                                   # (dwconv_mfma.h; fp32 storage stays on the VALU kernel): four 14-row bands, ragged 19/19/18
-                                   (96, 56, 64), (96, 56, 100)])
+@pytest.mark.parametrize("C,H,n", dwcases.SQUARE)
 def test_dwconv7x7_layernorm(dt, C, H, n):
     """ConvNeXt block front half: depthwise 7x7 p3 + LayerNorm(C, eps 1e-6), NHWC."""
     dtype = DTYPES[dt]
@@ -222,6 +249,54 @@ def test_dwconv7x7_layernorm(dt, C, H, n):
     kutil.call("gcv_k_dwconv7_ln", _lib.dtype_code(dtype), ptr(xd), ptr(wdw), ptr(D(b)), ptr(D(lw)),
                ptr(D(lb)), ptr(out), n, H, H, C, 1e-6)
     assert_close(out, want, tol(dtype, 3.0), "dwconv_ln")
+
+
+def _dw_case(dtype, C, H, W, n, shift=0):
+    """gcv_k_dwconv7_ln on n maps of H x W x C against F.conv2d + F.layer_norm (fp32, CPU).  The output buffer is one image
+    longer than the launch and pre-filled with a sentinel: nothing behind the last image — and, with `shift` elements of
+    offset from the allocation's start, nothing in front of the first — may be written."""
+    x = q(rnd((n, C, H, W), 1, 2.0), dtype)
+    w = rnd((C, 1, 7, 7), 2, 0.25)
+    b, lw, lb = rnd((C,), 3, 0.1), rnd((C,), 4, 0.5) + 1.0, rnd((C,), 5, 0.1)
+    want = F.layer_norm(F.conv2d(x, w, b, padding=3, groups=C).permute(0, 2, 3, 1), (C,), lw, lb, 1e-6)
+    img = H * W * C
+    xbuf = torch.zeros((shift + n * img,), dtype=dtype, device=dev())
+    xbuf[shift:] = x.permute(0, 2, 3, 1).reshape(-1).to(dev(), dtype)
+    ybuf = torch.full((shift + (n + 1) * img,), 7.0, dtype=dtype, device=dev())
+    xd, out = xbuf[shift:], ybuf[shift:]
+    assert xd.data_ptr() % 16 == (shift * xd.element_size()) % 16 and out.data_ptr() % 16 == xd.data_ptr() % 16
+    wdw = w.reshape(C, 49).t().contiguous().to(dev())
+    kutil.call("gcv_k_dwconv7_ln", _lib.dtype_code(dtype), ptr(xd), ptr(wdw), ptr(D(b)), ptr(D(lw)), ptr(D(lb)), ptr(out),
+               n, H, W, C, 1e-6)
+    assert (ybuf[:shift].float() == 7.0).all() and (out[n * img:].float() == 7.0).all(), "written outside the n images"
+    assert_close(out[:n * img].reshape(n, H, W, C), want, tol(dtype, 3.0), f"dwconv_ln C={C} {H}x{W} n={n}")
+
+
+@pytest.mark.parametrize("dt", ALL)
+@pytest.mark.parametrize("C,H,W,n", dwcases.TILE + dwcases.TILE_ODD)
+def test_dwconv7x7_layernorm_tile_kernel(dt, C, H, W, n):
+    """The generic tile kernel (dwconv7_ln_kernel<T, C>, DwKind::Tile) at each of its four widths: the maps of a res-160 pass
+    (40 / 20 / 10 / 5), odd maps with ragged right and bottom tiles, non-square and single-row maps, and at C = 96 (two
+    tiles per workgroup) odd tile counts, whose last workgroup has an idle second slot.  tests/test_host_cpu.py checks,
+    without a GPU, that each of these shapes plans as Tile."""
+    _dw_case(DTYPES[dt], C, H, W, n)
+
+
+@pytest.mark.parametrize("dt", ALL)
+def test_dwconv7x7_layernorm_unaligned_operands_run_the_tile_kernel(dt):
+    """x and y one element off a 16-byte boundary: launch_dwconv7_ln tests (x | y) & 15 itself and sends the launch to Tile
+    (dw_select: the band kernels are behind `if (aligned)`), whose every global access is one element wide — x through
+    `rp[xoff[s]]`, y through `yb[...] = from_f<T>(...)`, the fp32 taps and LayerNorm vectors one float each
+    (csrc/kernels_dev.h, dwconv7_ln_kernel).  56 x 56 at C = 96 is otherwise the Roll / Mfma shape."""
+    _dw_case(DTYPES[dt], 96, 56, 56, 2, shift=1)
+
+
+@pytest.mark.parametrize("dt", ALL)
+@pytest.mark.parametrize("C,H,W,n", dwcases.BANDS)
+def test_dwconv7x7_layernorm_band_kernels_off_square(dt, C, H, W, n):
+    """The band kernels (Roll, Mfma in 16-bit storage, Pair) with H != W: a single row, fewer rows than the 7 taps, a height
+    that is not a multiple of the band (57 rows: the last band is one row)."""
+    _dw_case(DTYPES[dt], C, H, W, n)
 
 
 @pytest.mark.parametrize("dt", ALL)
@@ -240,6 +315,38 @@ def test_layernorm2d_space_to_depth(dt, C, H):
     kutil.call("gcv_k_ln_patchify", _lib.dtype_code(dtype), ptr(D(x, dtype)), ptr(D(lw)),
                ptr(D(lb)), ptr(out), n, H, H, C, 1e-6)
     assert_close(out, want, tol(dtype, 3.0), "ln_patchify")
+
+
+def _lnp_case(dtype, C, H, W, n, shift=0):
+    x = q(rnd((n, H, W, C), 1, 2.0), dtype)
+    lw, lb = rnd((C,), 4, 0.5) + 1.0, rnd((C,), 5, 0.1)
+    Ho, Wo = H // 2, W // 2
+    y = F.layer_norm(x, (C,), lw, lb, 1e-6)[:, :2 * Ho, :2 * Wo]
+    want = y.reshape(n, Ho, 2, Wo, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(n, Ho, Wo, 4 * C)
+    xbuf = torch.zeros((shift + x.numel(),), dtype=dtype, device=dev())
+    xbuf[shift:] = x.reshape(-1).to(dev(), dtype)
+    out = torch.full((n + 1, Ho, Wo, 4 * C), 7.0, dtype=dtype, device=dev())
+    kutil.call("gcv_k_ln_patchify", _lib.dtype_code(dtype), ptr(xbuf[shift:]), ptr(D(lw)), ptr(D(lb)), ptr(out), n, H, W, C,
+               1e-6)
+    assert (out[n].float() == 7.0).all(), "written beyond the last image"
+    assert_close(out[:n], want, tol(dtype, 3.0), f"ln_patchify C={C} {H}x{W}")
+
+
+@pytest.mark.parametrize("dt", ALL)
+@pytest.mark.parametrize("C,H,W", [(768, 14, 14), (768, 7, 7), (768, 5, 8), (192, 9, 9)])
+def test_layernorm2d_space_to_depth_generic_kernel(dt, C, H, W):
+    """ln_patchify_kernel<T> in every storage dtype: C = 768 (ConvNeXt-L's stage 2 -> 3 boundary) has no vectorised kernel,
+    so 16-bit storage runs the generic one too.  Even and odd maps (last row / column dropped) and a non-square one."""
+    _lnp_case(DTYPES[dt], C, H, W, 3)
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+@pytest.mark.parametrize("H", [28, 7])
+def test_layernorm2d_space_to_depth_2byte_aligned_input(dt, H):
+    """16-bit storage at C = 96 with x two bytes off a 4-byte boundary: launch_ln_patchify's own `al` test ((x | out) & 3)
+    skips ln_patchify_vec_kernel for the generic kernel, which reads `src[c]` and writes `dst[c]` one element at a time
+    (csrc/kernels_dev.h, ln_patchify_kernel)."""
+    _lnp_case(DTYPES[dt], 96, H, H, 2, shift=1)
 
 
 @pytest.mark.parametrize("dt", ALL)
@@ -471,6 +578,67 @@ def test_fused_mlp_layerscale_residual(dt, C, M):
     assert_close(out, want, tol(dtype, 2.0), "fused mlp")
 
 
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+@pytest.mark.parametrize("C,M", [(C, M) for C in (96, 192, 384) for M in (1, 4, 16, 64, 33, 129)])
+def test_fused_mlp_at_a_handful_of_tokens(dt, C, M):
+    """One frame at res 32 is 64 / 16 / 4 / 1 tokens at stages 0 - 3: the fused MLP kinds (Fused96, Xs192, Pair384) far below
+    one token tile, and one token above a 32- and a 128-token tile.  The rows behind M carry a sentinel."""
+    dtype = DTYPES[dt]
+    x = q(rnd((M, C), 1, 1.5), dtype)
+    w1 = q(rnd((4 * C, C), 2, 1 / math.sqrt(C)), dtype)
+    w2 = q(rnd((C, 4 * C), 3, 1 / math.sqrt(4 * C)), dtype)
+    b1, b2, gamma = rnd((4 * C,), 4, 0.1), rnd((C,), 5, 0.1), rnd((C,), 6, 0.5)
+    res = q(rnd((M, C), 7), dtype)
+    want = res + gamma * (q(F.gelu(x @ w1.t() + b1), dtype) @ w2.t() + b2)
+    out = torch.full((M + 8, C), 7.0, dtype=dtype, device=dev())
+    out[:M] = res.to(dev(), dtype)
+    kutil.call("gcv_k_fused_mlp", _lib.dtype_code(dtype), C, ptr(D(x, dtype)), ptr(D(w1, dtype)), ptr(D(b1)),
+               ptr(D(w2)), ptr(D(b2)), ptr(D(gamma)), ptr(out), ptr(out), M)
+    assert (out[M:].float() == 7.0).all(), "rows past M were written"
+    assert_close(out[:M], want, tol(dtype, 2.0), f"fused mlp C={C} M={M}")
+
+
+@pytest.mark.parametrize("dt", ALL)
+@pytest.mark.parametrize("M", [1, 3])
+@pytest.mark.parametrize("N,K", [(3072, 768), (768, 3072), (768, 1536)])
+@pytest.mark.parametrize("epi", ["bias_gelu", "layerscale_residual"])
+def test_gemm_at_one_and_three_rows_with_stage3_shapes(dt, M, N, K, epi):
+    """The tile GEMMs of ConvNeXt-T's stage 3 (fc1, fc2, the down-sampling conv) as one small-resolution frame runs them:
+    1 token at res 32, a few for a small batch.  Rows behind M carry a sentinel."""
+    dtype = DTYPES[dt]
+    A, W = q(rnd((M, K), 1), dtype), q(rnd((N, K), 2, 1 / math.sqrt(K)), dtype)
+    bias = rnd((N,), 3, 0.1)
+    C = torch.full((M + 8, N), 7.0, dtype=dtype, device=dev())
+    if epi == "bias_gelu":
+        gemm(dtype, _lib.A_PLAIN, _lib.EPI_BIAS_ACT, D(A, dtype), D(W, dtype), C, M, N, K, lda=K, ldc=N, bias=D(bias), act=2)
+        want = F.gelu(A @ W.t() + bias)
+    else:
+        gamma, X = rnd((N,), 4, 0.5), q(rnd((M, N), 5), dtype)
+        C[:M] = X.to(dev(), dtype)
+        gemm(dtype, _lib.A_PLAIN, _lib.EPI_RESID, D(A, dtype), D(W, dtype), C, M, N, K, lda=K, ldc=N, bias=D(bias),
+             gamma=D(gamma), resid=C)
+        want = X + gamma * (A @ W.t() + bias)
+    assert (C[M:].float() == 7.0).all(), "rows past M were written"
+    assert_close(C[:M], want, tol(dtype, 2.0), f"gemm {epi} M={M}")
+
+
+@pytest.mark.parametrize("dt", ALL)
+def test_gemm_rejects_a_misaligned_operand(dt):
+    """The GEMM kernels read A and Wt in 16-byte pieces; launch_gemm has no unaligned kernel behind them and refuses the
+    launch.  Asserted as the error it is: nothing is launched, C keeps its sentinel."""
+    dtype = DTYPES[dt]
+    M, N, K = 8, 64, 64
+    buf = torch.zeros((M * K + 1,), dtype=dtype, device=dev())
+    W = torch.zeros((N, K), dtype=dtype, device=dev())
+    C = torch.full((M, N), 7.0, dtype=dtype, device=dev())
+    for A, Wt in ((buf[1:], W), (W, buf[1:])):
+        assert A.data_ptr() % 16 or Wt.data_ptr() % 16
+        with pytest.raises(_lib.GenConViTHipError, match="A/Wt must be 16-byte aligned"):
+            gemm(dtype, _lib.A_PLAIN, _lib.EPI_BIAS_ACT, A, Wt, C, M, N, K, lda=K, ldc=N)
+    torch.cuda.synchronize()
+    assert (C.float() == 7.0).all()
+
+
 # segments: (images, H, W) per segment, in token order
 _LNP_CASES = [
     (96, [(22, 56, 56)]),                          # one segment, 68 992 tokens: 2 156 wave tiles, none ragged
@@ -482,6 +650,9 @@ _LNP_CASES = [
     (192, [(5, 28, 28), (5, 14, 14)]),             # 3 920 + 980: boundary at 122 * 32 + 16, inside a wave tile
     (192, [(1, 14, 14), (2, 28, 28), (3, 6, 10)]),   # boundary at 196 = 6 * 32 + 4, non-square tail segment, 1 944 tokens
     (192, [(67, 28, 28), (67, 14, 14)]),           # 65 660 tokens: 257 passes on 256 persistent workgroups (second pass)
+    (192, [(1, 2, 2)]),                            # one frame at res 32 on a ConvNeXt-T handle: 4 tokens, one patch row
+    (192, [(1, 4, 4)]),                            # ... on a ConvNeXt-L handle (stage 0 is 8 x 8, C = 192; this is 16 tokens)
+    (192, [(3, 2, 2), (1, 4, 4)]),                 # 12 + 16 tokens
 ]
 
 

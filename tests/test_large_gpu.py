@@ -15,7 +15,7 @@ import torch.nn.functional as F
 
 from genconvit_amd import _lib, synth
 from oracle import cpu_ref
-from tests import kutil, largeutil
+from tests import dwcases, kutil, largeutil
 from tests.kutil import DTYPES, dev, ptr, rnd, tol
 
 pytestmark = pytest.mark.gpu
@@ -42,8 +42,7 @@ def err(got, want):
 
 # ----------------------------------------------------------------------------- kernels
 @pytest.mark.parametrize("dt", ALL)
-@pytest.mark.parametrize("C,H,n", [(192, 56, 3), (384, 28, 3), (768, 14, 5), (1536, 7, 3), (1536, 7, 600),
-                                   (1536, 3, 3), (1536, 1, 2), (1536, 4, 2)])
+@pytest.mark.parametrize("C,H,n", dwcases.LARGE)
 def test_dwconv7x7_layernorm_large_shapes(dt, C, H, n):
     """dw 7x7 + LayerNorm at C * W / 7 = 1536 (two channels per lane, dwconv_pair.h) and C = 1536 on maps up to 4 x 4."""
     dtype = DTYPES[dt]
@@ -171,6 +170,60 @@ def test_backbone_forward_large_fp32(res):
         want = largeutil.convnext_large(sd, "", x)
     assert m._get_handle(2).arch == _lib.ARCH_LARGE
     assert err(got, want) <= 1e-3
+
+
+@pytest.mark.parametrize("res", [32, 64, 96, 128, 156, 224])
+def test_backbone_forward_large_fp32_resolutions(res):
+    """ConvNeXt-L alone across its resolution range (stage-3 maps 1, 2, 3, 4, 4 and 7 pixels wide: every S of the C = 1536
+    whole-map kernel and the band kernel; 156: 39 / 19 / 9 / 4, odd at stages 0 - 2) against the fp32 restatement."""
+    m = _ed()
+    x = kutil.frames_at(res, 2)
+    got = m.backbone_forward(x.to(dev())).float().cpu()
+    sd = {k[len("backbone."):]: v for k, v in largeutil.state_dict("ed").items() if k.startswith("backbone.")}
+    with torch.no_grad():
+        want = largeutil.convnext_large(sd, "", x)
+    assert got.shape == want.shape == (2, 1000) and bool(torch.isfinite(got).all())
+    e = err(got, want)
+    print(f"Large fp32 backbone @{res}: {e:.3e}")
+    assert e <= 1e-3
+
+
+@pytest.mark.parametrize("arch,res,match", [
+    ("large", 160, r"multiple of 4 in \[32,156\], or 224, on a ConvNeXt-L handle"),
+    ("tiny", 30, r"multiple of 4 in \[32,224\]")])
+def test_refused_resolutions_leave_the_handle_as_it_was(arch, res, match):
+    """A resolution gcv_convnext_forward does not run is refused with the supported range, before anything is allocated or
+    launched: ConvNeXt-L at res 160 (a 5 x 5 stage-3 map, for which C = 1536 has no depthwise kernel), any handle at a res
+    that is no multiple of 4.  20 refused calls at the handle's max_batch between two ED forwards on the same handle: the
+    second forward is bit-equal to the first.  (Before the refusal moved in front of the pass, a Large pass at res 160
+    failed at stage 3 with its token buffers still allocated from the handle's arena — 236 MB per call at 32 fp32 frames,
+    by the sizes in run_convnext — and Arena::overflow, once set, was never cleared.  Read from the code; the sequence has
+    not been run against the earlier library.)"""
+    if arch == "large":
+        m = _ed()
+    else:
+        from genconvit_amd.model.config import load_config
+        from genconvit_amd.model.genconvit_ed import GenConViTED
+        from tests.conftest import synthetic_sd
+        m = GenConViTED(load_config(), init="empty")
+        m.load_state_dict(synthetic_sd("ed"))
+        m = m.to(dev()).eval()
+    x = synth.make_frames(2).to(dev())
+    first = m(x).clone()
+    h = m._get_handle(2)
+    B = h.max_batch
+    assert lib_res_ok(h.arch, res) == 0
+    bad = F.interpolate(synth.make_frames(B), size=(res, res), mode="bilinear", antialias=True).contiguous().to(dev())
+    for _ in range(20):
+        with pytest.raises(_lib.GenConViTHipError, match=match):
+            m.backbone_forward(bad)
+    assert m._get_handle(B) is h, "the refused calls ran on the same handle"
+    again = m(x)
+    assert torch.equal(first, again)
+
+
+def lib_res_ok(arch, res):
+    return _lib.load().gcv_convnext_res_ok(arch, res)
 
 
 def test_ed_vae_genconvit_large_fp32(monkeypatch):

@@ -89,6 +89,59 @@ def test_convnext_fp32_matches_oracle(res, sd_ed, hf_golden):
     assert err <= FP32_TOL and err_hf <= FP32_TOL
 
 
+# gcv_convnext_forward takes every multiple of 4 in [32, 224]: 49 resolutions.  Their maps are res / 4 pixels wide, halved with
+# floor per stage, so the sweep runs every depthwise kernel a ConvNeXt-T pass can reach (the generic tile kernel wherever the
+# width is not 7 NS, the whole-map kernel of 1 x 1 ... 4 x 4 stage-3 maps), odd maps at every stage (last row / column
+# dropped by the down-sampling) and the MLP / GEMM kernels from 1 token per frame up.
+CNX_RES = list(range(32, 228, 4))
+# 16-bit: a subset that touches each arm.  stage widths: 32: 8/4/2/1, 36: 9/4/2/1 (odd stage 0), 56: 14/7/3/1 (Tile at
+# C = 96, Roll, Tiny 3, 1), 64: 16/8/4/2, 96: 24/12/6/3, 100: 25/12/6/3, 128: 32/16/8/4, 160: 40/20/10/5 (Tile at every
+# stage), 196: 49/24/12/6, 220: 55/27/13/6 (odd at stages 0 - 2: the un-fused LayerNorm-patchify), 224: 56/28/14/7
+CNX_RES_16 = [32, 36, 56, 64, 96, 100, 128, 160, 196, 220, 224]
+# max |logits1000 - same-dtype restatement| over 3 frames, one MI355X run, per resolution of CNX_RES_16 in that order:
+#   fp16: 6.35e-03 6.73e-03 5.86e-03 4.39e-03 3.91e-03 3.91e-03 3.91e-03 3.91e-03 3.91e-03 3.91e-03 2.93e-03
+#   bf16: 4.10e-02 5.08e-02 4.69e-02 3.12e-02 3.12e-02 3.12e-02 3.12e-02 3.12e-02 3.12e-02 3.12e-02 2.34e-02
+# Bound: about 3x the largest (the suite's convention, tests/taputil.py): 6.73e-3 (fp16) and 5.08e-2 (bf16), both at res 36.
+# The logits are stored in the 16-bit dtype and reach |4.8|; one ulp there is 3.906e-3 (fp16) / 3.125e-2 (bf16), and half of
+# that below 4.  Res 96 ... 220 differ from the restatement by exactly one such ulp (a logit on a rounding boundary going
+# the other way), 224 (all |logits| < 4) by 1.5 ulp of the lower binade.  Res 32 ... 56 come to 1.5 - 1.7 ulp, 2.3x the
+# value at 224: their stage-3 map is a single token, so the pooled feature carries one token's rounding error instead of
+# the mean over up to 49, and the restatement's own 16-bit vs fp32 delta — no HIP kernel in it — grows the same way
+# (fp16 4.4e-3 ... 5.0e-3 at 32 ... 56 against 2.9e-3 at 224; bf16 3.7e-2 against 2.0e-2).
+CNX_BOUND_16 = {torch.float16: 2e-2, torch.bfloat16: 1.5e-1}
+
+
+@pytest.mark.parametrize("res", CNX_RES)
+def test_convnext_fp32_every_resolution(res, sd_ed):
+    """ConvNeXt-T alone, fp32, at every resolution gcv_convnext_forward accepts, against the oracle: all 3 x 1000 logits."""
+    from tests import kutil
+    x = kutil.frames_at(res, 3)
+    got = ed_model().backbone_forward(x.cuda()).cpu()
+    want = cpu_ref.convnext_tiny(sd_ed, "backbone.", x)
+    assert got.shape == want.shape == (3, 1000) and bool(torch.isfinite(got).all())
+    err = (got - want).abs().max().item()
+    print(f"\nConvNeXt-T fp32 @{res}: max |logits1000 diff| = {err:.3e} (|want| max {want.abs().max():.2f})")
+    assert err <= FP32_TOL
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("res", CNX_RES_16)
+def test_convnext_16bit_resolutions_vs_same_dtype_restatement(dtype, res, sd_ed):
+    """ConvNeXt-T alone in 16-bit storage against the oracle's same-dtype restatement (cpu_ref.storage_dtype: the CPU
+    evaluation rounded where the HIP path stores, with the even / odd map and fused-epilogue rules), all 3 x 1000 logits."""
+    from tests import kutil
+    x = kutil.frames_at(res, 3).to(dtype).float()
+    got = ed_model(dtype).backbone_forward(x.cuda()).float().cpu()
+    with cpu_ref.storage_dtype(dtype):
+        want = cpu_ref.convnext_tiny(sd_ed, "backbone.", x)
+    want32 = cpu_ref.convnext_tiny(sd_ed, "backbone.", x)
+    assert got.shape == want.shape == (3, 1000) and bool(torch.isfinite(got).all())
+    err = (got - want).abs().max().item()
+    print(f"\nConvNeXt-T {dtype} @{res}: max |logits1000 - same-dtype restatement| = {err:.3e} "
+          f"(restatement vs fp32 oracle {(want - want32).abs().max():.3e}, |want| max {want.abs().max():.2f})")
+    assert err <= CNX_BOUND_16[dtype]
+
+
 def test_ed_vae_fp32_match_huggingface_backed_golden(golden, hf_golden):
     """ED / VAE logits with the backbone evaluated by the independent implementation (the glue around it is the
     reference's own, pinned bit-exact): the HIP path is within 1e-3 of numbers no line of cpu_ref's ConvNeXt produced."""
