@@ -74,6 +74,8 @@ SIGNATURES = {
     "gcv_vote": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "gcv_preprocess": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "gcv_face_crop_resize": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "gcv_cam_overlay": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_float,
+                                c_int, c_void_p, c_void_p]),
     "gcv_vote_segments": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "gcv_tap_set": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t]),
     "gcv_tap_clear": (c_int, [c_void_p]),
@@ -557,18 +559,86 @@ def face_crop_resize(frames_u8, boxes, size=224):
         raise GenConViTHipError("face_crop_resize expects a uint8 device tensor of shape (F,H,W,3)")
     frames_u8 = frames_u8.contiguous()
     nf, h, w, _ = frames_u8.shape
-    b = torch.as_tensor(boxes, dtype=torch.int32).reshape(-1, 5).cpu()
-    if b.numel():
-        f, top, right, bottom, left = b.unbind(1)
-        ok = (f >= 0) & (f < nf) & (top >= 0) & (left >= 0) & (bottom <= h) & (right <= w) & (top < bottom) & (left < right)
-        if not bool(ok.all()):
-            raise GenConViTHipError(f"face_crop_resize: box {int((~ok).nonzero()[0])} lies outside its {h}x{w} frame")
+    b = _check_boxes("face_crop_resize", boxes, nf, h, w)
     out = torch.empty((b.shape[0], size, size, 3), dtype=torch.uint8, device=frames_u8.device)
     if b.shape[0] == 0:
         return out
     bd = b.to(frames_u8.device)
     check(lib.gcv_face_crop_resize(frames_u8.data_ptr(), nf, h, w, bd.data_ptr(), b.shape[0], out.data_ptr(), size,
                                    current_stream_ptr(frames_u8.device)), "gcv_face_crop_resize")
+    return out
+
+
+def _check_boxes(what, boxes, nf, h, w):
+    """``boxes`` as an (n,5) int32 host tensor; a box outside its (h, w) frame is an error."""
+    import torch
+    b = torch.as_tensor(boxes, dtype=torch.int32).reshape(-1, 5).cpu()
+    if b.numel():
+        f, top, right, bottom, left = b.unbind(1)
+        ok = (f >= 0) & (f < nf) & (top >= 0) & (left >= 0) & (bottom <= h) & (right <= w) & (top < bottom) & (left < right)
+        if not bool(ok.all()):
+            raise GenConViTHipError(f"{what}: box {int((~ok).nonzero()[0])} lies outside its {h}x{w} frame")
+    return b
+
+
+_JET = {}
+
+
+def jet_lut(device=None):
+    """The built-in colour map as a (256,3) uint8 tensor: lut[i][c] = rint(255 * clamp(1.5 - |4 i / 255 - (3, 2, 1)[c]|,
+    0, 1)), computed in float64 on the host — blue for 0 through green to red for 1.  ``device``: where to put it (kept
+    per device, as ``cam_overlay``'s default); None: the host."""
+    import torch
+    key = None if device is None else str(torch.device(device))
+    if key not in _JET:
+        i = torch.arange(256, dtype=torch.float64)[:, None]
+        c = torch.tensor([3.0, 2.0, 1.0], dtype=torch.float64)[None, :]
+        lut = torch.round(255.0 * (1.5 - (4.0 * i / 255.0 - c).abs()).clamp(0.0, 1.0)).to(torch.uint8)
+        _JET[key] = lut if device is None else lut.to(device)
+    return _JET[key]
+
+
+def cam_overlay(frames_u8, boxes, maps, alpha=0.5, weighted=True, lut=None, out=None):
+    """Draw evidence maps over their face boxes (``gcv_cam_overlay``, include/genconvit_hip.h: the arithmetic is stated
+    there).  ``frames_u8``: (F,H,W,3) uint8 device tensor (RGB); ``boxes``: (n,5) integers (frame index, top, right,
+    bottom, left), applied in row order; ``maps``: (n,mh,mw) floating point on the same device, one per box, values in
+    [0, 1] (``normalize_cams``), 1 <= mh, mw <= 224; ``alpha`` in [0, 1]: the blend weight, scaled by the map value when
+    ``weighted``; ``lut``: (256,3) uint8 colours (default ``jet_lut``); ``out``: a contiguous tensor like the frames to
+    write into (``out=frames_u8`` draws in place).  Returns the (F,H,W,3) uint8 frames with the overlays drawn."""
+    import torch
+    lib = load()
+    if not (torch.is_tensor(frames_u8) and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3):
+        raise GenConViTHipError("cam_overlay: frames must be a uint8 device tensor of shape (F,H,W,3)")
+    dev = frames_u8.device
+    nf, h, w, _ = frames_u8.shape
+    b = _check_boxes("cam_overlay", boxes, nf, h, w)
+    n = b.shape[0]
+    if not (torch.is_tensor(maps) and maps.is_floating_point() and maps.device == dev and maps.dim() == 3):
+        raise GenConViTHipError(f"cam_overlay: maps must be a floating-point tensor of shape (n,mh,mw) on {dev}")
+    if maps.shape[0] != n:
+        raise GenConViTHipError(f"cam_overlay: maps holds {maps.shape[0]} maps for {n} boxes")
+    mh, mw = maps.shape[1:]
+    if n and not (1 <= mh <= 224 and 1 <= mw <= 224):
+        raise GenConViTHipError(f"cam_overlay: maps of {mh}x{mw} cells; 1 ... 224 a side are accepted")
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise GenConViTHipError(f"cam_overlay: alpha {alpha} outside [0, 1]")
+    if lut is None:
+        lut = jet_lut(dev)
+    elif not (torch.is_tensor(lut) and lut.dtype == torch.uint8 and tuple(lut.shape) == (256, 3) and lut.device == dev):
+        raise GenConViTHipError(f"cam_overlay: lut must be a (256,3) uint8 tensor on {dev}")
+    if not frames_u8.is_cuda:                # last, so that the checks above do not need a device
+        raise GenConViTHipError("cam_overlay: frames must be a uint8 device tensor of shape (F,H,W,3); there is no CPU path")
+    if out is None:
+        out = torch.empty((nf, h, w, 3), dtype=torch.uint8, device=dev)
+    elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.shape == frames_u8.shape and out.device == dev
+              and out.is_contiguous()):
+        raise GenConViTHipError(f"cam_overlay: out must be a contiguous uint8 tensor of shape {tuple(frames_u8.shape)} on {dev}")
+    if nf * h * w == 0:
+        return out
+    src, maps, lut, bd = frames_u8.contiguous(), maps.float().contiguous(), lut.contiguous(), b.to(dev)
+    check(lib.gcv_cam_overlay(src.data_ptr(), nf, h, w, bd.data_ptr() if n else None, n, maps.data_ptr() if n else None,
+                              mh, mw, lut.data_ptr(), float(alpha), 1 if weighted else 0, out.data_ptr(),
+                              current_stream_ptr(dev)), "gcv_cam_overlay")
     return out
 
 

@@ -720,6 +720,14 @@ int gcv_face_crop_resize(const void* frames_u8_nhwc, int nframes, int H, int W, 
                                  size, (hipStream_t)s);
 }
 
+int gcv_cam_overlay(const void* frames_u8_nhwc, int nframes, int H, int W, const int* boxes5, int n, const float* maps,
+                    int mh, int mw, const unsigned char* lut768, float alpha, int weighted, void* out_u8_nhwc,
+                    gcv_stream stream) {
+  GCV_REQUIRE(frames_u8_nhwc && out_u8_nhwc && ((boxes5 && maps && lut768) || n == 0), "cam overlay: null pointer");
+  return launch_cam_overlay((const unsigned char*)frames_u8_nhwc, nframes, H, W, boxes5, n, maps, mh, mw, lut768, alpha,
+                            weighted, (unsigned char*)out_u8_nhwc, (hipStream_t)stream);
+}
+
 int gcv_k_fused_mlp(int dtype, int C, const void* x, const void* w1, const float* b1, const float* w2_f32,
                     const float* b2, const float* gamma, const void* resid, void* out, int M, gcv_stream s) {
   GCV_REQUIRE(dtype == GCV_F16 || dtype == GCV_BF16, "the MLP kernels are built for 16-bit storage");

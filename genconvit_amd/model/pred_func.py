@@ -43,7 +43,7 @@ _STD = torch.tensor(synth.IMAGENET_STD, dtype=torch.float32).view(1, 3, 1, 1)
 def preprocess_frame(frame):
     """uint8 (N,224,224,3) -> normalised fp32 NCHW (reference :95-108 with the 'vid' transform of
     dataset/loader.py:63-65,77), vectorised over the batch instead of a per-frame Python loop."""
-    u8 = torch.as_tensor(np.asarray(frame))
+    u8 = frame if torch.is_tensor(frame) else torch.as_tensor(np.asarray(frame))
     if torch.cuda.is_available() and u8.dtype == torch.uint8:
         # row N1: ship the uint8 crops (4x fewer H2D bytes than fp32) and normalise on the device
         return _lib.preprocess(u8.to(device))
@@ -141,8 +141,8 @@ def face_locations(frames):
 def crop_faces(frames, boxes, size=224):
     """Row N4: crop + ``cv2.INTER_AREA`` resize of every box on the MI355X (``gcv_face_crop_resize``); the RGB<->BGR
     swaps the reference wraps around the resize (:72,86) cancel.  uint8 (n,size,size,3) on the device."""
-    fr = torch.as_tensor(np.ascontiguousarray(frames)).to(device)
-    return _lib.face_crop_resize(fr, boxes, size)
+    fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
+    return _lib.face_crop_resize(fr.to(device), boxes, size)
 
 
 def face_rec(frames, p=None, klass=None, locate=None):
@@ -153,6 +153,56 @@ def face_rec(frames, p=None, klass=None, locate=None):
         return [], 0
     boxes = boxes[:len(frames)]
     return crop_faces(frames, boxes).cpu().numpy(), len(boxes)
+
+
+def _overlay_maps(model, cams, which):
+    """The map ``explain_frames`` draws for each face, (n, side, side) fp32 in [0, 1]: the original-frame pass of the ED,
+    the backbone(x) map of the VAE, or for the ensemble the one ``which`` names ("mean": the mean of the two after each
+    is scaled to [0, 1], not rescaled again)."""
+    net = getattr(model, "net", "genconvit")
+    ed = lambda: normalize_cams(cams["ed"][:, 1])
+    vae = lambda: normalize_cams(cams["vae"])
+    if net in ("ed", "vae"):
+        return ed() if net == "ed" else vae()
+    return ed() if which == "ed" else vae() if which == "vae" else (ed() + vae()) * 0.5
+
+
+def explain_frames(frames, model, boxes=None, locate=None, eps=None, target=None, layer="s3", which="mean", alpha=0.5,
+                   weighted=True, lut=None):
+    """The verdict on the faces of ``frames`` with the evidence drawn over them: returns ``((y, y_val), overlays, boxes)``.
+    ``frames``: uint8 (F,H,W,3) RGB, numpy or tensor; ``boxes``: rows (frame index, top, right, bottom, left) — by default
+    what ``(locate or face_locations)(frames)`` finds —, cut at ``len(frames)`` rows as ``face_rec`` does.  The faces are
+    cropped and normalised on the device (``crop_faces``, ``preprocess_frame``) and run through ``model.explain`` (``eps``,
+    ``target``, ``layer`` as there; the 224-pixel upsampling is skipped); ``(y, y_val)`` is what ``pred_vid_explain`` returns
+    for those crops.  Each face's map (``which``: "ed", "vae" or "mean" for the ensemble; a single network draws its own),
+    scaled to [0, 1], is drawn over its box as a colour heat overlay (``_lib.cam_overlay``: ``alpha``, ``weighted``,
+    ``lut``), sampled from the raw 7 x 7 / 14 x 14 cells at the box's own size and aspect.  ``overlays``: uint8 (F,H,W,3)
+    on the device; ``boxes``: the list used.  No face: ``((None, None), the frames on the device, [])``, nothing is run."""
+    if which not in ("ed", "vae", "mean"):
+        raise ValueError(f"unknown map {which!r}: accepted values are 'ed', 'vae' and 'mean'")
+    fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
+    if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
+        raise _lib.GenConViTHipError("explain_frames: frames must be uint8 of shape (F,H,W,3)")
+    if boxes is None:
+        boxes = (locate or face_locations)(frames)
+    boxes = list(boxes)[:len(fr)]
+    _lib._check_boxes("explain_frames", boxes, *fr.shape[:3])
+    fr = fr.to(device)
+    if len(boxes) == 0:
+        return (None, None), fr, []
+    df = preprocess_frame(crop_faces(fr, boxes))
+    p = next(model.parameters())
+    if df.device != p.device:
+        df = df.to(p.device)
+    logits, cams = model.explain(df, eps=eps, target=target, upsample=False, layer=layer)
+    out = logits.to(p.dtype) if getattr(model, "reference_logits_dtype", False) else logits
+    verdict = max_prediction_value(torch.sigmoid(out.squeeze()))
+    return verdict, _lib.cam_overlay(fr, boxes, _overlay_maps(model, cams, which), alpha, weighted, lut), boxes
+
+
+def explain_video(vid, model, num_frames=15, **kw):
+    """``explain_frames`` on ``num_frames`` frames of the video file ``vid`` (``extract_frames``)."""
+    return explain_frames(extract_frames(vid, num_frames), model, **kw)
 
 
 def df_face(vid, num_frames, net):

@@ -190,6 +190,29 @@ int gcv_preprocess(int dtype, const void* frames_u8_nhwc, void* out_nchw, int n,
 int gcv_face_crop_resize(const void* frames_u8_nhwc, int nframes, int H, int W, const int* boxes5, int n,
                          void* out_u8_nhwc, int size, gcv_stream s);
 
+/* The way back of gcv_face_crop_resize: draw each face's evidence map (gcv_*_explain) over its box of the source frame
+ * as a colour heat overlay, n boxes in one launch, one read and one write of the frames.
+ *   frames  (nframes,H,W,3) uint8 RGB on the device            out  the same shape; out == frames (in place) is allowed
+ *   boxes5  int32 device array of n rows (frame, top, right, bottom, left), as for gcv_face_crop_resize
+ *   maps    (n,mh,mw) fp32 on the device, one per box, 1 <= mh, mw <= 224; values are taken as [0, 1] (clamped)
+ *   lut768  256 x RGB uint8 on the device: the colour of map value k / 255
+ *   alpha   blend weight in [0, 1]; weighted != 0 scales it by the map value, so cold regions of a face stay untouched
+ * out is a copy of frames in which every pixel inside a box is blended with the colour of that box's map at that
+ * position.  Boxes are applied in row order: a later box draws over what an earlier one left, deterministically for
+ * overlapping and nested boxes (every pixel is read and written by one thread).  n == 0 copies the frames; a row outside
+ * its frame draws nothing.  No allocation, copy or synchronisation inside the call.
+ * Arithmetic (fixed, so that a CPU restatement is bit-equal: tests/overlayutil.py).  For row y of a box of height
+ * h = bottom - top, j = y - top (columns alike with w, mw, lx):
+ *   num = max((2j + 1) mh - h, 0);  i0 = num / 2h;  i1 = min(i0 + 1, mh - 1);  ly = float(num - i0 2h) / float(2h)
+ *   v   = (M[i0,j0] (1 - lx) + M[i0,j1] lx) (1 - ly) + (M[i1,j0] (1 - lx) + M[i1,j1] lx) ly, clamped to [0, 1]: every
+ *         multiply and add rounded to fp32 on its own — F.interpolate(map, (h, w), mode="bilinear", align_corners=False)
+ *         sampled straight from the raw cells, not through the 224-pixel crop
+ *   k   = rint(255 v);  a8 = clamp(rint(weighted ? (256 alpha) v : 256 alpha), 0, 256)   (rint: half to even)
+ *   out_c = (frame_c (256 - a8) + lut[k][c] a8 + 128) >> 8 */
+int gcv_cam_overlay(const void* frames_u8_nhwc, int nframes, int H, int W, const int* boxes5, int n, const float* maps,
+                    int mh, int mw, const unsigned char* lut768, float alpha, int weighted, void* out_u8_nhwc,
+                    gcv_stream stream);
+
 /* pred_vid's reduction (model/pred_func.py:120,125): mean2[c] = mean_r sigmoid(logits[r][c]). */
 int gcv_vote(const float* logits, int rows, float* mean2, gcv_stream stream);
 
