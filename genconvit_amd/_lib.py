@@ -74,9 +74,11 @@ SIGNATURES = {
     "gcv_vote": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "gcv_preprocess": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "gcv_face_crop_resize": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "gcv_face_crop_preprocess": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "gcv_cam_overlay": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_float,
                                 c_int, c_void_p, c_void_p]),
     "gcv_vote_segments": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "gcv_vote_windows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "gcv_tap_set": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t]),
     "gcv_tap_clear": (c_int, [c_void_p]),
     "gcv_tap_written": (c_int, [c_void_p, c_char_p]),
@@ -569,6 +571,29 @@ def face_crop_resize(frames_u8, boxes, size=224):
     return out
 
 
+def face_crop_preprocess(frames_u8, boxes, size=224, dtype=None):
+    """``preprocess(face_crop_resize(frames_u8, boxes, size), dtype)`` in one launch (``gcv_face_crop_preprocess``), bit for
+    bit: the boxes of the (F,H,W,3) uint8 device frames go straight to the network's normalised (n,3,size,size) input of
+    ``dtype`` (fp32 by default) with no uint8 image in between.  Boxes as for ``face_crop_resize``: one outside its frame
+    is an error, none give an empty tensor."""
+    import torch
+    lib = load()
+    dtype = dtype or torch.float32
+    if not (frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3):
+        raise GenConViTHipError("face_crop_preprocess expects a uint8 device tensor of shape (F,H,W,3)")
+    frames_u8 = frames_u8.contiguous()
+    nf, h, w, _ = frames_u8.shape
+    b = _check_boxes("face_crop_preprocess", boxes, nf, h, w)
+    code = dtype_code(dtype)
+    out = torch.empty((b.shape[0], 3, size, size), dtype=dtype, device=frames_u8.device)
+    if b.shape[0] == 0:
+        return out
+    bd = b.to(frames_u8.device)
+    check(lib.gcv_face_crop_preprocess(code, frames_u8.data_ptr(), nf, h, w, bd.data_ptr(), b.shape[0], out.data_ptr(),
+                                       size, current_stream_ptr(frames_u8.device)), "gcv_face_crop_preprocess")
+    return out
+
+
 def _check_boxes(what, boxes, nf, h, w):
     """``boxes`` as an (n,5) int32 host tensor; a box outside its (h, w) frame is an error."""
     import torch
@@ -654,6 +679,34 @@ def vote_segments(logits, batch, nets, offsets):
     check(lib.gcv_vote_segments(logits.data_ptr(), int(batch), int(nets), offsets.data_ptr(), nvid, out.data_ptr(),
                                 current_stream_ptr(logits.device)), "gcv_vote_segments")
     return out
+
+
+def vote_windows(logits, batch, nets, ranges):
+    """Per-frame scores and votes over arbitrary frame ranges (``gcv_vote_windows``).  ``logits``: the (nets * batch, 2)
+    rows of one forward, [net 0 frames; net 1 frames]; ``ranges``: (n,2) integers [lo, hi) of frame rows, which may
+    overlap, nest, repeat and come in any order (lo < 0, hi > batch or lo > hi is an error).  Returns ``(frame_p, mean2)``:
+    (batch,2) fp32 mean over nets of sigmoid per frame, and (n,2) fp32 mean of it over each range (0.5 for an empty one)."""
+    import torch
+    lib = load()
+    batch, nets = int(batch), int(nets)
+    if not (torch.is_tensor(logits) and logits.is_cuda):
+        raise GenConViTHipError("vote_windows expects the logits as a device tensor")
+    logits = logits.float().contiguous()
+    if nets not in (1, 2) or batch <= 0 or logits.numel() != 2 * nets * batch:
+        raise GenConViTHipError(f"vote_windows: {logits.numel()} logits for batch {batch} x {nets} nets x 2")
+    r = torch.as_tensor(ranges, dtype=torch.int32).reshape(-1, 2).cpu()
+    if r.numel():
+        ok = (r[:, 0] >= 0) & (r[:, 1] <= batch) & (r[:, 0] <= r[:, 1])
+        if not bool(ok.all()):
+            k = int((~ok).nonzero()[0])
+            raise GenConViTHipError(f"vote_windows: range {k} [{int(r[k, 0])}, {int(r[k, 1])}) is not inside [0, {batch}]")
+    n = r.shape[0]
+    frame_p = torch.empty((batch, 2), dtype=torch.float32, device=logits.device)
+    mean2 = torch.empty((n, 2), dtype=torch.float32, device=logits.device)
+    rd = r.contiguous().to(logits.device)
+    check(lib.gcv_vote_windows(logits.data_ptr(), batch, nets, rd.data_ptr() if n else None, n, frame_p.data_ptr(),
+                               mean2.data_ptr() if n else None, current_stream_ptr(logits.device)), "gcv_vote_windows")
+    return frame_p, mean2
 
 
 def vote(logits):

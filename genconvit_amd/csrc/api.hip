@@ -535,6 +535,11 @@ int gcv_vote_segments(const float* logits, int batch, int nets, const int* offse
   return launch_vote_segments(logits, batch, nets, offsets, n_videos, mean2, (hipStream_t)stream);
 }
 
+int gcv_vote_windows(const float* logits, int batch, int nets, const int* ranges2, int n_ranges, float* frame_p,
+                     float* mean2, gcv_stream stream) {
+  return launch_vote_windows(logits, batch, nets, ranges2, n_ranges, frame_p, mean2, (hipStream_t)stream);
+}
+
 int gcv_tap_set(gcv_handle* h, const char* name, void* dst, size_t bytes) {
   GCV_REQUIRE(h && name, "null handle / tap name");
   GCV_REQUIRE(tap_name_known(name, h->net->arch), std::string("unknown tap '") + name + "'");
@@ -718,6 +723,13 @@ int gcv_face_crop_resize(const void* frames_u8_nhwc, int nframes, int H, int W, 
   GCV_REQUIRE(frames_u8_nhwc && out_u8_nhwc && (boxes5 || n == 0), "face crop: null pointer");
   return launch_face_crop_resize((const unsigned char*)frames_u8_nhwc, nframes, H, W, boxes5, n, (unsigned char*)out_u8_nhwc,
                                  size, (hipStream_t)s);
+}
+
+int gcv_face_crop_preprocess(int dtype, const void* frames_u8_nhwc, int nframes, int H, int W, const int* boxes5, int n,
+                             void* out_nchw, int size, gcv_stream s) {
+  GCV_REQUIRE(frames_u8_nhwc && out_nchw && (boxes5 || n == 0), "face crop: null pointer");
+  DISPATCH_DT(dtype, launch_face_crop_preprocess<T>((const unsigned char*)frames_u8_nhwc, nframes, H, W, boxes5, n,
+                                                    (T*)out_nchw, size, (hipStream_t)s));
 }
 
 int gcv_cam_overlay(const void* frames_u8_nhwc, int nframes, int H, int W, const int* boxes5, int n, const float* maps,

@@ -5,6 +5,7 @@
 // shrink (fp32 area tables, x then y, one multiply and one add per term), and the area-mode bilinear used as soon as a
 // dimension grows (11-bit fixed point) — exactly as oracle/cv_area.py restates it; the kernel is bit-equal to that
 // restatement (tests/test_parity_gpu.py), which itself is unpinned against a real OpenCV build (see its header).
+// gcv_face_crop_preprocess (further down) takes the same pixel straight to the network's normalised NCHW input.
 // fp contraction is off for this TU: every multiply and add rounds on its own, as in the CPU code.
 #pragma clang fp contract(off)
 #include <cfloat>
@@ -54,18 +55,14 @@ __device__ __forceinline__ LinCoef lin_coef(int d, int ssize, double scale, doub
 
 __device__ __forceinline__ unsigned char sat_u8(float v) { return (unsigned char)max(0, min(255, __float2int_rn(v))); }
 
-__global__ void __launch_bounds__(256) face_crop_resize_kernel(const unsigned char* __restrict__ frames, int nframes,
-                                                               int H, int W, const int* __restrict__ boxes, int n,
-                                                               unsigned char* __restrict__ out, int S) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (int64_t)n * S * S) return;
-  const int box = (int)(idx / (S * S)), rem = (int)(idx - (int64_t)box * S * S);
-  const int dy = rem / S, dx = rem - dy * S;
-  const int f = boxes[5 * box], top = boxes[5 * box + 1], right = boxes[5 * box + 2], bottom = boxes[5 * box + 3],
-            left = boxes[5 * box + 4];
-  unsigned char* o = out + idx * 3;
+// One destination pixel (dy, dx) of box row `b` (frame, top, right, bottom, left) resized to S x S: the three bytes cv2
+// would write, in o.  The three regimes of INTER_AREA live here and nowhere else, so every kernel of this TU that needs a
+// crop pixel gets the same bits.  A row outside its frame reads nothing and gives zeros (the host wrappers reject it first).
+__device__ __forceinline__ void area_pixel(const unsigned char* __restrict__ frames, int nframes, int H, int W,
+                                           const int* __restrict__ b, int S, int dy, int dx, unsigned char (&o)[3]) {
+  const int f = b[0], top = b[1], right = b[2], bottom = b[3], left = b[4];
   if (f < 0 || f >= nframes || top < 0 || left < 0 || bottom > H || right > W || top >= bottom || left >= right) {
-    o[0] = o[1] = o[2] = 0;                  // a box outside its frame reads nothing (the host wrapper rejects it first)
+    o[0] = o[1] = o[2] = 0;
     return;
   }
   const int sh = bottom - top, sw = right - left;
@@ -131,6 +128,44 @@ __global__ void __launch_bounds__(256) face_crop_resize_kernel(const unsigned ch
   }
 }
 
+__global__ void __launch_bounds__(256) face_crop_resize_kernel(const unsigned char* __restrict__ frames, int nframes,
+                                                               int H, int W, const int* __restrict__ boxes, int n,
+                                                               unsigned char* __restrict__ out, int S) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)n * S * S) return;
+  const int box = (int)(idx / (S * S)), rem = (int)(idx - (int64_t)box * S * S);
+  const int dy = rem / S, dx = rem - dy * S;
+  unsigned char px[3];
+  area_pixel(frames, nframes, H, W, boxes + 5 * box, S, dy, dx, px);
+  unsigned char* o = out + idx * 3;
+  o[0] = px[0]; o[1] = px[1]; o[2] = px[2];
+}
+
+// gcv_face_crop_preprocess: the crop pixel above, normalised like preprocess_kernel (kernels_dev.h) and written straight to
+// the network's NCHW input — no uint8 image in between.  One thread = one output pixel; consecutive lanes hold consecutive
+// dx of one row, so each of the three plane stores of a wave is one contiguous run (256 B in fp32, 128 B in 16 bit).
+// Two pixels per lane would widen the 16-bit stores to a dword; the kernel's time is expected (not measured) to be the
+// source gather and the area sums, which doubling the work per lane does not shorten, and S may be odd.
+template <typename T>
+__global__ void __launch_bounds__(256) face_crop_preprocess_kernel(const unsigned char* __restrict__ frames, int nframes,
+                                                                   int H, int W, const int* __restrict__ boxes, int n,
+                                                                   T* __restrict__ out, int S) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int hw = S * S;
+  if (idx >= (int64_t)n * hw) return;
+  const int box = (int)(idx / hw), rem = (int)(idx - (int64_t)box * hw);
+  const int dy = rem / S, dx = rem - dy * S;
+  unsigned char px[3];
+  area_pixel(frames, nframes, H, W, boxes + 5 * box, S, dy, dx, px);
+  const float mean[3] = {0.485f, 0.456f, 0.406f};
+  const float stdv[3] = {0.229f, 0.224f, 0.225f};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float v = (float)px[c] / 255.0f;
+    out[((int64_t)box * 3 + c) * hw + rem] = from_f<T>((v - mean[c]) / stdv[c]);
+  }
+}
+
 int launch_face_crop_resize(const unsigned char* frames, int nframes, int H, int W, const int* boxes, int n,
                             unsigned char* out, int S, hipStream_t s) {
   GCV_REQUIRE(nframes > 0 && H > 0 && W > 0 && S > 0 && S <= 4096, "face crop: bad geometry");
@@ -142,5 +177,21 @@ int launch_face_crop_resize(const unsigned char* frames, int nframes, int H, int
   GCV_CHECK_HIP(hipGetLastError());
   return 0;
 }
+
+template <typename T>
+int launch_face_crop_preprocess(const unsigned char* frames, int nframes, int H, int W, const int* boxes, int n, T* out,
+                                int S, hipStream_t s) {
+  GCV_REQUIRE(nframes > 0 && H > 0 && W > 0 && S > 0 && S <= 4096, "face crop: bad geometry");
+  if (n <= 0) return 0;
+  const int64_t total = (int64_t)n * S * S;
+  GCV_REQUIRE(total < ((int64_t)1 << 31) * 256, "face crop: too many output pixels for one launch");
+  hipLaunchKernelGGL((face_crop_preprocess_kernel<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frames,
+                     nframes, H, W, boxes, n, out, S);
+  GCV_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+template int launch_face_crop_preprocess<float>(const unsigned char*, int, int, int, const int*, int, float*, int, hipStream_t);
+template int launch_face_crop_preprocess<half_t>(const unsigned char*, int, int, int, const int*, int, half_t*, int, hipStream_t);
+template int launch_face_crop_preprocess<bf16_t>(const unsigned char*, int, int, int, const int*, int, bf16_t*, int, hipStream_t);
 
 }  // namespace gcv

@@ -21,4 +21,15 @@ int launch_vote_segments(const float* logits, int B, int nets, const int* off, i
   GCV_CHECK_HIP(hipGetLastError());
   return 0;
 }
+int launch_vote_windows(const float* logits, int B, int nets, const int* ranges, int nr, float* frame_p, float* mean2,
+                        hipStream_t s) {
+  GCV_REQUIRE(logits && frame_p && B > 0 && nr >= 0 && (nets == 1 || nets == 2), "vote_windows: bad arguments");
+  GCV_REQUIRE(nr == 0 || (ranges && mean2), "vote_windows: ranges without a place for their means");
+  hipLaunchKernelGGL(vote_frames_kernel, dim3((B + 255) / 256), dim3(256), 0, s, logits, B, nets, frame_p);
+  GCV_CHECK_HIP(hipGetLastError());
+  if (nr == 0) return 0;
+  hipLaunchKernelGGL(vote_windows_kernel, dim3(nr), dim3(64), 0, s, frame_p, B, ranges, mean2);
+  GCV_CHECK_HIP(hipGetLastError());
+  return 0;
+}
 }  // namespace gcv

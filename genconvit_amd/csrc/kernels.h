@@ -72,6 +72,9 @@ template <typename T> int launch_preprocess(const unsigned char* u8, T* out, int
 // N4 (face.hip): crop + cv2.INTER_AREA resize of n face boxes, uint8 RGB
 int launch_face_crop_resize(const unsigned char* frames, int nframes, int H, int W, const int* boxes5, int n,
                             unsigned char* out, int S, hipStream_t s);
+// the same crop pixels, normalised like launch_preprocess and written as NCHW in T: one launch, no uint8 image in between
+template <typename T> int launch_face_crop_preprocess(const unsigned char* frames, int nframes, int H, int W,
+                                                      const int* boxes5, int n, T* out, int S, hipStream_t s);
 // overlay.hip: evidence maps drawn over their face boxes as a colour heat overlay, uint8 RGB frames in and out
 int launch_cam_overlay(const unsigned char* frames, int nframes, int H, int W, const int* boxes5, int n, const float* maps,
                        int mh, int mw, const unsigned char* lut768, float alpha, int weighted, unsigned char* out,
@@ -80,5 +83,7 @@ int launch_kl(const float* partial, int splitk, const float* bias, const float* 
               int N, hipStream_t s);
 int launch_vote(const float* logits, int rows, float* mean2, hipStream_t s);
 int launch_vote_segments(const float* logits, int B, int nets, const int* off, int nvid, float* mean2, hipStream_t s);
+int launch_vote_windows(const float* logits, int B, int nets, const int* ranges2, int n_ranges, float* frame_p,
+                        float* mean2, hipStream_t s);
 
 }  // namespace gcv

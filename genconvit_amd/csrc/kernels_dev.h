@@ -1436,4 +1436,40 @@ static __global__ void __launch_bounds__(64) vote_segments_kernel(const float* _
   }
 }
 
+// ------------------------------------------------------------------ per-frame scores and votes over arbitrary row ranges
+// Same logits layout as above.  Pass 1, one thread per frame: frame_p[f][c] = (1/nets) sum_n sigmoid(logit[n B + f][c]) —
+// every sigmoid is evaluated here, once.  Pass 2, one wave per range [lo, hi) (clamped to [0, B]; ranges may overlap, nest,
+// repeat, come in any order): mean2[k][c] = mean of frame_p over the range, 0.5 for an empty one like vote_segments.
+static __global__ void __launch_bounds__(256) vote_frames_kernel(const float* __restrict__ logits, int B, int nets,
+                                                                 float* __restrict__ frame_p) {
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  if (f >= B) return;
+  float s0 = 0.0f, s1 = 0.0f;
+  for (int n = 0; n < nets; ++n) {
+    const int64_t r = (int64_t)n * B + f;
+    s0 += 1.0f / (1.0f + expf(-logits[2 * r]));
+    s1 += 1.0f / (1.0f + expf(-logits[2 * r + 1]));
+  }
+  frame_p[2 * f] = s0 / (float)nets;
+  frame_p[2 * f + 1] = s1 / (float)nets;
+}
+
+static __global__ void __launch_bounds__(64) vote_windows_kernel(const float* __restrict__ frame_p, int B,
+                                                                 const int* __restrict__ ranges, float* __restrict__ mean2) {
+  const int k = blockIdx.x, lane = threadIdx.x;
+  const int lo = max(ranges[2 * k], 0), hi = min(ranges[2 * k + 1], B);
+  float s0 = 0.0f, s1 = 0.0f;
+  for (int f = lo + lane; f < hi; f += 64) {
+    s0 += frame_p[2 * f];
+    s1 += frame_p[2 * f + 1];
+  }
+  s0 = wave_sum(s0);
+  s1 = wave_sum(s1);
+  if (lane == 0) {
+    const float cnt = (float)(hi - lo);
+    mean2[2 * k] = cnt > 0 ? s0 / cnt : 0.5f;
+    mean2[2 * k + 1] = cnt > 0 ? s1 / cnt : 0.5f;
+  }
+}
+
 }  // namespace gcv

@@ -2,7 +2,8 @@
 
 Same names and argument meaning (``load_genconvit``, ``preprocess_frame``, ``pred_vid``,
 ``max_prediction_value``, ``real_or_fake``, ``df_face``, ``face_rec``, ``extract_frames``,
-``is_video``, ``set_result``, ``store_result``).  ``prediction.py`` star-imports this module and
+``is_video``, ``set_result``, ``store_result``), plus what the reference lacks: evidence maps (``explain_*``) and the
+whole-video scan with per-track sliding-window verdicts (``scan_frames``, ``scan_video``).  ``prediction.py`` star-imports this module and
 relies on ``torch``/``os``/``np`` coming along, so they stay module globals.  The heavy CPU-side
 dependencies (dlib, face_recognition, decord) are imported lazily inside the video / face
 functions so the model path imports on a box without them; cv2 is not needed any more (the crop +
@@ -122,10 +123,11 @@ def extract_frames(video_file, frames_nums=15):
     return vr.get_batch(list(range(0, len(vr), step_size))[:frames_nums]).asnumpy()
 
 
-def face_locations(frames):
+def face_locations(frames, keep_all=False):
     """The detector call of the reference's face_rec (:71-76): dlib's CNN / HOG detector through ``face_recognition``
     on the CPU (third-party; imported lazily).  Returns rows (frame index, top, right, bottom, left), at most
-    ``len(frames)`` of them in frame order — the reference stops filling ``temp_face`` there (:78,88-89)."""
+    ``len(frames)`` of them in frame order — the reference stops filling ``temp_face`` there (:78,88-89).
+    ``keep_all=True`` lifts that cut and returns every face of every frame (``scan_frames``)."""
     import dlib
     import face_recognition
     mod = "cnn" if dlib.DLIB_USE_CUDA else "hog"
@@ -133,7 +135,7 @@ def face_locations(frames):
     for i, frame in enumerate(frames):
         bgr = np.ascontiguousarray(frame[..., ::-1])          # cv2.cvtColor(frame, cv2.COLOR_RGB2BGR) (:72)
         for loc in face_recognition.face_locations(bgr, number_of_times_to_upsample=0, model=mod):
-            if len(boxes) < len(frames):
+            if keep_all or len(boxes) < len(frames):
                 boxes.append((i, *loc))
     return boxes
 
@@ -203,6 +205,198 @@ def explain_frames(frames, model, boxes=None, locate=None, eps=None, target=None
 def explain_video(vid, model, num_frames=15, **kw):
     """``explain_frames`` on ``num_frames`` frames of the video file ``vid`` (``extract_frames``)."""
     return explain_frames(extract_frames(vid, num_frames), model, **kw)
+
+
+def window_ranges(length, window, stride):
+    """The sliding windows over a track of ``length`` frames as ``[(lo, hi), ...]``: none for ``length <= 0``, the whole
+    track for ``length <= window``, else the starts 0, stride, 2 stride, ... while the window fits, plus a last window
+    ending at ``length`` when the stride does not land there — the tail of a track is always covered."""
+    if window < 1 or stride < 1:
+        raise ValueError(f"window_ranges: window {window} and stride {stride} must both be at least 1")
+    if length <= 0:
+        return []
+    if length <= window:
+        return [(0, length)]
+    starts = list(range(0, length - window + 1, stride))
+    if starts[-1] != length - window:
+        starts.append(length - window)
+    return [(s, s + window) for s in starts]
+
+
+def _box_iou(a, b):
+    """IoU of two (top, right, bottom, left) boxes: integer areas, the quotient in float64."""
+    ih = min(a[2], b[2]) - max(a[0], b[0])
+    iw = min(a[1], b[1]) - max(a[3], b[3])
+    inter = ih * iw if ih > 0 and iw > 0 else 0
+    union = (a[2] - a[0]) * (a[1] - a[3]) + (b[2] - b[0]) * (b[1] - b[3]) - inter
+    return float(inter) / float(union) if union > 0 else 0.0
+
+
+def track_boxes(boxes, iou=0.3, max_gap=1):
+    """Link face boxes into tracks.  ``boxes``: rows (frame, top, right, bottom, left) in any order; they are taken frame by
+    frame, ascending.  In frame f a live track (last seen in [f - max_gap, f)) and a box are a candidate pair when the IoU
+    of the box with the track's last box is at least ``iou``; pairs are taken greedily by descending IoU (ties: lower track
+    id, then earlier box row), one box per track and one track per box.  A box left over opens a new track; tracks are
+    numbered by first appearance.  Frames a track skipped (max_gap > 1: a detector run on every k-th frame) are filled by
+    per-coordinate linear interpolation between the two boxes around the gap, floor(a + (b - a) t + 0.5): each coordinate
+    stays between its two ends, and top < bottom, left < right carry over because x -> floor(x + 0.5) is monotone and
+    the ends differ by at least one — so the filled boxes lie inside the frame whenever both ends do and need no clipping.
+    Returns a list of tracks, each a list of (frame, top, right, bottom, left) over consecutive frames."""
+    rows = [tuple(int(v) for v in b) for b in boxes]
+    by_frame = {}
+    for i, b in enumerate(rows):
+        by_frame.setdefault(b[0], []).append(i)
+    tracks = []                                             # per track: the boxes seen, ascending frames
+    for f in sorted(by_frame):
+        live = [t for t, tr in enumerate(tracks) if f - max_gap <= tr[-1][0] < f]
+        pairs = []
+        for t in live:
+            for i in by_frame[f]:
+                v = _box_iou(tracks[t][-1][1:], rows[i][1:])
+                if v >= iou:
+                    pairs.append((-v, t, i))
+        used_t, used_i = set(), set()
+        for _, t, i in sorted(pairs):
+            if t not in used_t and i not in used_i:
+                used_t.add(t)
+                used_i.add(i)
+                tracks[t].append(rows[i])
+        for i in by_frame[f]:
+            if i not in used_i:
+                tracks.append([rows[i]])
+    out = []
+    for tr in tracks:
+        full = [tr[0]]
+        for a, b in zip(tr, tr[1:]):
+            g = b[0] - a[0]
+            for k in range(1, g):
+                full.append((a[0] + k,) + tuple(int(np.floor(a[c] + (b[c] - a[c]) * (k / g) + 0.5)) for c in range(1, 5)))
+            full.append(b)
+        out.append(full)
+    return out
+
+
+def _verdict(m):
+    """(y, y_val) of a mean pair, as ``max_prediction_value`` / ``pred_vids`` compute it."""
+    return int(torch.argmax(m).item()), m[0].item() if m[0] > m[1] else abs(1 - m[1]).item()
+
+
+def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3, window=15, stride=1, max_batch=128,
+                eps=None):
+    """When is a video fake, and whose face: every face of every frame is scored, linked into per-person tracks, and voted
+    over sliding windows of each track.  ``frames``: uint8 (F,H,W,3) RGB, numpy or a tensor on either device.  ``boxes``:
+    rows (frame, top, right, bottom, left); by default the detector — ``locate``, else ``face_locations(..., keep_all=True)``
+    — runs on ``frames[::detect_every]``, handed over as a numpy array on the host whatever ``frames`` is, and its frame
+    indices are mapped back.  ALL faces are kept: the ``len(frames)`` cut is ``face_rec``'s contract, not this function's,
+    and the default detector is called without it.  Tracks: ``track_boxes(boxes, iou, max_gap=detect_every)``, which also fills the frames the detector
+    skipped (``detect_every`` sets that gap for explicit ``boxes`` too).  The crops run in frame order in groups of at most
+    ``max_batch``: of host frames only the frames a group's crops lie on are uploaded (at most ``max_batch`` of them, however
+    far apart), so device memory is bounded by the group, not the video; each group is one ``_lib.face_crop_preprocess`` launch into the model's parameter dtype and one
+    ``model(x)`` — ``model(x, eps=...)`` with the group's rows of ``eps`` (n_crops, latent), given in crop order.  The
+    groups' [net 0 | net 1] logits are put into [net 0 all crops; net 1 all crops] in (track, frame) order on the device,
+    and ONE ``_lib.vote_windows`` call votes every window of every track (``window_ranges(len, window, stride)``), every
+    whole track and everything.  Returns a dict:
+      tracks          the tracks, lists of (frame, top, right, bottom, left)
+      boxes           the crop rows: the tracks concatenated, i.e. (track, frame) order — the order of everything below
+      track_offsets   track t owns crop rows [track_offsets[t], track_offsets[t + 1])
+      frame_scores    (n_crops, 2) fp32 on the device: per crop, the mean over the networks of sigmoid(logits)
+      windows         [(track, first_frame, last_frame, y, y_val), ...], frames inclusive
+      window_means    (n_windows, 2) fp32: the mean pair behind each window's (y, y_val)
+      track_verdicts  [(y, y_val), ...]: ``pred_vid`` over each track's crops
+      verdict         (y, y_val): ``pred_vid`` over all crops
+      segments        [(track, first_frame, last_frame, peak y_val), ...]: the maximal runs of consecutive FAKE windows
+                      (y == 0, what ``real_or_fake`` calls FAKE) of one track, from the first window's first frame to
+                      the last window's last frame
+    No face: ``verdict == (None, None)``, empty lists and tensors, and nothing is launched.  ``reference_logits_dtype`` is
+    honoured as in ``pred_vid_explain``."""
+    fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
+    if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
+        raise _lib.GenConViTHipError("scan_frames: frames must be uint8 of shape (F,H,W,3)")
+    if detect_every < 1 or max_batch < 1:
+        raise ValueError(f"scan_frames: detect_every {detect_every} and max_batch {max_batch} must both be at least 1")
+    window_ranges(1, window, stride)                        # bad window / stride: raise before anything runs
+    if boxes is None:
+        seen = (fr.cpu().numpy() if torch.is_tensor(frames) else np.asarray(frames))[::detect_every]
+        found = locate(seen) if locate is not None else face_locations(seen, keep_all=True)
+        boxes = [(int(b[0]) * detect_every, *b[1:]) for b in found]
+    boxes = [tuple(int(v) for v in b) for b in boxes]
+    _lib._check_boxes("scan_frames", boxes, *fr.shape[:3])
+    p = next(model.parameters())
+    tracks = track_boxes(boxes, iou=iou, max_gap=detect_every)
+    rows = [b for tr in tracks for b in tr]
+    offsets = [0] + [int(v) for v in np.cumsum([len(tr) for tr in tracks])]
+    n = len(rows)
+    res = {"tracks": tracks, "boxes": rows, "track_offsets": offsets, "windows": [], "track_verdicts": [],
+           "verdict": (None, None), "segments": []}
+    if n == 0:
+        res["frame_scores"] = torch.empty((0, 2), dtype=torch.float32, device=p.device)
+        res["window_means"] = torch.empty((0, 2), dtype=torch.float32, device=p.device)
+        return res
+    if eps is not None and eps.shape[0] != n:
+        raise ValueError(f"scan_frames: eps holds {eps.shape[0]} rows for {n} crops")
+    nets = 2 if getattr(model, "net", "genconvit") not in ("ed", "vae") else 1
+    order = sorted(range(n), key=lambda i: (rows[i][0], i))             # frame order
+    parts, src = [], [0] * (nets * n)
+    with torch.no_grad():
+        for g in range(0, n, max_batch):
+            ids = order[g:g + max_batch]
+            used = sorted({rows[i][0] for i in ids})                    # the frames this group's crops lie on, no others
+            at = {f: k for k, f in enumerate(used)}
+            slab = fr.index_select(0, torch.as_tensor(used, device=fr.device)).to(p.device)
+            x = _lib.face_crop_preprocess(slab, [(at[rows[i][0]], *rows[i][1:]) for i in ids], dtype=p.dtype)
+            if eps is not None:
+                logits = model(x, eps=eps[torch.as_tensor(ids, device=eps.device)].to(p.device))
+            else:
+                logits = model(x)
+            if getattr(model, "reference_logits_dtype", False):
+                logits = logits.to(p.dtype)
+            parts.append(logits.reshape(-1, 2))
+            for k in range(nets):                                       # this group's rows are [net 0 | net 1]
+                for j, i in enumerate(ids):
+                    src[k * n + i] = nets * g + k * len(ids) + j
+        logits = torch.cat(parts).index_select(0, torch.as_tensor(src, device=p.device))
+        ranges, wins = [], []
+        for t, tr in enumerate(tracks):
+            for lo, hi in window_ranges(len(tr), window, stride):
+                ranges.append((offsets[t] + lo, offsets[t] + hi))
+                wins.append((t, tr[lo][0], tr[hi - 1][0]))
+        ranges += [(offsets[t], offsets[t + 1]) for t in range(len(tracks))] + [(0, n)]
+        frame_p, mean2 = _lib.vote_windows(logits, n, nets, ranges)
+    means = mean2.cpu()
+    nw = len(wins)
+    res["frame_scores"], res["window_means"] = frame_p, mean2[:nw]
+    res["windows"] = [(*w, *_verdict(means[k])) for k, w in enumerate(wins)]
+    res["track_verdicts"] = [_verdict(means[nw + t]) for t in range(len(tracks))]
+    res["verdict"] = _verdict(means[nw + len(tracks)])
+    run = None
+    for t, first, last, y, y_val in res["windows"] + [(None, 0, 0, 1, 0.0)]:
+        if run is not None and (y != 0 or t != run[0]):
+            res["segments"].append(tuple(run))
+            run = None
+        if y == 0:
+            run = [t, first, last, y_val] if run is None else [t, run[1], last, max(run[3], y_val)]
+    return res
+
+
+def _read_frames(vid, select):
+    """The frames ``select(number of frames)`` of the video file ``vid`` as (uint8 (n,H,W,3) RGB, their indices) — decord,
+    on the CPU (third-party, imported lazily)."""
+    from decord import VideoReader, cpu
+    vr = VideoReader(vid, ctx=cpu(0))
+    index = list(select(len(vr)))
+    return vr.get_batch(index).asnumpy(), index
+
+
+def scan_video(vid, model, every=1, max_frames=None, **kw):
+    """``scan_frames`` on the frames ``range(0, len, every)[:max_frames]`` of the video file ``vid``; the result also
+    holds ``frame_index``, the source frame number of each scanned frame (the frame numbers in ``tracks``, ``windows``
+    and ``segments`` count scanned frames: look them up there)."""
+    if every < 1:
+        raise ValueError(f"scan_video: every {every} must be at least 1")
+    frames, index = _read_frames(vid, lambda n: list(range(0, n, every))[:max_frames])
+    res = scan_frames(frames, model, **kw)
+    res["frame_index"] = [int(i) for i in index]
+    return res
 
 
 def df_face(vid, num_frames, net):

@@ -190,6 +190,16 @@ int gcv_preprocess(int dtype, const void* frames_u8_nhwc, void* out_nchw, int n,
 int gcv_face_crop_resize(const void* frames_u8_nhwc, int nframes, int H, int W, const int* boxes5, int n,
                          void* out_u8_nhwc, int size, gcv_stream s);
 
+/* gcv_face_crop_resize and gcv_preprocess in one launch: the same frames and boxes straight to the network's input,
+ * out (n,3,size,size) NCHW in `dtype` (GCV_F32, GCV_BF16 or GCV_F16), no uint8 image in between.  With u8 exactly the byte
+ * gcv_face_crop_resize writes for that pixel and channel,
+ *   out[b][c][dy][dx] = (T)(((float)u8 / 255.0f - mean_c) / std_c)         (each operation rounded to fp32 on its own),
+ * so the result is bit-equal to gcv_preprocess(gcv_face_crop_resize(...)) for all three dtypes.  A row outside its frame
+ * writes the value of u8 = 0 (and reads nothing); n == 0 launches nothing.  The call allocates, copies and synchronises
+ * nothing. */
+int gcv_face_crop_preprocess(int dtype, const void* frames_u8_nhwc, int nframes, int H, int W, const int* boxes5, int n,
+                             void* out_nchw, int size, gcv_stream s);
+
 /* The way back of gcv_face_crop_resize: draw each face's evidence map (gcv_*_explain) over its box of the source frame
  * as a colour heat overlay, n boxes in one launch, one read and one write of the frames.
  *   frames  (nframes,H,W,3) uint8 RGB on the device            out  the same shape; out == frames (in place) is allowed
@@ -221,6 +231,19 @@ int gcv_vote(const float* logits, int rows, float* mean2, gcv_stream stream);
  * mean2[v][c] = mean over its frames and nets of sigmoid(logit[.][c]) — what max_prediction_value reduces per video. */
 int gcv_vote_segments(const float* logits, int batch, int nets, const int* offsets, int n_videos, float* mean2,
                       gcv_stream stream);
+
+/* Per-frame scores and votes over arbitrary ranges of frame rows, for sliding windows over a face track.  logits as for
+ * gcv_vote_segments ([net 0 frames 0..batch-1; net 1 ...], two columns, nets = 1 or 2).
+ *   frame_p (batch,2) fp32, required: frame_p[f][c] = (1/nets) sum_n sigmoid(logits[n batch + f][c]) — the timeline
+ *   ranges2 int32 device array of n_ranges rows [lo, hi) of frame rows; they may overlap, nest, repeat, come unsorted;
+ *           a row is clamped to [0, batch] (a caller should reject what that would change, as the Python binding does)
+ *   mean2   (n_ranges,2) fp32: mean2[k][c] = mean of frame_p[lo..hi-1][c] = the mean over the range's frames and nets of
+ *           sigmoid(logit) that max_prediction_value reduces; 0.5 for an empty range, like gcv_vote_segments, with which
+ *           it agrees (to fp32 summation order) on a range that is one of its segments
+ * Two small launches on `stream`: every sigmoid is evaluated once, in the frame pass; the range pass reads frame_p.
+ * n_ranges == 0 (ranges2 and mean2 may be null) fills frame_p only. */
+int gcv_vote_windows(const float* logits, int batch, int nets, const int* ranges2, int n_ranges, float* frame_p,
+                     float* mean2, gcv_stream stream);
 
 /* ---- multi-GPU: frame shards, one process per GPU, RCCL over xGMI (new capability: the reference is single
  * device, model/pred_func.py:15).  The only exchange of the path is one all-gather of per-frame logits before the
