@@ -77,6 +77,7 @@ SIGNATURES = {
     "gcv_face_crop_preprocess": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "gcv_cam_overlay": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_float,
                                 c_int, c_void_p, c_void_p]),
+    "gcv_track_match": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gcv_vote_segments": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "gcv_vote_windows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "gcv_tap_set": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t]),
@@ -604,6 +605,61 @@ def _check_boxes(what, boxes, nf, h, w):
         if not bool(ok.all()):
             raise GenConViTHipError(f"{what}: box {int((~ok).nonzero()[0])} lies outside its {h}x{w} frame")
     return b
+
+
+TRACK_GRIDS, TRACK_RADIUS_MAX, TRACK_WEIGHT_MAX = (16, 32, 64), 32, 1024
+
+
+def _check_track_jobs(what, jobs, nf, h, w, grid):
+    """``jobs`` as an (n,17) int32 host tensor (``gcv_track_match``, include/genconvit_hip.h); a frame index out of range, a
+    box outside its (h, w) frame or smaller than ``grid`` a side, or weights outside wa, wb >= 0, 1 <= wa + wb <= 1024 is
+    an error."""
+    import torch
+    j = torch.as_tensor(jobs, dtype=torch.int32).reshape(-1, 17).cpu()
+    if j.numel():
+        ok = torch.ones(j.shape[0], dtype=torch.bool)
+        for c in (0, 5, 11):
+            f, top, right, bottom, left = j[:, c:c + 5].unbind(1)
+            ok &= (f >= 0) & (f < nf) & (top >= 0) & (left >= 0) & (bottom <= h) & (right <= w)
+            ok &= (bottom.long() - top.long() >= grid) & (right.long() - left.long() >= grid)
+        wa, wb = j[:, 10].long(), j[:, 16].long()
+        ok &= (wa >= 0) & (wb >= 0) & (wa + wb >= 1) & (wa + wb <= TRACK_WEIGHT_MAX)
+        if not bool(ok.all()):
+            raise GenConViTHipError(f"{what}: job {int((~ok).nonzero()[0])} has a frame index out of range, a box outside its "
+                                    f"{h}x{w} frame or smaller than {grid} a side, or weights outside 1 <= wa + wb <= "
+                                    f"{TRACK_WEIGHT_MAX}")
+    return j
+
+
+def track_match(frames_u8, jobs, grid=64, radius=16):
+    """Where is the face in a frame the detector skipped (``gcv_track_match``, include/genconvit_hip.h: the arithmetic is
+    stated there): integer block matching on a ``grid`` x ``grid`` lattice of mean-luma cells, searched ``radius`` cells
+    either way around the prior box, against the two detections around the gap.  ``frames_u8``: (F,H,W,3) uint8 device
+    tensor (RGB); ``jobs``: (n,17) integers, per row (fs, top, right, bottom, left) the skipped frame and the prior box,
+    (fa, ta, ra, ba, la, wa) and (fb, tb, rb, bb, lb, wb) the two anchors and their weights.  Returns (n,4) int32 on the
+    device: (oy, ox, best cost, cost at zero displacement) with (oy, ox) the pixel offset to add to the prior box.  A
+    ``grid`` other than 16, 32, 64, a ``radius`` outside 0 ... 32 and a bad row are errors; none give an empty tensor."""
+    import torch
+    lib = load()
+    if not (torch.is_tensor(frames_u8) and frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4
+            and frames_u8.shape[3] == 3):
+        raise GenConViTHipError("track_match expects a uint8 device tensor of shape (F,H,W,3)")
+    grid, radius = int(grid), int(radius)
+    if grid not in TRACK_GRIDS:
+        raise GenConViTHipError(f"track_match: grid {grid}; accepted values are 16, 32 and 64")
+    if not 0 <= radius <= TRACK_RADIUS_MAX:
+        raise GenConViTHipError(f"track_match: radius {radius} outside 0 ... {TRACK_RADIUS_MAX}")
+    frames_u8 = frames_u8.contiguous()
+    nf, h, w, _ = frames_u8.shape
+    j = _check_track_jobs("track_match", jobs, nf, h, w, grid)
+    n = j.shape[0]
+    out = torch.empty((n, 4), dtype=torch.int32, device=frames_u8.device)
+    if n == 0:
+        return out
+    jd = j.contiguous().to(frames_u8.device)
+    check(lib.gcv_track_match(frames_u8.data_ptr(), nf, h, w, jd.data_ptr(), n, grid, radius, out.data_ptr(),
+                              current_stream_ptr(frames_u8.device)), "gcv_track_match")
+    return out
 
 
 _JET = {}

@@ -740,6 +740,13 @@ int gcv_cam_overlay(const void* frames_u8_nhwc, int nframes, int H, int W, const
                             weighted, (unsigned char*)out_u8_nhwc, (hipStream_t)stream);
 }
 
+int gcv_track_match(const void* frames_u8_nhwc, int nframes, int H, int W, const int* jobs17, int n, int grid, int radius,
+                    int* out4, gcv_stream s) {
+  GCV_REQUIRE(n <= 0 || (frames_u8_nhwc && jobs17 && out4), "track match: null pointer");
+  return launch_track_match((const unsigned char*)frames_u8_nhwc, nframes, H, W, jobs17, n, grid, radius, out4,
+                            (hipStream_t)s);
+}
+
 int gcv_k_fused_mlp(int dtype, int C, const void* x, const void* w1, const float* b1, const float* w2_f32,
                     const float* b2, const float* gamma, const void* resid, void* out, int M, gcv_stream s) {
   GCV_REQUIRE(dtype == GCV_F16 || dtype == GCV_BF16, "the MLP kernels are built for 16-bit storage");

@@ -3,7 +3,8 @@
 Same names and argument meaning (``load_genconvit``, ``preprocess_frame``, ``pred_vid``,
 ``max_prediction_value``, ``real_or_fake``, ``df_face``, ``face_rec``, ``extract_frames``,
 ``is_video``, ``set_result``, ``store_result``), plus what the reference lacks: evidence maps (``explain_*``) and the
-whole-video scan with per-track sliding-window verdicts (``scan_frames``, ``scan_video``).  ``prediction.py`` star-imports this module and
+whole-video scan with per-track sliding-window verdicts (``scan_frames``, ``scan_video``; ``follow_tracks`` moves the
+boxes of frames the detector skipped onto the face).  ``prediction.py`` star-imports this module and
 relies on ``torch``/``os``/``np`` coming along, so they stay module globals.  The heavy CPU-side
 dependencies (dlib, face_recognition, decord) are imported lazily inside the video / face
 functions so the model path imports on a box without them; cv2 is not needed any more (the crop +
@@ -232,7 +233,7 @@ def _box_iou(a, b):
     return float(inter) / float(union) if union > 0 else 0.0
 
 
-def track_boxes(boxes, iou=0.3, max_gap=1):
+def track_boxes(boxes, iou=0.3, max_gap=1, return_anchors=False):
     """Link face boxes into tracks.  ``boxes``: rows (frame, top, right, bottom, left) in any order; they are taken frame by
     frame, ascending.  In frame f a live track (last seen in [f - max_gap, f)) and a box are a candidate pair when the IoU
     of the box with the track's last box is at least ``iou``; pairs are taken greedily by descending IoU (ties: lower track
@@ -241,7 +242,9 @@ def track_boxes(boxes, iou=0.3, max_gap=1):
     per-coordinate linear interpolation between the two boxes around the gap, floor(a + (b - a) t + 0.5): each coordinate
     stays between its two ends, and top < bottom, left < right carry over because x -> floor(x + 0.5) is monotone and
     the ends differ by at least one — so the filled boxes lie inside the frame whenever both ends do and need no clipping.
-    Returns a list of tracks, each a list of (frame, top, right, bottom, left) over consecutive frames."""
+    Returns a list of tracks, each a list of (frame, top, right, bottom, left) over consecutive frames; with
+    ``return_anchors=True`` the pair (tracks, anchors), ``anchors[t][i]`` telling whether box i of track t was detected
+    (an input row) rather than filled."""
     rows = [tuple(int(v) for v in b) for b in boxes]
     by_frame = {}
     for i, b in enumerate(rows):
@@ -273,7 +276,83 @@ def track_boxes(boxes, iou=0.3, max_gap=1):
                 full.append((a[0] + k,) + tuple(int(np.floor(a[c] + (b[c] - a[c]) * (k / g) + 0.5)) for c in range(1, 5)))
             full.append(b)
         out.append(full)
+    if return_anchors:
+        seen = [{b[0] for b in tr} for tr in tracks]
+        return out, [[b[0] in s for b in full] for full, s in zip(out, seen)]
     return out
+
+
+def _check_follow(what, grid, radius):
+    if grid not in _lib.TRACK_GRIDS or not 0 <= radius <= _lib.TRACK_RADIUS_MAX:
+        raise ValueError(f"{what}: grid {grid} must be 16, 32 or 64 and radius {radius} lie in 0 ... {_lib.TRACK_RADIUS_MAX}")
+
+
+def follow_tracks(frames, tracks, anchors, grid=64, radius=16, max_frames=128, dev=None):
+    """Move the filled boxes of ``tracks`` onto the face: ``track_boxes`` fills the frames a detector skipped by linear
+    interpolation, which a head that turns, nods or moves on a curve inside the gap leaves behind.  Every filled box
+    between two detected boxes of its track (``anchors``, as ``track_boxes(..., return_anchors=True)`` returns them) is one
+    job of ``_lib.track_match``: the interpolated box is the prior, the detections before and after the gap are the
+    templates, and for frame fa + k of a gap g = fb - fa they weigh g - k and k, so the nearer one counts more.  The box
+    moves by the (oy, ox) found, at most ``radius`` cells of its ``grid`` x ``grid`` lattice either way and never out of the
+    frame; its size stays the interpolated one.  A filled box gets no job and stays as interpolated when one of the three
+    boxes is lower or narrower than ``grid`` pixels, when g > 1024, and before the first or after the last detection.
+    ``frames``: uint8 (F,H,W,3) RGB, numpy or a tensor.  Frames on the GPU are used in place, all jobs in one launch.  Of
+    host frames the jobs go in (fa, fb, fs) order in groups launched one after another, a group being a run of jobs that
+    needs at most ``max_frames`` (>= 3) distinct frames: only those are uploaded (to ``dev``, by default this module's
+    ``device``), so device memory is bounded by the group, not the video.
+    Returns ``(tracks, follow)``: the tracks with the filled boxes moved, and an int32 (n_jobs, 6) array of (track, frame,
+    oy, ox, cost, cost0) rows in (track, frame) order — cost0 is the cost at the interpolated position.
+    What this does not do: sub-cell refinement, a change of box size beyond the interpolation, extending a track past its
+    last detection."""
+    _check_follow("follow_tracks", grid, radius)
+    if max_frames < 3:
+        raise ValueError(f"follow_tracks: max_frames {max_frames} must be at least 3 (a job reads three frames)")
+    fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
+    if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
+        raise _lib.GenConViTHipError("follow_tracks: frames must be uint8 of shape (F,H,W,3)")
+    big = lambda b: b[3] - b[1] >= grid and b[2] - b[4] >= grid
+    jobs = []                                               # (track, index in the track, the 17 integers)
+    for t, (tr, flags) in enumerate(zip(tracks, anchors)):
+        if len(tr) != len(flags):
+            raise ValueError(f"follow_tracks: track {t} has {len(tr)} boxes and {len(flags)} anchor flags")
+        seen = [i for i, d in enumerate(flags) if d]
+        for ia, ib in zip(seen, seen[1:]):
+            a, b = tr[ia], tr[ib]
+            g = b[0] - a[0]
+            if g > _lib.TRACK_WEIGHT_MAX or not (big(a) and big(b)):
+                continue
+            for i in range(ia + 1, ib):
+                k = tr[i][0] - a[0]
+                if 0 < k < g and big(tr[i]):
+                    jobs.append((t, i, tuple(int(v) for v in (*tr[i], *a, g - k, *b, k))))
+    out = [list(tr) for tr in tracks]
+    follow = np.zeros((len(jobs), 6), dtype=np.int32)
+    if not jobs:
+        return out, follow
+    res = np.zeros((len(jobs), 4), dtype=np.int64)
+    if fr.is_cuda:
+        res[:] = _lib.track_match(fr, [j[2] for j in jobs], grid=grid, radius=radius).cpu().numpy()
+    else:
+        groups, used = [], set()
+        for n in sorted(range(len(jobs)), key=lambda n: (jobs[n][2][5], jobs[n][2][11], jobs[n][2][0], n)):
+            need = {jobs[n][2][0], jobs[n][2][5], jobs[n][2][11]}
+            if not groups or len(used | need) > max_frames:
+                groups.append([])
+                used = set()
+            groups[-1].append(n)
+            used |= need
+        for ids in groups:
+            used = sorted({jobs[n][2][c] for n in ids for c in (0, 5, 11)})
+            at = {f: k for k, f in enumerate(used)}
+            slab = fr.index_select(0, torch.as_tensor(used)).to(dev or device)
+            rows = [tuple(at[v] if c in (0, 5, 11) else v for c, v in enumerate(jobs[n][2])) for n in ids]
+            res[ids] = _lib.track_match(slab, rows, grid=grid, radius=radius).cpu().numpy()
+    for n, (t, i, row) in enumerate(jobs):
+        f, top, right, bottom, left = out[t][i]
+        oy, ox = int(res[n, 0]), int(res[n, 1])
+        out[t][i] = (f, top + oy, right + ox, bottom + oy, left + ox)
+        follow[n] = (t, f, oy, ox, res[n, 2], res[n, 3])
+    return out, follow
 
 
 def _verdict(m):
@@ -282,7 +361,7 @@ def _verdict(m):
 
 
 def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3, window=15, stride=1, max_batch=128,
-                eps=None):
+                eps=None, follow=False, follow_grid=64, follow_radius=16):
     """When is a video fake, and whose face: every face of every frame is scored, linked into per-person tracks, and voted
     over sliding windows of each track.  ``frames``: uint8 (F,H,W,3) RGB, numpy or a tensor on either device.  ``boxes``:
     rows (frame, top, right, bottom, left); by default the detector — ``locate``, else ``face_locations(..., keep_all=True)``
@@ -308,13 +387,20 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
                       (y == 0, what ``real_or_fake`` calls FAKE) of one track, from the first window's first frame to
                       the last window's last frame
     No face: ``verdict == (None, None)``, empty lists and tensors, and nothing is launched.  ``reference_logits_dtype`` is
-    honoured as in ``pred_vid_explain``."""
+    honoured as in ``pred_vid_explain``.
+    ``follow=True`` (off by default; for ``detect_every`` > 1, without which no box is filled): before the crops are cut, the
+    boxes that ``track_boxes`` filled are moved onto the face by block matching against the two detections around their gap
+    (``follow_tracks`` with ``follow_grid``, ``follow_radius`` and ``max_batch`` as its ``max_frames``); ``tracks`` and
+    ``boxes`` then hold the followed boxes and the result gains ``follow``, int32 (n_jobs, 6) rows (track, frame, oy, ox,
+    cost, cost0)."""
     fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
     if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
         raise _lib.GenConViTHipError("scan_frames: frames must be uint8 of shape (F,H,W,3)")
     if detect_every < 1 or max_batch < 1:
         raise ValueError(f"scan_frames: detect_every {detect_every} and max_batch {max_batch} must both be at least 1")
     window_ranges(1, window, stride)                        # bad window / stride: raise before anything runs
+    if follow:
+        _check_follow("scan_frames", follow_grid, follow_radius)
     if boxes is None:
         seen = (fr.cpu().numpy() if torch.is_tensor(frames) else np.asarray(frames))[::detect_every]
         found = locate(seen) if locate is not None else face_locations(seen, keep_all=True)
@@ -322,12 +408,19 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
     boxes = [tuple(int(v) for v in b) for b in boxes]
     _lib._check_boxes("scan_frames", boxes, *fr.shape[:3])
     p = next(model.parameters())
-    tracks = track_boxes(boxes, iou=iou, max_gap=detect_every)
+    if follow:
+        tracks, anchors = track_boxes(boxes, iou=iou, max_gap=detect_every, return_anchors=True)
+        tracks, moved = follow_tracks(fr, tracks, anchors, grid=follow_grid, radius=follow_radius,
+                                      max_frames=max(max_batch, 3), dev=p.device)
+    else:
+        tracks = track_boxes(boxes, iou=iou, max_gap=detect_every)
     rows = [b for tr in tracks for b in tr]
     offsets = [0] + [int(v) for v in np.cumsum([len(tr) for tr in tracks])]
     n = len(rows)
     res = {"tracks": tracks, "boxes": rows, "track_offsets": offsets, "windows": [], "track_verdicts": [],
            "verdict": (None, None), "segments": []}
+    if follow:
+        res["follow"] = moved
     if n == 0:
         res["frame_scores"] = torch.empty((0, 2), dtype=torch.float32, device=p.device)
         res["window_means"] = torch.empty((0, 2), dtype=torch.float32, device=p.device)

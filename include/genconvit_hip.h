@@ -223,6 +223,45 @@ int gcv_cam_overlay(const void* frames_u8_nhwc, int nframes, int H, int W, const
                     int mh, int mw, const unsigned char* lut768, float alpha, int weighted, void* out_u8_nhwc,
                     gcv_stream stream);
 
+/* Follow a face between two detector frames: integer block matching of n (track, skipped frame) jobs in one launch.
+ * A whole-video scan runs its CPU face detector on every k-th frame; in a skipped frame the face is searched around the
+ * interpolated ("prior") box, with the two detected faces around the gap as templates.
+ *   frames  (nframes,H,W,3) uint8 RGB on the device, as for gcv_face_crop_resize
+ *   jobs17  int32 device array of n rows:
+ *             fs, top, right, bottom, left      the skipped frame and the prior box in it
+ *             fa, ta, ra, ba, la, wa            anchor a: the detection before the gap, and its weight
+ *             fb, tb, rb, bb, lb, wb            anchor b: the detection after the gap, and its weight
+ *   grid    G: 16, 32 or 64 cells a side;  radius R: 0 ... 32 cells of search range either way
+ *   out4    (n,4) int32: (oy, ox, best cost, cost at zero displacement); (oy, ox) is the pixel offset to add to the prior
+ *           box, whose size does not change
+ * Arithmetic (fixed and all-integer, so that a CPU restatement is bit-equal: tests/followutil.py); a // b is floor
+ * division, also for negative a:
+ *   luma of a pixel   Y = (77 R + 150 G + 29 B + 128) >> 8
+ *   cell edges        for an extent h: e_h(u) = (u h) // G for any integer u; cell u covers the rows [e_h(u), e_h(u + 1))
+ *                     relative to the box top; columns alike with w
+ *   precondition      h >= G and w >= G for the prior box and both anchors, so that no cell is empty
+ *   cell value        (sum of Y over the cell's pixel rectangle + cnt // 2) // cnt, cnt the rectangle's pixels: 0 ... 255
+ *   templates         A[u][v], B[u][v], u, v in [0, G): anchor a's box in frame fa and anchor b's box in frame fb, each
+ *                     with its own height and width — a face that grows or shrinks across the gap is compared at a
+ *                     normalised scale
+ *   search window     V[u][v], u, v in [-R, G + R): frame fs around the prior box, with the prior box's h, w
+ *   displacements     (dy, dx) in [-R, R]^2 count cells, so the search range scales with the face
+ *   cost(dy, dx)      sum over u, v of wa |A[u][v] - V[u + dy][v + dx]| + wb |B[u][v] - V[u + dy][v + dx]|
+ *   valid candidate   0 <= top + e_h(dy) and top + e_h(dy) + h <= H, and the same in x.  e_h(G + dy) = h + e_h(dy), so the
+ *                     cells dy ... dy + G - 1 tile exactly the displaced box: a valid candidate reads only pixels inside the
+ *                     frame, (0, 0) is always valid, and window cells no valid candidate uses are never read
+ *   result            the valid candidate with the smallest (cost, dy dy + dx dx, dy, dx) in lexicographic order:
+ *                     out = (e_h(dy), e_w(dx), cost(dy, dx), cost(0, 0))
+ * Refused before anything is launched (gcv_last_error() says why): grid not 16, 32 or 64; radius outside 0 ... 32;
+ * nframes, H or W not positive (or H W > 2^30).  n == 0 launches nothing.  The rows are the caller's to check (the Python
+ * binding does): frame indices in range, boxes inside the frame, every h, w >= G, wa, wb >= 0 and 1 <= wa + wb <= 1024, which
+ * keeps the cost below 2^31 (64 * 64 * 255 * 1024).  A row that breaks any of this reads nothing and gives (0, 0, 0, 0).
+ * One launch, one workgroup per job; the call allocates, copies and synchronises nothing.
+ * Not done here: sub-cell refinement, a change of box size inside a gap beyond the interpolation, extending a track past
+ * its last detection. */
+int gcv_track_match(const void* frames_u8_nhwc, int nframes, int H, int W, const int* jobs17, int n, int grid, int radius,
+                    int* out4, gcv_stream s);
+
 /* pred_vid's reduction (model/pred_func.py:120,125): mean2[c] = mean_r sigmoid(logits[r][c]). */
 int gcv_vote(const float* logits, int rows, float* mean2, gcv_stream stream);
 
