@@ -158,4 +158,10 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return base + local;
 }
 
+// One-pass LayerNorm statistics (sum / sum of squares) cancel once the channels of a row share an offset: at |mean| / std
+// = 128 the normalised output is off by 2e-2, at 1000 the variance is lost (tests/test_numerics_gpu.py).  The kernels that
+// take them keep the one pass where it is accurate and go over the values they hold in registers a second time where
+// var < E[x^2] / 16 (|mean| / std > 3.9): the variance from the centred values.  kLnRecentre is that fraction.
+constexpr float kLnRecentre = 1.0f / 16.0f;
+
 }  // namespace gcv

@@ -303,7 +303,9 @@ dwconv7_ln_mfma_kernel(const T* __restrict__ x, const float* __restrict__ wdw /*
       }
       const float mean = dw_group_sum<L>(s0 + s1) * (1.0f / C);
       const float ex2 = dw_group_sum<L>(q0 + q1) * (1.0f / C);
-      const float rstd = __builtin_amdgcn_rsqf(fmaxf(fmaf(-mean, mean, ex2), 0.0f) + eps);
+      float var = fmaf(-mean, mean, ex2);
+      if (var < ex2 * kLnRecentre) var = dw_ln_var_centred<L, C>(v, mean);     // second pass where one cancels (common.h)
+      const float rstd = __builtin_amdgcn_rsqf(fmaxf(var, 0.0f) + eps);
       const float nmr = -mean * rstd;
 #if GCV_DW_STAMPS
       asm volatile("" ::"v"(nmr), "v"(rstd));

@@ -63,6 +63,19 @@ template <int L> __device__ __forceinline__ float dw_group_sum(float v) {
   else return wave_sum(v);
 }
 
+// the second pass of the depthwise kernels: a pixel's C channels sit 24 to a lane in groups of L lanes; `mean` is the
+// pixel's, the same in all L lanes
+template <int L, int C> __device__ __forceinline__ float dw_ln_var_centred(const float (&v)[24], float mean) {
+  static_assert(C == 24 * L, "24 channels per lane");
+  float q0 = 0.0f, q1 = 0.0f;
+#pragma unroll
+  for (int e = 0; e < 24; e += 2) {
+    const float d0 = v[e] - mean, d1 = v[e + 1] - mean;
+    q0 = fmaf(d0, d0, q0); q1 = fmaf(d1, d1, q1);
+  }
+  return dw_group_sum<L>(q0 + q1) * (1.0f / C);
+}
+
 #define GCV_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 // ---- inline-asm LDS reads of one staged (fp32) input row; the offsets are instruction immediates ----
@@ -316,7 +329,8 @@ dwconv7_ln_roll_kernel(const T* __restrict__ x, const float* __restrict__ wdw /*
         const float dm = m - mean;
         const float var = dw_group_sum<L>(fmaf(24.0f * dm, dm, qq)) * (1.0f / C);
         rstd = 1.0f / sqrtf(var + eps);
-      } else {                                         // 16-bit storage: sum / sum of squares in one pass, v_rsq_f32
+      } else {                                         // 16-bit storage: sum / sum of squares in one pass, v_rsq_f32;
+                                                       // a second, centred pass where the first cancels (common.h)
         float s0 = 0.0f, s1 = 0.0f, q0 = 0.0f, q1 = 0.0f;
 #pragma unroll
         for (int e = 0; e < 24; e += 2) {
@@ -325,7 +339,9 @@ dwconv7_ln_roll_kernel(const T* __restrict__ x, const float* __restrict__ wdw /*
         }
         mean = dw_group_sum<L>(s0 + s1) * (1.0f / C);
         const float ex2 = dw_group_sum<L>(q0 + q1) * (1.0f / C);
-        rstd = __builtin_amdgcn_rsqf(fmaxf(fmaf(-mean, mean, ex2), 0.0f) + eps);
+        float var = fmaf(-mean, mean, ex2);
+        if (var < ex2 * kLnRecentre) var = dw_ln_var_centred<L, C>(v, mean);   // the L lanes of a pixel decide alike
+        rstd = __builtin_amdgcn_rsqf(fmaxf(var, 0.0f) + eps);
       }
 #if GCV_DW_STAMPS
       asm volatile("" : "+v"(rstd), "+v"(mean));

@@ -291,7 +291,19 @@ __global__ void __launch_bounds__(512, 1) fused_mlp_res_kernel(const MlpArgs a) 
       s1 += __shfl_xor(s1, 32);                            // the other half of the row's channels lives in lane ^ 32
       s2 += __shfl_xor(s2, 32);
       const float mean = s1 * (1.0f / C);
-      const float rstd = __builtin_amdgcn_rsqf(fmaxf(fmaf(-mean, mean, s2 * (1.0f / C)), 0.0f) + a.lnp_eps);
+      float var = fmaf(-mean, mean, s2 * (1.0f / C));
+      if (var < s2 * (kLnRecentre / C)) {
+        // one pass cancels here (common.h, kLnRecentre): the squares of the centred values instead; lanes l and l + 32
+        // hold the same mean and s2 and decide alike
+        s2 = 0.0f;
+#pragma unroll
+        for (int o = 0; o < NO; ++o)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) s2 = fmaf(acc2[o][e] - mean, acc2[o][e] - mean, s2);
+        s2 += __shfl_xor(s2, 32);
+        var = s2 * (1.0f / C);
+      }
+      const float rstd = __builtin_amdgcn_rsqf(fmaxf(var, 0.0f) + a.lnp_eps);
       const float nmr = -mean * rstd;
       // patch position of this lane's token: segment, image, (y, x) -> patch row and the quarter of its 4C columns
       int sg = 0;

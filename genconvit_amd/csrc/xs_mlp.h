@@ -345,7 +345,18 @@ __global__ void __launch_bounds__(512, 2) xs_mlp_kernel(const XsMlpArgs a, const
         s1 += __shfl_xor(s1, 32);
         s2 += __shfl_xor(s2, 32);
         const float mean = s1 * (1.0f / C);
-        const float rstd = __builtin_amdgcn_rsqf(fmaxf(fmaf(-mean, mean, s2 * (1.0f / C)), 0.0f) + a.lnp_eps);
+        // one pass cancels once the channels share an offset (common.h, kLnRecentre): the squares of the centred values
+        // are summed as well, without a branch (one more live register under a branch spills past the scratch budget),
+        // and stand in for E[x^2] - mean^2 where that is below E[x^2] / 16
+        float sc = 0.0f;
+#pragma unroll
+        for (int o = 0; o < NO; ++o)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) sc = fmaf(acc2[o][e] - mean, acc2[o][e] - mean, sc);
+        sc += __shfl_xor(sc, 32);
+        const float var1 = fmaf(-mean, mean, s2 * (1.0f / C));
+        const float var = var1 < s2 * (kLnRecentre / C) ? sc * (1.0f / C) : var1;
+        const float rstd = __builtin_amdgcn_rsqf(fmaxf(var, 0.0f) + a.lnp_eps);
         const float nmr = -mean * rstd;
         int sg = 0;
 #pragma unroll
