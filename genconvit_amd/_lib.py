@@ -78,6 +78,8 @@ SIGNATURES = {
     "gcv_cam_overlay": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_float,
                                 c_int, c_void_p, c_void_p]),
     "gcv_track_match": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gcv_frame_hist": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gcv_hist_diff": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "gcv_vote_segments": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "gcv_vote_windows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "gcv_tap_set": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t]),
@@ -660,6 +662,59 @@ def track_match(frames_u8, jobs, grid=64, radius=16):
     check(lib.gcv_track_match(frames_u8.data_ptr(), nf, h, w, jd.data_ptr(), n, grid, radius, out.data_ptr(),
                               current_stream_ptr(frames_u8.device)), "gcv_track_match")
     return out
+
+
+CUT_REGIONS, CUT_BINS = (1, 2, 4, 8), 64
+
+
+def frame_hist(frames_u8, regions=4, out=None):
+    """Luma histograms of the ``regions`` x ``regions`` parts of every frame (``gcv_frame_hist``, include/genconvit_hip.h: the
+    arithmetic is stated there).  ``frames_u8``: (F,H,W,3) uint8 device tensor (RGB), F >= 1; a slice such as ``frames[1:]``
+    is used in place, whatever its alignment.  Returns (F, regions^2, 64) int32 on the device: the C entry's uint32 counts,
+    which stay below 2^31 (a frame holds at most 2^30 pixels).  ``out``: write into this contiguous int32 tensor of that
+    shape on the same device instead of a new one (the rows of one group of frames in a whole video's buffer).  ``regions``
+    other than 1, 2, 4, 8, a frame lower or narrower than ``regions``, more than 2^30 pixels a frame, a host tensor and a
+    wrong shape or dtype are errors."""
+    import torch
+    if not (torch.is_tensor(frames_u8) and frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4
+            and frames_u8.shape[3] == 3 and frames_u8.shape[0] >= 1):
+        raise GenConViTHipError("frame_hist expects a uint8 device tensor of shape (F,H,W,3), F >= 1")
+    if isinstance(regions, bool) or not isinstance(regions, int) or regions not in CUT_REGIONS:
+        raise GenConViTHipError(f"frame_hist: regions {regions}; accepted values are 1, 2, 4 and 8")
+    frames_u8 = frames_u8.contiguous()
+    nf, h, w, _ = frames_u8.shape
+    if h < regions or w < regions or h * w > 1 << 30:
+        raise GenConViTHipError(f"frame_hist: frames of {h}x{w} pixels; each side must be at least regions = {regions} and "
+                                f"a frame hold at most 2^30 pixels")
+    shape = (nf, regions * regions, CUT_BINS)
+    if out is None:
+        hist = torch.empty(shape, dtype=torch.int32, device=frames_u8.device)
+    elif (torch.is_tensor(out) and out.dtype == torch.int32 and out.device == frames_u8.device and tuple(out.shape) == shape
+          and out.is_contiguous()):
+        hist = out
+    else:
+        raise GenConViTHipError(f"frame_hist: out must be a contiguous int32 tensor of shape {shape} on {frames_u8.device}")
+    check(load().gcv_frame_hist(frames_u8.data_ptr(), nf, h, w, regions, hist.data_ptr(), current_stream_ptr(frames_u8.device)),
+          "gcv_frame_hist")
+    return hist
+
+
+def hist_diff(hist):
+    """L1 distance between the histograms of consecutive frames (``gcv_hist_diff``).  ``hist``: (F, R^2, 64) int32 device
+    tensor as ``frame_hist`` returns it, R in 1, 2, 4, 8.  Returns (F - 1, R^2) int32 on the device, empty for F = 1 (nothing
+    is launched).  A distance is at most twice the region's pixel count; the one value that does not fit int32, 2^31 (a
+    whole frame of 2^30 pixels at R = 1 with disjoint histograms), reads -2^31: view the tensor's numpy array as uint32."""
+    import torch
+    if not (torch.is_tensor(hist) and hist.is_cuda and hist.dtype == torch.int32 and hist.dim() == 3
+            and hist.shape[0] >= 1 and hist.shape[2] == CUT_BINS and hist.shape[1] in [r * r for r in CUT_REGIONS]):
+        raise GenConViTHipError("hist_diff expects an int32 device tensor of shape (F, R^2, 64), F >= 1, R in 1, 2, 4, 8")
+    hist = hist.contiguous()
+    nf, rr, _ = hist.shape
+    dist = torch.empty((nf - 1, rr), dtype=torch.int32, device=hist.device)
+    if nf > 1:
+        check(load().gcv_hist_diff(hist.data_ptr(), nf, CUT_REGIONS[[r * r for r in CUT_REGIONS].index(rr)], dist.data_ptr(),
+                                current_stream_ptr(hist.device)), "gcv_hist_diff")
+    return dist
 
 
 _JET = {}

@@ -747,6 +747,16 @@ int gcv_track_match(const void* frames_u8_nhwc, int nframes, int H, int W, const
                             (hipStream_t)s);
 }
 
+int gcv_frame_hist(const void* frames_u8_nhwc, int nframes, int H, int W, int regions, uint32_t* hist_u32, gcv_stream s) {
+  GCV_REQUIRE(frames_u8_nhwc && hist_u32, "frame hist: null pointer");
+  return launch_frame_hist((const unsigned char*)frames_u8_nhwc, nframes, H, W, regions, hist_u32, (hipStream_t)s);
+}
+
+int gcv_hist_diff(const uint32_t* hist_u32, int nframes, int regions, uint32_t* dist_u32, gcv_stream s) {
+  GCV_REQUIRE(nframes == 1 || (hist_u32 && dist_u32), "hist diff: null pointer");
+  return launch_hist_diff(hist_u32, nframes, regions, dist_u32, (hipStream_t)s);
+}
+
 int gcv_k_fused_mlp(int dtype, int C, const void* x, const void* w1, const float* b1, const float* w2_f32,
                     const float* b2, const float* gamma, const void* resid, void* out, int M, gcv_stream s) {
   GCV_REQUIRE(dtype == GCV_F16 || dtype == GCV_BF16, "the MLP kernels are built for 16-bit storage");

@@ -82,6 +82,10 @@ int launch_cam_overlay(const unsigned char* frames, int nframes, int H, int W, c
 // follow.hip: block matching of a face between two detector frames, n jobs of 17 ints -> n rows (oy, ox, cost, cost0)
 int launch_track_match(const unsigned char* frames, int nframes, int H, int W, const int* jobs17, int n, int grid,
                        int radius, int* out4, hipStream_t s);
+// cuts.hip: 64-bin luma histograms of the regions x regions parts of every frame, and their L1 distance between
+// consecutive frames
+int launch_frame_hist(const unsigned char* frames, int nframes, int H, int W, int regions, uint32_t* hist, hipStream_t s);
+int launch_hist_diff(const uint32_t* hist, int nframes, int regions, uint32_t* dist, hipStream_t s);
 int launch_kl(const float* partial, int splitk, const float* bias, const float* mu, float* rowsum, float* kl, int B,
               int N, hipStream_t s);
 int launch_vote(const float* logits, int rows, float* mean2, hipStream_t s);

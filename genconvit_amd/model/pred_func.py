@@ -4,7 +4,7 @@ Same names and argument meaning (``load_genconvit``, ``preprocess_frame``, ``pre
 ``max_prediction_value``, ``real_or_fake``, ``df_face``, ``face_rec``, ``extract_frames``,
 ``is_video``, ``set_result``, ``store_result``), plus what the reference lacks: evidence maps (``explain_*``) and the
 whole-video scan with per-track sliding-window verdicts (``scan_frames``, ``scan_video``; ``follow_tracks`` moves the
-boxes of frames the detector skipped onto the face).  ``prediction.py`` star-imports this module and
+boxes of frames the detector skipped onto the face, ``shot_cuts`` finds the hard cuts at which tracks end).  ``prediction.py`` star-imports this module and
 relies on ``torch``/``os``/``np`` coming along, so they stay module globals.  The heavy CPU-side
 dependencies (dlib, face_recognition, decord) are imported lazily inside the video / face
 functions so the model path imports on a box without them; cv2 is not needed any more (the crop +
@@ -233,7 +233,7 @@ def _box_iou(a, b):
     return float(inter) / float(union) if union > 0 else 0.0
 
 
-def track_boxes(boxes, iou=0.3, max_gap=1, return_anchors=False):
+def track_boxes(boxes, iou=0.3, max_gap=1, return_anchors=False, cuts=None):
     """Link face boxes into tracks.  ``boxes``: rows (frame, top, right, bottom, left) in any order; they are taken frame by
     frame, ascending.  In frame f a live track (last seen in [f - max_gap, f)) and a box are a candidate pair when the IoU
     of the box with the track's last box is at least ``iou``; pairs are taken greedily by descending IoU (ties: lower track
@@ -244,14 +244,19 @@ def track_boxes(boxes, iou=0.3, max_gap=1, return_anchors=False):
     the ends differ by at least one — so the filled boxes lie inside the frame whenever both ends do and need no clipping.
     Returns a list of tracks, each a list of (frame, top, right, bottom, left) over consecutive frames; with
     ``return_anchors=True`` the pair (tracks, anchors), ``anchors[t][i]`` telling whether box i of track t was detected
-    (an input row) rather than filled."""
+    (an input row) rather than filled.
+    ``cuts``: frame numbers at which a new shot starts (``shot_cuts``).  A track whose last box is in frame l is live for
+    frame f only if no cut c has l < c <= f: a track never crosses a cut, and since only the gaps inside a track are
+    filled, no box is interpolated across one.  ``None`` and an empty list change nothing."""
     rows = [tuple(int(v) for v in b) for b in boxes]
+    cuts = [int(c) for c in cuts] if cuts is not None else []
     by_frame = {}
     for i, b in enumerate(rows):
         by_frame.setdefault(b[0], []).append(i)
     tracks = []                                             # per track: the boxes seen, ascending frames
     for f in sorted(by_frame):
-        live = [t for t, tr in enumerate(tracks) if f - max_gap <= tr[-1][0] < f]
+        live = [t for t, tr in enumerate(tracks) if f - max_gap <= tr[-1][0] < f and
+                not any(tr[-1][0] < c <= f for c in cuts)]
         pairs = []
         for t in live:
             for i in by_frame[f]:
@@ -355,13 +360,66 @@ def follow_tracks(frames, tracks, anchors, grid=64, radius=16, max_frames=128, d
     return out, follow
 
 
+def _check_cuts(what, threshold, regions):
+    if not 0.0 < threshold <= 1.0:
+        raise ValueError(f"{what}: threshold {threshold} must lie in (0, 1]")
+    if isinstance(regions, bool) or not isinstance(regions, int) or regions not in _lib.CUT_REGIONS:
+        raise ValueError(f"{what}: regions {regions} must be 1, 2, 4 or 8")
+
+
+def shot_cuts(frames, threshold=0.4, regions=4, max_frames=128, dev=None):
+    """Where the hard cuts of a video are.  ``track_boxes`` links faces by position alone, and after a cut the face of
+    another person often sits where the last one sat; a track must end there.  Every frame is cut into ``regions`` x
+    ``regions`` parts (R = 1, 2, 4 or 8; part (u, v) covers rows [(u H) // R, ((u + 1) H) // R) and the columns alike), each
+    part gets a 64-bin luma histogram (``_lib.frame_hist``), and ``_lib.hist_diff`` gives dist[p][r], the L1 distance
+    between the histograms of part r in frames p and p + 1 — integers, at most twice the part's pixel count n_r.  The score
+    of the pair p keeps the max(1, R^2 // 2) parts with the smallest (dist[p][r], r):
+        scores[p] = sum of the kept dist / (2 * sum of the kept n_r),   a value in [0, 1].
+    Dropping the half of the parts that changed most keeps a moving head from counting as a cut; a cut changes every part.
+    ``frames``: uint8 (F,H,W,3) RGB, numpy or a tensor.  Frames on the GPU are used in place: one ``frame_hist`` and one
+    ``hist_diff`` launch.  Host frames are uploaded (to ``dev``, by default this module's ``device``) in consecutive groups of
+    at most ``max_frames``, one ``frame_hist`` launch per group into its rows of a single (F, R^2, 64) device buffer (4 KB
+    a frame at R = 4), then one ``hist_diff`` over the whole buffer: device memory for pixels is bounded by the group, not
+    the video.
+    Returns ``(cuts, scores)``: ``scores`` float64 numpy (F - 1,), and ``cuts`` the ascending frame numbers c = p + 1 with
+    scores[p] >= ``threshold`` — a new shot starts at frame c.  F <= 1 gives ([], empty) and launches nothing; a
+    ``threshold`` outside (0, 1] is a ValueError.
+    What this does not do: fades and dissolves are not detected, only hard cuts; a one-frame flash gives two adjacent
+    cuts; two shots with the same luma distribution in every part are not separated.  The default threshold is a starting
+    value from synthetic material (about 0.05 inside a shot, about 0.7 at a cut); no accuracy is claimed — look at the
+    scores and choose."""
+    _check_cuts("shot_cuts", threshold, regions)
+    if max_frames < 1:
+        raise ValueError(f"shot_cuts: max_frames {max_frames} must be at least 1")
+    fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
+    if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
+        raise _lib.GenConViTHipError("shot_cuts: frames must be uint8 of shape (F,H,W,3)")
+    nf, h, w = (int(v) for v in fr.shape[:3])
+    if nf <= 1:
+        return [], np.empty((0,), dtype=np.float64)
+    if fr.is_cuda:
+        hist = _lib.frame_hist(fr, regions)
+    else:
+        hist = torch.empty((nf, regions * regions, _lib.CUT_BINS), dtype=torch.int32, device=dev or device)
+        for g in range(0, nf, max_frames):
+            _lib.frame_hist(fr[g:g + max_frames].to(hist.device), regions, out=hist[g:g + max_frames])
+    dist = _lib.hist_diff(hist).cpu().numpy().view(np.uint32).astype(np.int64)              # (F - 1, R^2)
+    ey = [(u * h) // regions for u in range(regions + 1)]
+    ex = [(v * w) // regions for v in range(regions + 1)]
+    pixels = np.array([(ey[u + 1] - ey[u]) * (ex[v + 1] - ex[v]) for u in range(regions) for v in range(regions)],
+                      dtype=np.int64)
+    kept = np.argsort(dist, axis=1, kind="stable")[:, :max(1, regions * regions // 2)]       # ties: the lower r
+    scores = np.take_along_axis(dist, kept, 1).sum(1) / (2.0 * pixels[kept].sum(1))
+    return [int(p) + 1 for p in np.nonzero(scores >= threshold)[0]], scores
+
+
 def _verdict(m):
     """(y, y_val) of a mean pair, as ``max_prediction_value`` / ``pred_vids`` compute it."""
     return int(torch.argmax(m).item()), m[0].item() if m[0] > m[1] else abs(1 - m[1]).item()
 
 
 def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3, window=15, stride=1, max_batch=128,
-                eps=None, follow=False, follow_grid=64, follow_radius=16):
+                eps=None, follow=False, follow_grid=64, follow_radius=16, cuts=None, cut_threshold=0.4, cut_regions=4):
     """When is a video fake, and whose face: every face of every frame is scored, linked into per-person tracks, and voted
     over sliding windows of each track.  ``frames``: uint8 (F,H,W,3) RGB, numpy or a tensor on either device.  ``boxes``:
     rows (frame, top, right, bottom, left); by default the detector — ``locate``, else ``face_locations(..., keep_all=True)``
@@ -392,10 +450,27 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
     boxes that ``track_boxes`` filled are moved onto the face by block matching against the two detections around their gap
     (``follow_tracks`` with ``follow_grid``, ``follow_radius`` and ``max_batch`` as its ``max_frames``); ``tracks`` and
     ``boxes`` then hold the followed boxes and the result gains ``follow``, int32 (n_jobs, 6) rows (track, frame, oy, ox,
-    cost, cost0)."""
+    cost, cost0).
+    ``cuts`` (``None`` by default: nothing changes): the hard cuts of edited footage, at which every track ends — after a cut
+    the face of another person often sits where the last one sat, and IoU alone would join the two.  ``True``:
+    ``shot_cuts(frames, cut_threshold, cut_regions, max_frames=max_batch)`` over ALL scanned frames, not only the
+    detector's (this runs even when no face is found); a list: the frame numbers at which a new shot starts, integers in
+    [1, F - 1], anything else is a ValueError.  They go to ``track_boxes``, so no track, and therefore no window, no
+    segment and no ``follow`` job, straddles a cut.  The result gains ``cuts``, and ``cut_scores`` (float64 (F - 1,)) when
+    they were computed here: the default threshold is a starting value, not a tuned one.  With ``detect_every`` > 1 a face
+    goes unscored between its last detection before a cut and its first detection after it: tracks are not extended past
+    a detection.  Fades and dissolves are not found, and a one-frame flash gives two adjacent cuts."""
     fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
     if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
         raise _lib.GenConViTHipError("scan_frames: frames must be uint8 of shape (F,H,W,3)")
+    if cuts is True:
+        _check_cuts("scan_frames", cut_threshold, cut_regions)
+    elif cuts is not None:
+        given = list(cuts) if isinstance(cuts, (list, tuple, np.ndarray)) else None
+        if given is None or not all(isinstance(c, (int, np.integer)) and not isinstance(c, bool) and
+                                    1 <= c < fr.shape[0] for c in given):
+            raise ValueError(f"scan_frames: cuts must be True or a list of integers in [1, {fr.shape[0] - 1}]")
+        cuts = sorted({int(c) for c in given})
     if detect_every < 1 or max_batch < 1:
         raise ValueError(f"scan_frames: detect_every {detect_every} and max_batch {max_batch} must both be at least 1")
     window_ranges(1, window, stride)                        # bad window / stride: raise before anything runs
@@ -408,12 +483,15 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
     boxes = [tuple(int(v) for v in b) for b in boxes]
     _lib._check_boxes("scan_frames", boxes, *fr.shape[:3])
     p = next(model.parameters())
+    cut_scores = None
+    if cuts is True:
+        cuts, cut_scores = shot_cuts(fr, cut_threshold, cut_regions, max_frames=max_batch, dev=p.device)
     if follow:
-        tracks, anchors = track_boxes(boxes, iou=iou, max_gap=detect_every, return_anchors=True)
+        tracks, anchors = track_boxes(boxes, iou=iou, max_gap=detect_every, return_anchors=True, cuts=cuts)
         tracks, moved = follow_tracks(fr, tracks, anchors, grid=follow_grid, radius=follow_radius,
                                       max_frames=max(max_batch, 3), dev=p.device)
     else:
-        tracks = track_boxes(boxes, iou=iou, max_gap=detect_every)
+        tracks = track_boxes(boxes, iou=iou, max_gap=detect_every, cuts=cuts)
     rows = [b for tr in tracks for b in tr]
     offsets = [0] + [int(v) for v in np.cumsum([len(tr) for tr in tracks])]
     n = len(rows)
@@ -421,6 +499,10 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
            "verdict": (None, None), "segments": []}
     if follow:
         res["follow"] = moved
+    if cuts is not None:
+        res["cuts"] = cuts
+        if cut_scores is not None:
+            res["cut_scores"] = cut_scores
     if n == 0:
         res["frame_scores"] = torch.empty((0, 2), dtype=torch.float32, device=p.device)
         res["window_means"] = torch.empty((0, 2), dtype=torch.float32, device=p.device)

@@ -262,6 +262,34 @@ int gcv_cam_overlay(const void* frames_u8_nhwc, int nframes, int H, int W, const
 int gcv_track_match(const void* frames_u8_nhwc, int nframes, int H, int W, const int* jobs17, int n, int grid, int radius,
                     int* out4, gcv_stream s);
 
+/* Shot cuts: per-region luma histograms of every frame (gcv_frame_hist) and their L1 distance between consecutive frames
+ * (gcv_hist_diff).  A whole-video scan links face boxes into tracks by position; after a hard cut the face of another
+ * person often sits where the last one sat.  pred_func.shot_cuts turns the distances into cuts, at which tracks end.
+ *   frames   (nframes,H,W,3) uint8 RGB on the device, as for gcv_face_crop_resize; the pointer may have any alignment (a
+ *            slice frames[1:] of a 37 x 53 video starts 5 883 bytes in), and no byte outside
+ *            [frames, frames + nframes H W 3) is read
+ *   regions  R: 1, 2, 4 or 8; a frame is cut into R x R regions
+ *   hist     (nframes, R R, 64) uint32: hist[f][u R + v][b] = the number of pixels of region (u, v) of frame f in bin b.
+ *            Every element is written, empty bins as 0.  The counts of a region add up to its pixel count
+ *   dist     (nframes - 1, R R) uint32: dist[p][r] = sum over b of |hist[p + 1][r][b] - hist[p][r][b]|, at most twice the
+ *            region's pixel count (<= 2^31)
+ * Arithmetic (fixed and all-integer, so that a CPU restatement is bit-equal: tests/cutsutil.py); a // b is floor division:
+ *   region (u, v)     rows [(u H) // R, ((u + 1) H) // R) and columns [(v W) // R, ((v + 1) W) // R): the cell-edge rule of
+ *                     gcv_track_match.  H >= R and W >= R, so no region is empty
+ *   luma of a pixel   Y = (77 R + 150 G + 29 B + 128) >> 8, as in gcv_track_match;  bin = Y >> 2: 64 bins
+ * Refused before anything is launched (gcv_last_error() says why): regions not 1, 2, 4 or 8; nframes, H or W not positive;
+ * H < regions or W < regions; H W > 2^30 (a count is 32 bits); a null pointer.  gcv_hist_diff with nframes == 1 launches
+ * nothing and writes nothing.
+ * gcv_frame_hist reads every pixel once: one workgroup per (frame, region), or, where that leaves the chip idle (few
+ * frames, R = 1 or 2), several per region whose counts are merged by integer atomic adds into the output, which a
+ * hipMemsetAsync on the stream zeroes first — integer adds commute, so the result is the same whatever the order.
+ * gcv_hist_diff is one launch.  Neither call allocates, copies or synchronises anything.
+ * Not done here: fades and dissolves (only a hard cut changes every region at once), and two shots whose regions have the
+ * same luma distribution are not told apart. */
+int gcv_frame_hist(const void* frames_u8_nhwc, int nframes, int H, int W, int regions, uint32_t* hist_u32,
+                   gcv_stream stream);
+int gcv_hist_diff(const uint32_t* hist_u32, int nframes, int regions, uint32_t* dist_u32, gcv_stream stream);
+
 /* pred_vid's reduction (model/pred_func.py:120,125): mean2[c] = mean_r sigmoid(logits[r][c]). */
 int gcv_vote(const float* logits, int rows, float* mean2, gcv_stream stream);
 
