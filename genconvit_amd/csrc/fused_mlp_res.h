@@ -14,8 +14,9 @@
 //     independent MFMAs) are issued around GELU(g), so its own vector instructions also have matrix work to hide under
 //   * rows are 192 B (no room for padding): the 16-byte chunk index is XOR-swizzled inside groups of four by
 //     (row >> 2) & 3, which puts the 16 lanes of a ds_read_b128 group on 16 distinct 16-byte bank groups
-//   * no LDS is left for an epilogue transposition: the (token on lane, 4 channels in registers) accumulator is
-//     stored as 8-byte pieces, 32 rows x 16 B per instruction; L2 merges the 12 pieces of a row before write-back
+//   * no LDS is left for an epilogue transposition: a v_permlane32_swap per dword pairs the two half-waves' 8-byte
+//     halves of the (token on lane, 4 channels in registers) accumulator, which is stored as 16-byte pieces, 32 rows
+//     x 32 B per instruction; L2 merges the 6 pieces of a row before write-back
 #pragma once
 #include "fused_mlp.h"
 
@@ -128,6 +129,10 @@ __global__ void __launch_bounds__(512, 1) fused_mlp_res_kernel(const MlpArgs a) 
     const int64_t mld = (GCV_MLP_ABLATE & 8) ? (int64_t)lr : mc;
 
 
+    // (Peeling the first loop iteration would make this zero the inline constant of the first MFMAs' C operand and save
+    // the 48 v_mov_b32 per tile, bit for bit, as xs_mlp_kernel does; here it costs 8 more VGPRs, so it is not done.
+    // Starting at b2 instead would save the epilogue's adds too, but changes the order of the fp32 sum and with it
+    // the last bit of some outputs.)
     f32x16 acc2[NO];
 #pragma unroll
     for (int o = 0; o < NO; ++o)
@@ -253,11 +258,13 @@ __global__ void __launch_bounds__(512, 1) fused_mlp_res_kernel(const MlpArgs a) 
     mfma2(w2f, hfB);
 
     if (titer == 2) GCV_STAMP(7);
-    // ---- epilogue: (acc2 + b2) * gamma + resid -> 16-bit, 8-byte pieces ----
-    // (pointers through an empty asm: keeps the loop-invariant b2 / gamma LDS reads inside the tile loop, unspilled)
-    const float* sB2t = sB2;
-    const float* sGt = sG;
-    asm volatile("" : "+v"(sB2t), "+v"(sGt));
+    // ---- epilogue: (acc2 + b2) * gamma + resid -> 16-bit, 16-byte pieces ----
+    // (LDS offsets through an empty asm: keeps the loop-invariant b2 / gamma LDS reads inside the tile loop, unspilled;
+    // offsets rather than pointers, which would come back generic and make the reads flat loads)
+    int oB2 = MlpResSmem::kB2, oG = MlpResSmem::kG;
+    asm volatile("" : "+s"(oB2), "+s"(oG));
+    const float* const sB2t = reinterpret_cast<const float*>(smem + oB2);
+    const float* const sGt = reinterpret_cast<const float*>(smem + oG);
     // A row's 16 bytes (o, q) are split over the half-waves (lane lr: channels 8q .. 8q+3, lane lr+32: 8q+4 .. 8q+7).
     // One v_permlane32_swap per dword of a (q, q+1) pair leaves lanes 0-31 with the 16 contiguous bytes of piece q
     // and lanes 32-63 with those of piece q+1: six 16-byte stores per tile instead of twelve 8-byte ones (each store
@@ -315,8 +322,9 @@ __global__ void __launch_bounds__(512, 1) fused_mlp_res_kernel(const MlpArgs a) 
       const int py = rem / wd, px = rem - py * wd;
       const int64_t prow = (int64_t)a.lnp_out0[sg] + ((int64_t)img * (hw / wd / 2) + (py >> 1)) * (wd >> 1) + (px >> 1);
       T* const dst = Op + prow * (4 * C) + ((py & 1) * 2 + (px & 1)) * C;
-      const float* sLw = reinterpret_cast<const float*>(smem + MlpResSmem::kLn);
-      asm volatile("" : "+v"(sLw));
+      int oLn = MlpResSmem::kLn;
+      asm volatile("" : "+s"(oLn));
+      const float* const sLw = reinterpret_cast<const float*>(smem + oLn);
 #pragma unroll
       for (int o = 0; o < NO; ++o)
 #pragma unroll

@@ -179,6 +179,9 @@ __global__ void __launch_bounds__(512, 2) xs_mlp_kernel(const XsMlpArgs a, const
 #pragma unroll
     for (int p = 0; p < KP1; ++p) asm volatile("" : "+v"(xf[p]));
 
+    // GEMM2's accumulators start at zero; the first steady-state pair of steps is peeled (below) so that the zero is the
+    // inline constant of the first MFMAs' C operand instead of C/2 v_mov_b32 per pass (a zero carried into the loop is a
+    // register value).  The sums keep their order: the output is bit for bit what the zero-filled accumulator gave.
     f32x16 acc2[NO];
 #pragma unroll
     for (int o = 0; o < NO; ++o)
@@ -290,10 +293,14 @@ __global__ void __launch_bounds__(512, 2) xs_mlp_kernel(const XsMlpArgs a, const
     step(accA, accB, hfA, hfA, 1, TT{}, TT{}, FF{}, R2{});               // g = 1: GEMM1(1) -> B, h(0) -> hfA
     if (it == 0) XM_STAMP(2);
     // steady state, two steps per iteration: (cur A->hfB | GEMM2 hfA) then (cur B->hfA | GEMM2 hfB)
+    // (g = 2, 3 outside the loop: the first GEMM2 of every accumulator is here, straight-line behind its zero)
+    static_assert(NKC >= 6, "one peeled pair of steps and at least one in the loop");
+    step(accB, accA, hfA, hfB, 2, TT{}, TT{}, TT{}, R1{});               // GEMM1(g) -> A, h(g-1) = GELU(B) -> hfB, GEMM2(g-2) hfA
+    step(accA, accB, hfB, hfA, 3, TT{}, TT{}, TT{}, R2{});               // GEMM1(g+1) -> B, h(g) = GELU(A) -> hfA, GEMM2(g-1) hfB
 #pragma unroll 1
-    for (int g = 2; g < NKC; g += 2) {
-      step(accB, accA, hfA, hfB, g, TT{}, TT{}, TT{}, R1{});             // GEMM1(g) -> A, h(g-1) = GELU(B) -> hfB, GEMM2(g-2) hfA
-      step(accA, accB, hfB, hfA, g + 1, TT{}, TT{}, TT{}, R2{});         // GEMM1(g+1) -> B, h(g) = GELU(A) -> hfA, GEMM2(g-1) hfB
+    for (int g = 4; g < NKC; g += 2) {
+      step(accB, accA, hfA, hfB, g, TT{}, TT{}, TT{}, R1{});
+      step(accA, accB, hfB, hfA, g + 1, TT{}, TT{}, TT{}, R2{});
     }
     if (it == 0) XM_STAMP(3);
     // residual rows into the (now dead) x registers: 16-byte pieces, lanes 0-31 channels 16p .. 16p+7, lanes 32-63 the
@@ -313,9 +320,10 @@ __global__ void __launch_bounds__(512, 2) xs_mlp_kernel(const XsMlpArgs a, const
     // ---- epilogue: (acc2 + b2) * gamma + resid -> 16-bit, 16-byte pieces (v_permlane32_swap converts between a row's
     // 16-byte piece and the accumulator's (8q + 4lh) halves, it is its own inverse)
     {
-      const float* sB2 = sB2_;
-      const float* sG = sG_;
-      asm volatile("" : "+v"(sB2), "+v"(sG));              // keeps the LDS reads inside the pass loop, unspilled
+      // b2 | gamma behind b1, from the lane's live b1 pointer (+ 4 lh).  (A pointer laundered through an empty asm comes
+      // back generic and turns these LDS reads into flat loads.)
+      const float* const sB2 = sb1 + 4 * C;
+      const float* const sG = sb1 + 5 * C;
       if constexpr (LNP) {
         // out = LayerNorm2d(resid + gamma * (acc2 + b2)) at the patch position of token m (see fused_mlp_res.h)
         float s1 = 0.0f, s2 = 0.0f;
@@ -330,7 +338,7 @@ __global__ void __launch_bounds__(512, 2) xs_mlp_kernel(const XsMlpArgs a, const
 #pragma unroll
             for (int d = 0; d < 2; ++d) {
               const int q = 2 * pr + d;
-              const int n = 32 * o + 8 * q + 4 * lh;
+              const int n = 32 * o + 8 * q;                 // (+ 4 lh: in the pointer)
               const f32x4 bv = *(const f32x4*)(sB2 + n);
               const f32x4 gv = *(const f32x4*)(sG + n);
 #pragma unroll
@@ -367,8 +375,7 @@ __global__ void __launch_bounds__(512, 2) xs_mlp_kernel(const XsMlpArgs a, const
         const int py = rem / wd, px = rem - py * wd;
         const int64_t prow = (int64_t)a.lnp_out0[sg] + ((int64_t)img * (hw / wd / 2) + (py >> 1)) * (wd >> 1) + (px >> 1);
         T* const dst = Op + prow * (4 * C) + ((py & 1) * 2 + (px & 1)) * C;
-        const float* sLw = reinterpret_cast<const float*>(smem + CF::kLn);
-        asm volatile("" : "+v"(sLw));
+        const float* const sLw = sb1 + 6 * C;              // LayerNorm weight | bias behind gamma
 #pragma unroll
         for (int o = 0; o < NO; ++o)
 #pragma unroll
@@ -377,7 +384,7 @@ __global__ void __launch_bounds__(512, 2) xs_mlp_kernel(const XsMlpArgs a, const
 #pragma unroll
             for (int d = 0; d < 2; ++d) {
               const int q = 2 * pr + d;
-              const int n = 32 * o + 8 * q + 4 * lh;
+              const int n = 32 * o + 8 * q;                 // (+ 4 lh: in the pointer)
               const f32x4 wv = *(const f32x4*)(sLw + n);
               const f32x4 cv = *(const f32x4*)(sLw + C + n);
               t4 o4;
@@ -403,7 +410,7 @@ __global__ void __launch_bounds__(512, 2) xs_mlp_kernel(const XsMlpArgs a, const
 #pragma unroll
           for (int d = 0; d < 2; ++d) {
             const int q = 2 * pr + d;
-            const int n = 32 * o + 8 * q + 4 * lh;
+            const int n = 32 * o + 8 * q;                 // (+ 4 lh: in the pointer)
             const f32x4 bv = *(const f32x4*)(sB2 + n);
             const f32x4 gv = *(const f32x4*)(sG + n);
             t4 o4;
