@@ -1,0 +1,620 @@
+"""One builder per kernel family whose output feeds the verdict: the CPU inputs of a case exactly as the GPU test uploads
+them, the float64 reference, the comparator, an honest float32 model, and the family's planted defects.  The GPU tests
+(tests/test_kernels_gpu.py, tests/test_mlp_bias_init_gpu.py) and the CPU audit (tests/test_kernel_sensitivity_cpu.py) share
+them, so what the audit proves about the comparator and the inputs holds for what the GPU tests assert.  Nothing here
+needs a GPU.
+
+A builder returns a Case:
+  inputs            name -> CPU tensor (fp32 holding values of the storage dtype where the kernel reads that dtype)
+  ref(inputs)       the plain reference in float64 on those inputs.  Where the kernel rounds the hidden activation to the
+                    storage dtype (the fused MLPs), the reference rounds it too.
+  check(got, want, inputs) -> (ok, message)
+  defects           name -> function(inputs) -> float64 result of a reference with that defect planted
+  model(inputs)     an honest float32 implementation (torch matmul / conv in float32, the 16-bit GELU through
+                    numutil.gelu_h16_ref), rounded to the storage dtype: what a correct kernel may legitimately return
+
+Comparator.  16-bit storage, per element: |got - want| <= 0.5 ulp_T(want) + e, e one scalar per (family, dtype) in E
+below: fp32 accumulation order, hidden values that land on the other side of a rounding step, the packed GELU polynomial.
+Its largest per-element bound must stay <= kutil.tol(dtype, scale) of the test it replaces (asserted on every call), so
+nothing gets weaker.  fp32 storage, and the fp32 partial sums of split-K, keep their flat bound.
+
+Inputs.  Every vector term (bias, b1, b2, gamma, LayerNorm weight / bias, the 49 depthwise taps) is drawn from +-[lo, hi],
+never U(-s, s): an element that is dropped, rotated in from its neighbour or swapped moves the output by at least lo times
+its factor.  The shortcut of the residual families is |res| <= 0.25 so that the output's rounding step stays below the
+branch's smallest term.
+
+Defects that do not apply to a family (every other entry of the catalogue applies):
+  split-K          no bias, gamma, activation or shortcut: contraction and row defects only (plus a K index at a split edge)
+  GEMM bias/act    no gamma, no shortcut, no branch to scale; ReLU-for-LeakyReLU only where the activation is LeakyReLU;
+                   activation-omitted only where there is one
+  POOL4 / CONVT    no gamma, no shortcut; CONVT has no pool, POOL4's activation is ReLU
+  dw7x7 + LN       no gamma, no shortcut, no activation; its contraction is the 49 taps (one tap zeroed on one channel)
+  fused MLP        no pool, no taps; LN-patchify row defects exist only behind gcv_k_fused_mlp_lnp, and the
+                   previous-segment-geometry defect needs a second segment
+  M = 1            no row before the last one: the row defects are left out at a single row
+Where a defect names "one" element, it is the vector's last element, the pair (2c, 2c + 1) at c = n // 4, the centre tap of
+the last channel, hidden unit 4C - 31, and for an omitted activation the column with the lowest bias (behind the 2x2 pool
+an omitted ReLU shows only where all four pixels of a window are negative).
+The erf-versus-tanh GELU and the LayerNorm eps belong to tests/test_numerics_*.
+"""
+import math
+
+import torch
+import torch.nn.functional as F
+
+from tests import kutil, numutil
+from tests.kutil import rnd
+
+F16, BF16, F32 = torch.float16, torch.bfloat16, torch.float32
+NAMES = {F16: "f16", BF16: "bf16", F32: "f32"}
+
+# e per (family, dtype): 3 x the largest excess |got - want64| - 0.5 ulp_T(want) measured on the MI355X over all of the family's
+# cases in the GPU tests (the measured value in the comment).  An fp32 accumulator rounded once to T exceeds half a step by
+# at most its own fp32 error, hence the 1e-7s measured for the families without a hidden rounding or a polynomial.  Those
+# get the floor FP32_ACC instead of 3 x 1e-7: the honest float32 model of tests/test_kernel_sensitivity_cpu.py sums in the
+# host BLAS's order, reaches 3e-7 there already, and must pass on any host; sixteen fp32 roundings at 1.0 is still a
+# thousand times below the smallest planted defect.  "gemm_bias_gelu" carries GeluH16's polynomial, the MLP families that
+# and the hidden values which land on the other side of a rounding step (the LN-patchify epilogue scales both by
+# lw / std of a row, about 4 here).
+FP32_ACC = 16 * 2.0 ** -24             # 9.54e-07
+E = {
+    ("mlp", BF16): 2.4e-3,             # 8.31e-04
+    ("mlp", F16): 1.3e-3,              # 4.62e-04
+    ("mlp_lnp", BF16): 1.3e-2,         # 4.41e-03
+    ("mlp_lnp", F16): 6.6e-3,          # 2.23e-03
+    ("gemm_bias_gelu", BF16): 1.7e-3,  # 5.96e-04
+    ("gemm_bias_gelu", F16): 1.7e-3,   # 5.89e-04
+    ("dw_ln", BF16): 2.4e-6,           # 8.33e-07
+    ("dw_ln", F16): 2.7e-6,            # 9.16e-07
+    ("gemm_resid", BF16): FP32_ACC,    # 2.33e-07
+    ("gemm_resid", F16): 1.0e-6,       # 3.38e-07
+    ("gemm_bias_act", BF16): FP32_ACC,   # 1.41e-07
+    ("gemm_bias_act", F16): FP32_ACC,    # 1.63e-07
+    ("conv_s2", BF16): FP32_ACC,       # 2.17e-08
+    ("conv_s2", F16): FP32_ACC,        # 7.64e-08
+    ("pool4", BF16): FP32_ACC,         # 3.16e-08
+    ("pool4", F16): FP32_ACC,          # 1.31e-07
+    ("convt", BF16): FP32_ACC,         # 2.61e-08
+    ("convt", F16): FP32_ACC,          # 7.90e-08
+}
+SPLITK_BOUND = {F32: 2e-5, BF16: 1e-4, F16: 1e-4}      # fp32 partial sums in every storage dtype: the flat bound as before
+
+_CHUNK = 1 << 23
+
+
+def q(t, dtype):
+    """round a CPU tensor through the storage dtype; fp32 out"""
+    return t.to(dtype).float()
+
+
+def round_to(t64, dtype):
+    """a float64 result as the storage dtype would hold it; float64 out.  (torch converts through float32: next to a tie of
+    T the result can be the other neighbour, 2^-25 |v| further away than the nearest — a quarter of E's floor at |v| = 8.)"""
+    return t64.to(dtype).double()
+
+
+def signed(shape, seed, lo, hi):
+    """uniform in +-[lo, hi].  In a vector, element 2c + 1 takes the sign opposite to element 2c's, so the two values of a
+    packed pair differ by at least 2 lo: swapped, each moves by that much."""
+    u = rnd(shape, seed)                                   # U(-1, 1): the sign, and |u| for the magnitude
+    sign = torch.sign(u + (u == 0).float())
+    if len(shape) == 1:
+        sign[1::2] = -sign[0:shape[0] - shape[0] % 2:2]
+    return sign * (lo + (hi - lo) * u.abs())
+
+
+def vec_variants(v):
+    """the three vector defects: last element zeroed, rotated by one, elements 2c and 2c + 1 swapped (c = n // 4)"""
+    n = v.numel()
+    z, s = v.clone(), v.clone()
+    z[n - 1] = 0
+    c = n // 4
+    s[2 * c], s[2 * c + 1] = v[2 * c + 1], v[2 * c]
+    return {"one_zeroed": z, "rotated": torch.roll(v, 1), "pair_swapped": s}
+
+
+def k_indices(K):
+    """first, last, and one index next to a 32-element K-tile edge"""
+    return {"k_first": 0, "k_last": K - 1, "k_tile_edge": 32 if K > 33 else min(31, K - 1)}
+
+
+def _with(inp, **kw):
+    d = dict(inp)
+    d.update(kw)
+    return d
+
+
+class Case:
+    def __init__(self, family, dtype, inputs, ref, model, defects, scale, flat=None, what=""):
+        self.family, self.dtype, self.inputs, self.ref, self.model, self.defects = family, dtype, inputs, ref, model, defects
+        self.what = f"{what or family} {NAMES[dtype]}"
+        self.tol_before = kutil.tol(dtype, scale) if flat is None else flat      # the bound of the test this replaces
+        self.e = E[(family, dtype)] if (flat is None and dtype != F32) else None
+        self._want = None
+
+    def want(self):
+        """ref(inputs), computed once"""
+        if self._want is None:
+            self._want = self.ref(self.inputs)
+        return self._want
+
+    def measure(self, got, want):
+        """largest |got - want|, largest err / bound with its flat index, largest excess err - 0.5 ulp_T(want) (the
+        quantity E is set from; for a flat bound the largest error itself)"""
+        g, w = got.detach().cpu().reshape(-1), want.reshape(-1)
+        assert g.numel() == w.numel(), f"{self.what}: {tuple(got.shape)} against {tuple(want.shape)}"
+        out = {"err": 0.0, "ratio": 0.0, "at": 0, "excess": -math.inf, "bound": 0.0}
+        for s in range(0, g.numel(), _CHUNK):
+            wd = w[s:s + _CHUNK].double()
+            err = (g[s:s + _CHUNK].double() - wd).abs()
+            err = torch.where(torch.isfinite(err), err, torch.full_like(err, math.inf))
+            if self.e is None:
+                bound, ex = torch.full_like(err, self.tol_before), err.max().item()
+            else:
+                half = 0.5 * numutil.ulp(wd, self.dtype)
+                bound, ex = half + self.e, (err - half).max().item()
+                assert bound.max().item() <= self.tol_before, \
+                    f"{self.what}: per-element bound {bound.max().item():.3e} above the flat bound {self.tol_before:.3e}"
+            ratio = err / bound
+            i = int(ratio.argmax())
+            if ratio[i].item() >= out["ratio"]:
+                out.update(ratio=ratio[i].item(), at=s + i, bound=bound[i].item())
+            out["err"], out["excess"] = max(out["err"], err.max().item()), max(out["excess"], ex)
+        return out
+
+    def check(self, got, want, inputs=None):
+        m = self.measure(got, want)
+        ok = m["ratio"] <= 1.0
+        idx = tuple(int(i) for i in torch.unravel_index(torch.tensor(m["at"]), want.shape)) if want.dim() else ()
+        msg = (f"{self.what}: max |diff| {m['err']:.3e}, worst err/bound {m['ratio']:.2f} at {idx} (bound there "
+               f"{m['bound']:.3e}), excess {m['excess']:.3e}"
+               + (f" (e = {self.e:.1e})" if self.e is not None else f" (flat bound {self.tol_before:.1e})"))
+        return ok, msg
+
+    def assert_close(self, got):
+        ok, msg = self.check(got, self.want(), self.inputs)
+        print(msg)
+        assert ok, msg
+
+    def to_storage(self, t64):
+        """a float64 result as the kernel's output buffer would hold it (fp32 where the bound is flat)"""
+        return t64.float() if self.e is None else round_to(t64, self.dtype)
+
+
+def _act64(v, act, noact_col=None, relu_for_leaky=False):
+    """activation of the GEMM epilogues on (..., N) float64: 0 none, 1 ReLU, 2 exact GELU, 3 LeakyReLU(0.01)"""
+    if act == 0:
+        return v
+    if act == 1 or (act == 3 and relu_for_leaky):
+        y = v.clamp(min=0)
+    elif act == 2:
+        y = numutil.gelu_ref(v)
+    else:
+        y = torch.where(v >= 0, v, 0.01 * v)
+    if noact_col is not None:
+        y = y.clone()
+        y[..., noact_col] = v[..., noact_col]
+    return y
+
+
+def _act32(v, act, dtype):
+    """the same in float32 as a kernel computes it: the 16-bit GELU sites behind act4n end in the fp32 finish"""
+    if act == 0:
+        return v
+    if act == 1:
+        return v.clamp(min=0)
+    if act == 3:
+        return torch.where(v >= 0, v, 0.01 * v)
+    if dtype == F32:
+        return F.gelu(v)
+    return numutil.gelu_h16_ref(v, dtype, packed_finish=False).float()
+
+
+def _d(inp):
+    return {k: v.double() for k, v in inp.items()}
+
+
+# ----------------------------------------------------------------------------- GEMM epilogues on a plain A
+def gemm(epi, M, N, K, dtype, act=0, k_per_split=0):
+    """epi: "bias_act", "resid" (X + gamma (A W^T + bias), in place) or "splitk" (fp32 partial sums, summed by the test)"""
+    inp = {"A": q(rnd((M, K), 1), dtype), "W": q(rnd((N, K), 2, 1 / math.sqrt(K)), dtype)}
+    if epi != "splitk":
+        inp["bias"] = signed((N,), 3, 0.05, 0.2)
+    if epi == "resid":
+        inp["gamma"], inp["X"] = signed((N,), 4, 0.25, 0.5), q(rnd((M, N), 5, 0.25), dtype)
+
+    def ref(i, branch=1.0, gamma_one=False, noact_col=None, relu_for_leaky=False, last_from_prev=False, resid_shift=False):
+        i = _d(i)
+        pre = i["A"] @ i["W"].t()
+        if epi == "splitk":
+            y = pre
+        else:
+            y = _act64(pre + i["bias"], act, noact_col, relu_for_leaky)
+        if last_from_prev:
+            y = y.clone()
+            y[M - 1] = y[M - 2]
+        if epi == "resid":
+            X = i["X"]
+            if resid_shift:
+                X = X.clone()
+                X[M - 1] = X[M - 2]
+            y = X + (1.0 if gamma_one else i["gamma"]) * y * branch
+        return y
+
+    def model(i):
+        pre = i["A"].float() @ i["W"].float().t()
+        if epi == "splitk":
+            return pre.double()
+        y = _act32(pre + i["bias"], act, dtype)
+        if epi == "resid":
+            y = i["X"] + i["gamma"] * y
+        return y.double() if dtype == F32 else round_to(y.double(), dtype)
+
+    def zero_k(k):
+        def f(i):
+            W = i["W"].clone()
+            W[:, k] = 0
+            return ref(_with(i, W=W))
+        return f
+
+    ks = k_indices(K)
+    if epi == "splitk":
+        ks["k_split_edge"] = k_per_split
+    defects = {name: zero_k(k) for name, k in ks.items()}
+    for vec in ("bias", "gamma"):
+        if vec in inp:
+            for name, v in vec_variants(inp[vec]).items():
+                defects[f"{vec}_{name}"] = (lambda i, vec=vec, v=v: ref(_with(i, **{vec: v})))
+    if epi == "resid":
+        defects["branch_15_16"] = lambda i: ref(i, branch=15 / 16)
+        defects["gamma_as_one"] = lambda i: ref(i, gamma_one=True)
+        if M > 1:
+            defects["resid_from_row_before"] = lambda i: ref(i, resid_shift=True)
+    if M > 1:
+        defects["last_row_from_row_before"] = lambda i: ref(i, last_from_prev=True)
+    if epi == "bias_act" and act != 0:
+        defects["act_omitted_on_one_column"] = lambda i: ref(i, noact_col=int(inp["bias"].argmin()))
+    if epi == "bias_act" and act == 3:
+        defects["relu_for_leaky"] = lambda i: ref(i, relu_for_leaky=True)
+    family = {"bias_act": "gemm_bias_gelu" if act == 2 else "gemm_bias_act", "resid": "gemm_resid", "splitk": "splitk"}[epi]
+    return Case(family, dtype, inp, ref, model, defects, 2.0, flat=SPLITK_BOUND[dtype] if epi == "splitk" else None,
+                what=f"gemm {epi} {M}x{N}x{K} act={act}")
+
+
+# ----------------------------------------------------------------------------- conv as GEMM
+def _conv_inputs(n, H, cin, cout, dtype):
+    return {"x": q(rnd((n, cin, H, H), 1), dtype),                                     # NCHW here; the test uploads NHWC
+            "w": q(rnd((cout, cin, 3, 3), 2, 1 / math.sqrt(9 * cin)), dtype),
+            "b": signed((cout,), 3, 0.05, 0.2)}
+
+
+def _conv3_defects(ref, inp, cin, cout):
+    def zero_w(ci, ky, kx):
+        def f(i):
+            w = i["w"].clone()
+            w[:, ci, ky, kx] = 0
+            return ref(_with(i, w=w))
+        return f
+    e = 32                                                  # K index (ky, kx, ci) next to the first K-tile edge
+    defects = {"k_first": zero_w(0, 0, 0), "tap22_of_last_cin": zero_w(cin - 1, 2, 2),
+               "k_tile_edge": zero_w(e % cin, (e // cin) // 3, (e // cin) % 3)}
+    for name, v in vec_variants(inp["b"]).items():
+        defects[f"bias_{name}"] = (lambda i, v=v: ref(_with(i, b=v)))
+    defects["act_omitted_on_one_column"] = lambda i: ref(i, noact_col=int(inp["b"].argmin()))
+    defects["last_row_from_row_before"] = lambda i: ref(i, last_from_prev=True)
+    return defects
+
+
+def _last_from_prev(y):
+    """(n, h, w, c): the last pixel takes the result of the pixel before it"""
+    y = y.clone()
+    flat = y.view(-1, y.shape[-1])
+    flat[-1] = flat[-2]
+    return y
+
+
+def conv3x3_s2(n, H, cin, cout, dtype):
+    """conv3x3 stride 2 pad 1 + bias + LeakyReLU(0.01) (A_IM2COL3_S2, EPI_BIAS_ACT); NHWC out"""
+    inp = _conv_inputs(n, H, cin, cout, dtype)
+
+    def ref(i, noact_col=None, relu_for_leaky=False, last_from_prev=False):
+        i = _d(i)
+        y = F.conv2d(i["x"], i["w"], i["b"], stride=2, padding=1).permute(0, 2, 3, 1)
+        y = _act64(y, 3, noact_col, relu_for_leaky).contiguous()
+        return _last_from_prev(y) if last_from_prev else y
+
+    def model(i):
+        y = F.conv2d(i["x"], i["w"], i["b"], stride=2, padding=1).permute(0, 2, 3, 1)
+        y = torch.where(y >= 0, y, 0.01 * y).double()
+        return y if dtype == F32 else round_to(y, dtype)
+
+    defects = _conv3_defects(ref, inp, cin, cout)
+    defects["relu_for_leaky"] = lambda i: ref(i, relu_for_leaky=True)
+    return Case("conv_s2", dtype, inp, ref, model, defects, 2.0, what=f"conv3 s2 n={n} H={H} {cin}->{cout}")
+
+
+def conv3x3_pool(n, H, cin, cout, dtype):
+    """conv3x3 stride 1 pad 1 + bias + ReLU + maxpool 2 (A_IM2COL3_POOL, EPI_POOL4); NHWC out"""
+    inp = _conv_inputs(n, H, cin, cout, dtype)
+
+    def ref(i, noact_col=None, last_from_prev=False, three_of_four=False):
+        i = _d(i)
+        y = F.conv2d(i["x"], i["w"], i["b"], padding=1).permute(0, 2, 3, 1)
+        y = _act64(y, 1, noact_col)
+        win = y.reshape(n, H // 2, 2, H // 2, 2, cout).permute(0, 1, 3, 5, 2, 4).reshape(n, H // 2, H // 2, cout, 4)
+        y = (win[..., :3] if three_of_four else win).max(-1).values.contiguous()
+        return _last_from_prev(y) if last_from_prev else y
+
+    def model(i):
+        y = F.max_pool2d(F.relu(F.conv2d(i["x"], i["w"], i["b"], padding=1)), 2).permute(0, 2, 3, 1).double()
+        return y if dtype == F32 else round_to(y, dtype)
+
+    defects = _conv3_defects(ref, inp, cin, cout)
+    defects["pool_over_three_of_four"] = lambda i: ref(i, three_of_four=True)
+    return Case("pool4", dtype, inp, ref, model, defects, 2.0, what=f"conv3 pool n={n} H={H} {cin}->{cout}")
+
+
+def conv_transpose2x2(n, H, cin, cout, act, dtype):
+    """ConvTranspose2d(k = 2, s = 2) + bias + activation (EPI_CONVT); NHWC out"""
+    inp = {"x": q(rnd((n, cin, H, H), 1), dtype), "w": q(rnd((cin, cout, 2, 2), 2, 1 / math.sqrt(cin)), dtype),
+           "b": signed((cout,), 3, 0.05, 0.2)}
+
+    def ref(i, noact_col=None, relu_for_leaky=False):
+        i = _d(i)
+        y = F.conv_transpose2d(i["x"], i["w"], i["b"], stride=2).permute(0, 2, 3, 1)
+        return _act64(y, act, noact_col, relu_for_leaky).contiguous()
+
+    def model(i):
+        y = _act32(F.conv_transpose2d(i["x"], i["w"], i["b"], stride=2).permute(0, 2, 3, 1), act, dtype).double()
+        return y if dtype == F32 else round_to(y, dtype)
+
+    def zero_k(k):
+        def f(i):
+            w = i["w"].clone()
+            w[k] = 0
+            return ref(_with(i, w=w))
+        return f
+
+    def last_from_prev(i):
+        x = i["x"].clone()                                  # the last input pixel's row of A is the one before it
+        x[n - 1, :, H - 1, H - 1] = x[n - 1, :, H - 1, H - 2]
+        return ref(_with(i, x=x))
+
+    defects = {name: zero_k(k) for name, k in k_indices(cin).items()}
+    for name, v in vec_variants(inp["b"]).items():
+        defects[f"bias_{name}"] = (lambda i, v=v: ref(_with(i, b=v)))
+    defects["act_omitted_on_one_column"] = lambda i: ref(i, noact_col=int(inp["b"].argmin()))
+    if act == 3:
+        defects["relu_for_leaky"] = lambda i: ref(i, relu_for_leaky=True)
+    defects["quadrants_dy_dx_swapped"] = lambda i: ref(_with(i, w=i["w"].transpose(2, 3)))
+    defects["last_row_from_row_before"] = last_from_prev
+    return Case("convt", dtype, inp, ref, model, defects, 2.0, what=f"convT n={n} H={H} {cin}->{cout} act={act}")
+
+
+# ----------------------------------------------------------------------------- depthwise 7x7 + LayerNorm
+DW_KINDS = ("tile", "tiny", "tiny_pair", "roll", "mfma", "pair")      # gcv_dw_plan's kind codes (include/genconvit_hip.h)
+
+
+def dw_kind(dtype, n, H, W, C, aligned=True):
+    """the kernel gcv_k_dwconv7_ln runs for this launch, asked of the library's own planner (host code, no GPU)"""
+    import ctypes
+    from genconvit_amd import _lib
+    out = (ctypes.c_int * 5)()
+    _lib.check(_lib.load().gcv_dw_plan(_lib.dtype_code(dtype), n, H, W, C, int(aligned), out), "gcv_dw_plan")
+    return DW_KINDS[out[0]]
+
+
+def dwconv7_ln(C, H, W, n, dtype, aligned=True):
+    """depthwise 7x7 pad 3 + bias + LayerNorm(C, eps 1e-6); x NCHW here (the test uploads NHWC), NHWC out.  The taps are
+    uploaded in fp32.  The matrix-pipe kernel (csrc/dwconv_mfma.h, 16-bit storage) rounds them to the storage dtype, being
+    an MFMA operand; for a launch that gcv_dw_plan sends there, reference, model and defects round them too."""
+    inp = {"x": q(rnd((n, C, H, W), 1, 2.0), dtype), "w": signed((C, 1, 7, 7), 2, 0.05, 0.25),
+           "b": signed((C,), 3, 0.1, 0.3), "lw": rnd((C,), 4, 0.5) + 1.0, "lb": signed((C,), 5, 0.1, 0.3)}
+    taps_in_T = dw_kind(dtype, n, H, W, C, aligned) == "mfma"
+
+    cache = {}
+
+    def conv(i, clamp_right=False):
+        """the depthwise conv + bias in float64, NHWC; the clean inputs' result is kept (the matrix-pipe cases are large)"""
+        keep = not clamp_right and all(i[k] is inp[k] for k in ("x", "w", "b"))
+        if keep and "y" in cache:
+            return cache["y"]
+        d = _d({k: (q(i[k], dtype) if (k == "w" and taps_in_T) else i[k]) for k in ("x", "w", "b")})
+        if clamp_right:
+            xp = F.pad(d["x"], (3, 3, 3, 3))
+            xp[:, :, 3:H + 3, W + 3:] = d["x"][:, :, :, W - 1:]      # the last column again where zeros belong
+            y = F.conv2d(xp, d["w"], d["b"], groups=C)
+        else:
+            y = F.conv2d(d["x"], d["w"], d["b"], padding=3, groups=C)
+        y = y.permute(0, 2, 3, 1).contiguous()
+        if keep:
+            cache["y"] = y
+        return y
+
+    def ref(i, clamp_right=False, last_from_prev=False, y=None):
+        y = conv(i, clamp_right) if y is None else y
+        if last_from_prev:
+            y = _last_from_prev(y)
+        return numutil.ln_ref(y, i["lw"].double(), i["lb"].double(), 1e-6).contiguous()
+
+    def model(i):
+        y = F.conv2d(i["x"], q(i["w"], dtype) if taps_in_T else i["w"], i["b"], padding=3, groups=C).permute(0, 2, 3, 1)
+        y = F.layer_norm(y, (C,), i["lw"], i["lb"], 1e-6).double()
+        return y if dtype == F32 else round_to(y, dtype)
+
+    def tap_zeroed(i):
+        y = conv(i).clone()                                 # the centre tap of the last channel: on data at every map size
+        wc = (q(i["w"], dtype) if taps_in_T else i["w"]).double()[C - 1, 0, 3, 3]
+        y[..., C - 1] -= wc * i["x"].double()[:, C - 1]
+        return ref(i, y=y)
+
+    def bias_zeroed(i):
+        y = conv(i).clone()
+        y[..., C - 1] -= i["b"].double()[C - 1]
+        return ref(i, y=y)
+
+    defects = {"one_tap_zeroed_on_one_channel": tap_zeroed, "dw_bias_zeroed_on_one_channel": bias_zeroed}
+    if W > 1:
+        defects["right_edge_clamped"] = lambda i: ref(i, clamp_right=True)
+    for vec in ("lw", "lb"):
+        for name, v in vec_variants(inp[vec]).items():
+            defects[f"{vec}_{name}"] = (lambda i, vec=vec, v=v: ref(_with(i, **{vec: v})))
+    if n * H * W > 1:
+        defects["last_row_from_row_before"] = lambda i: ref(i, last_from_prev=True)
+    return Case("dw_ln", dtype, inp, ref, model, defects, 3.0, what=f"dwconv_ln C={C} {H}x{W} n={n}")
+
+
+# ----------------------------------------------------------------------------- fused ConvNeXt MLP
+def xs_pw1_range(C, M):
+    """width of the hidden ranges the C = 384 pw1 kernel's workgroups own at M tokens (csrc/mlp_pair_impl.h,
+    xs_pw1_pick_split: 256-token tiles, whole pairs of 32-wide chunks per workgroup, at most 24 ranges)"""
+    ntile, nkc = -(-M // 256), 4 * C // 32
+    best, best_cost = 1, None
+    for ns in range(1, 25):
+        if nkc % ns or (nkc // ns) % 2:
+            continue
+        cost = ((ntile * ns + 255) // 256) * (nkc // ns + 3)
+        if best_cost is None or cost < best_cost:
+            best, best_cost = ns, cost
+    return 32 * (nkc // best)
+
+
+def lnp_index(segs):
+    """token index of each (patch row, quadrant) behind the LN-patchify epilogue: (M / 4, 4), quadrant = 2 dy + dx"""
+    rows, t = [], 0
+    for n, H, W in segs:
+        img, py, px = torch.meshgrid(torch.arange(n), torch.arange(H // 2), torch.arange(W // 2), indexing="ij")
+        base = t + img * (H * W) + 2 * py * W + 2 * px
+        rows.append(torch.stack([base, base + 1, base + W, base + W + 1], -1).reshape(-1, 4))
+        t += n * H * W
+    return torch.cat(rows)
+
+
+def fused_mlp(C, M, dtype, segs=None, b2_range=(0.25, 0.5)):
+    """fc1 -> exact GELU -> (rounded to T) -> fc2 -> * gamma -> + shortcut (gcv_k_fused_mlp); at C = 384 the kernel pair's fc2
+    weight is T(gamma * W2), and the reference rounds that product as the packer does.  With `segs` ((images, H, W)
+    per segment, M their token count) the stage boundary's LayerNorm2d(eps 1e-6) and 2x2 space-to-depth follow
+    (gcv_k_fused_mlp_lnp): (M / 4, 4 C) out.  The reference keeps pre-activation, hidden and fc2 product of the clean inputs
+    and derives each defect from them by the rank-one (or 32-wide) update that the defect is, so that the 70 000-token cases
+    stay affordable; a defect in front of the GELU repeats the GELU and fc2."""
+    assert dtype in (F16, BF16)
+    inp = {"x": q(rnd((M, C), 1, 1.5), dtype),
+           "w1": q(rnd((4 * C, C), 2, 1 / math.sqrt(C)), dtype),
+           "w2": q(rnd((C, 4 * C), 3, 1 / math.sqrt(4 * C)), dtype),
+           "b1": signed((4 * C,), 4, 0.75, 1.5), "b2": signed((C,), 5, *b2_range), "gamma": signed((C,), 6, 0.25, 0.5),
+           "res": q(rnd((M, C), 7, 0.25), dtype)}
+    if segs is not None:
+        assert M == sum(n * h * w for n, h, w in segs)
+        inp["lw"], inp["lb"] = rnd((C,), 8, 0.5) + 1.0, signed((C,), 9, 0.1, 0.3)
+        index = lnp_index(segs)
+    cache = {}
+    fold = C == 384      # the kernel pair multiplies by T(gamma * W2), rounded once when the weights are packed (mlp_pair.h)
+
+    def hidden(pre):
+        return numutil.gelu_ref(pre).to(dtype).double()
+
+    def w2g(i, gamma_one=False):
+        """what GEMM2 multiplies the hidden by, layer scale included; (C, 4C) float64"""
+        if gamma_one:
+            return i["w2"].double()
+        if fold:
+            return q(i["gamma"][:, None] * i["w2"], dtype).double()
+        return i["gamma"].double()[:, None] * i["w2"].double()
+
+    def stages(i):
+        """pre-activation, hidden, and gamma (W2 . h) of the case's own inputs"""
+        if "pre" not in cache:
+            d = _d(i)
+            cache["pre"] = d["x"] @ d["w1"].t() + d["b1"]
+            cache["h"] = hidden(cache["pre"])
+            cache["zg"] = cache["h"] @ w2g(i).t()
+        return cache["pre"], cache["h"], cache["zg"]
+
+    def tail(i, zg, branch=1.0, gamma_one=False, last_from_prev=False, resid_shift=False, idx=None):
+        d = _d({k: v for k, v in i.items() if k in ("b2", "gamma", "res", "lw", "lb")})
+        br = zg + (1.0 if gamma_one else d["gamma"]) * d["b2"]
+        res = d["res"]
+        if last_from_prev:
+            br = br.clone()
+            br[M - 1] = br[M - 2]
+        if resid_shift:
+            res = res.clone()
+            res[M - 1] = res[M - 2]
+        y = res + br * branch
+        if segs is None:
+            return y
+        yn = numutil.ln_ref(y, d["lw"], d["lb"], 1e-6)      # the residual stream stays fp32 in registers: no rounding of y
+        return yn[index if idx is None else idx].reshape(-1, 4 * C)
+
+    def ref(i, **kw):
+        if i is inp:
+            return tail(i, stages(i)[2], **kw)
+        d = _d(i)                                           # other inputs than the case's own: from scratch
+        return tail(i, hidden(d["x"] @ d["w1"].t() + d["b1"]) @ w2g(i).t(), **kw)
+
+    def model(i):
+        pre = i["x"] @ i["w1"].t() + i["b1"]
+        packed = not (C == 96 and M < 65536)                # fused_mlp_kernel<T, 96, 4> ends in the fp32 finish (numutil)
+        h = numutil.gelu_h16_ref(pre, dtype, packed_finish=packed).float()
+        if fold:
+            y = i["res"] + (h @ q(i["gamma"][:, None] * i["w2"], dtype).t() + i["gamma"] * i["b2"])
+        else:
+            y = i["res"] + i["gamma"] * (h @ i["w2"].t() + i["b2"])
+        if segs is not None:
+            y = F.layer_norm(y, (C,), i["lw"], i["lb"], 1e-6)[index].reshape(-1, 4 * C)
+        return round_to(y.double(), dtype)
+
+    def fc1_k(k):
+        def f(i):
+            pre, _, _ = stages(i)
+            d = _d(i)
+            return tail(i, hidden(pre - torch.outer(d["x"][:, k], d["w1"][:, k])) @ w2g(i).t())
+        return f
+
+    def b1_as(v):
+        def f(i):
+            pre, _, _ = stages(i)
+            return tail(i, hidden(pre + (v.double() - i["b1"].double())) @ w2g(i).t())
+        return f
+
+    def hidden_dropped(j0, j1):
+        def f(i):
+            _, h, zg = stages(i)
+            return tail(i, zg - h[:, j0:j1] @ w2g(i)[:, j0:j1].t())
+        return f
+
+    def gamma_as(v):
+        def f(i):
+            i2 = _with(i, gamma=v)
+            return tail(i2, stages(i)[1] @ w2g(i2).t())
+        return f
+
+    width = xs_pw1_range(C, M) if C == 384 else 32
+    defects = {f"fc1_{name}": fc1_k(k) for name, k in k_indices(C).items()}
+    defects["one_hidden_unit_dropped"] = hidden_dropped(4 * C - 31, 4 * C - 30)
+    defects[f"last_{width}_hidden_units_dropped"] = hidden_dropped(4 * C - width, 4 * C)
+    for name, v in vec_variants(inp["b1"]).items():
+        defects[f"b1_{name}"] = b1_as(v)
+    for name, v in vec_variants(inp["gamma"]).items():
+        defects[f"gamma_{name}"] = gamma_as(v)
+    for vec in ("b2",) + (("lw", "lb") if segs is not None else ()):
+        for name, v in vec_variants(inp[vec]).items():
+            defects[f"{vec}_{name}"] = (lambda i, vec=vec, v=v: tail(_with(i, **{vec: v}), stages(i)[2]))
+    defects["branch_15_16"] = lambda i: tail(i, stages(i)[2], branch=15 / 16)
+    defects["gamma_as_one"] = lambda i: tail(i, stages(i)[1] @ w2g(i, gamma_one=True).t(), gamma_one=True)
+    if M > 1:
+        defects["last_row_from_row_before"] = lambda i: tail(i, stages(i)[2], last_from_prev=True)
+        defects["resid_from_row_before"] = lambda i: tail(i, stages(i)[2], resid_shift=True)
+    if segs is not None:
+        defects["quadrants_dy_dx_swapped"] = lambda i: tail(i, stages(i)[2], idx=index[:, [0, 2, 1, 3]])
+        if len(segs) > 1 and segs[1][2] != segs[0][2]:
+            def prev_geometry(i):
+                idx = index.clone()
+                r = sum(n * (h // 2) * (w // 2) for n, h, w in segs[:1])     # first patch row of the second segment ...
+                t0, wprev = segs[0][0] * segs[0][1] * segs[0][2], segs[0][2]
+                idx[r] = torch.tensor([t0, t0 + 1, t0 + wprev, t0 + wprev + 1])   # ... with the first segment's width
+                return tail(i, stages(i)[2], idx=idx)
+            defects["segment_start_with_previous_geometry"] = prev_geometry
+    family, scale = ("mlp", 2.0) if segs is None else ("mlp_lnp", 4.0)
+    return Case(family, dtype, inp, ref, model, defects, scale,
+                what=f"fused mlp C={C} M={M}" + (f" + LN-patchify {segs}" if segs is not None else ""))

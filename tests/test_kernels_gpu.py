@@ -1,6 +1,9 @@
 """Per-kernel parity on the MI355X: every HIP kernel (called through the C ABI's gcv_k_* entry
 points) against a plain PyTorch fp32 CPU reference of the same op.  fp32 storage must agree to
-~1e-5; 16-bit storage is checked against the same fp32 math on inputs rounded to that dtype."""
+~1e-5; 16-bit storage is checked against the same fp32 math on inputs rounded to that dtype.
+The families that feed the verdict (fused MLPs, the GEMM epilogues, conv-as-GEMM, dw7x7 + LN) take inputs, float64
+reference and per-element comparator from tests/kcases.py; tests/test_kernel_sensitivity_cpu.py shows, without a GPU,
+which planted defects that comparator rejects."""
 import ctypes
 import math
 
@@ -9,7 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from genconvit_amd import _lib
-from tests import dwcases, kutil
+from tests import dwcases, kcases, kutil
 from tests.kutil import DTYPES, dev, gemm, ptr, rnd, tol
 
 pytestmark = pytest.mark.gpu
@@ -61,15 +64,14 @@ def assert_close(got, want, atol, what=""):
 ])
 def test_gemm_bias_act(dt, M, N, K, act):
     dtype = DTYPES[dt]
-    A, W = q(rnd((M, K), 1), dtype), q(rnd((N, K), 2, 1 / math.sqrt(K)), dtype)
-    bias = rnd((N,), 3, 0.1)
+    case = kcases.gemm("bias_act", M, N, K, dtype, act=act)
+    i = case.inputs
     ldc = N + 8
     C = torch.full((M, ldc), 7.0, dtype=dtype, device=dev())
-    gemm(dtype, _lib.A_PLAIN, _lib.EPI_BIAS_ACT, A.to(dev(), dtype), W.to(dev(), dtype), C, M, N, K, lda=K, ldc=ldc,
-         bias=bias.to(dev()), act=act)
-    want = act_ref(A @ W.t() + bias, act)
-    assert_close(C[:, :N], want, tol(dtype, 2.0), "gemm")
+    gemm(dtype, _lib.A_PLAIN, _lib.EPI_BIAS_ACT, D(i["A"], dtype), D(i["W"], dtype), C, M, N, K, lda=K, ldc=ldc,
+         bias=D(i["bias"]), act=act)
     assert torch.all(C[:, N:].float() == 7.0), "padding columns were overwritten"
+    case.assert_close(C[:, :N])
 
 
 @pytest.mark.parametrize("dt", ALL)
@@ -99,26 +101,28 @@ def test_gelu_nan_behaviour_is_documented(dt):
 @pytest.mark.parametrize("dt", ALL)
 @pytest.mark.parametrize("M,N,K", [(300, 96, 384), (150, 256, 64), (129, 768, 3072)])
 def test_gemm_layerscale_residual(dt, M, N, K):
-    dtype = DTYPES[dt]
-    A, W = q(rnd((M, K), 1), dtype), q(rnd((N, K), 2, 1 / math.sqrt(K)), dtype)
-    bias, gamma = rnd((N,), 3, 0.1), rnd((N,), 4, 0.5)
-    X = q(rnd((M, N), 5), dtype)
-    Xd = X.to(dev(), dtype)
-    gemm(dtype, _lib.A_PLAIN, _lib.EPI_RESID, A.to(dev(), dtype), W.to(dev(), dtype), Xd, M, N, K, lda=K, ldc=N,
-         bias=bias.to(dev()), gamma=gamma.to(dev()), resid=Xd)          # in place, like the forward does
-    want = X + gamma * (A @ W.t() + bias)
-    assert_close(Xd, want, tol(dtype, 2.0), "gemm resid")
+    _resid_case(DTYPES[dt], M, N, K)
+
+
+def _resid_case(dtype, M, N, K):
+    case = kcases.gemm("resid", M, N, K, dtype)
+    i = case.inputs
+    Xd = D(i["X"], dtype).clone()
+    gemm(dtype, _lib.A_PLAIN, _lib.EPI_RESID, D(i["A"], dtype), D(i["W"], dtype), Xd, M, N, K, lda=K, ldc=N,
+         bias=D(i["bias"]), gamma=D(i["gamma"]), resid=Xd)              # in place, like the forward does
+    case.assert_close(Xd)
 
 
 @pytest.mark.parametrize("dt", ALL)
 @pytest.mark.parametrize("M,N,K,splitk,kps", [(8, 256, 512, 4, 128), (40, 384, 1024, 2, 512), (130, 128, 640, 3, 256)])
 def test_gemm_splitk(dt, M, N, K, splitk, kps):
     dtype = DTYPES[dt]
-    A, W = q(rnd((M, K), 1), dtype), q(rnd((N, K), 2, 1 / math.sqrt(K)), dtype)
+    case = kcases.gemm("splitk", M, N, K, dtype, k_per_split=kps)
+    i = case.inputs
     part = torch.zeros((splitk, M, N), dtype=torch.float32, device=dev())
-    gemm(dtype, _lib.A_PLAIN, _lib.EPI_SPLITK, A.to(dev(), dtype), W.to(dev(), dtype), None, M, N, K, lda=K,
+    gemm(dtype, _lib.A_PLAIN, _lib.EPI_SPLITK, D(i["A"], dtype), D(i["W"], dtype), None, M, N, K, lda=K,
          partial=part, splitk=splitk, k_per_split=kps)
-    assert_close(part.sum(0), A @ W.t(), 2e-5 if dt == "f32" else 1e-4, "splitk")
+    case.assert_close(part.sum(0))
 
 
 # ----------------------------------------------------------------------------- conv as GEMM
@@ -128,16 +132,14 @@ def test_gemm_splitk(dt, M, N, K, splitk, kps):
 def test_conv3x3_relu_maxpool(dt, n, H, cin, cout):
     """ED encoder layers 2-5 (model/genconvit_ed.py:18-32): conv3x3 s1 p1 -> ReLU -> maxpool2."""
     dtype = DTYPES[dt]
-    x = q(rnd((n, cin, H, H), 1), dtype)
-    w = q(rnd((cout, cin, 3, 3), 2, 1 / math.sqrt(9 * cin)), dtype)
-    b = rnd((cout,), 3, 0.1)
-    want = F.max_pool2d(F.relu(F.conv2d(x, w, b, padding=1)), 2).permute(0, 2, 3, 1)
-    x_nhwc = x.permute(0, 2, 3, 1).contiguous().to(dev(), dtype)
-    wt = w.permute(0, 2, 3, 1).reshape(cout, 9 * cin).contiguous().to(dev(), dtype)
+    case = kcases.conv3x3_pool(n, H, cin, cout, dtype)
+    x, w, b = (case.inputs[k] for k in ("x", "w", "b"))
+    x_nhwc = D(x.permute(0, 2, 3, 1).contiguous(), dtype)
+    wt = D(w.permute(0, 2, 3, 1).reshape(cout, 9 * cin).contiguous(), dtype)
     out = torch.zeros((n, H // 2, H // 2, cout), dtype=dtype, device=dev())
     gemm(dtype, _lib.A_IM2COL3_POOL, _lib.EPI_POOL4, x_nhwc, wt, out, n * H * H, cout, 9 * cin, ldc=cout,
-         bias=b.to(dev()), act=1, H=H, W=H, cin_log2=int(math.log2(cin)))
-    assert_close(out, want, tol(dtype, 2.0), "conv3 pool")
+         bias=D(b), act=1, H=H, W=H, cin_log2=int(math.log2(cin)))
+    case.assert_close(out)
 
 
 @pytest.mark.parametrize("dt", ALL)
@@ -145,16 +147,14 @@ def test_conv3x3_relu_maxpool(dt, n, H, cin, cout):
 def test_conv3x3_stride2_leaky(dt, n, H, cin, cout):
     """VAE encoder layers 2-4 (model/genconvit_vae.py:19-30), BatchNorm folded by the caller."""
     dtype = DTYPES[dt]
-    x = q(rnd((n, cin, H, H), 1), dtype)
-    w = q(rnd((cout, cin, 3, 3), 2, 1 / math.sqrt(9 * cin)), dtype)
-    b = rnd((cout,), 3, 0.1)
-    want = F.leaky_relu(F.conv2d(x, w, b, stride=2, padding=1), 0.01).permute(0, 2, 3, 1)
-    x_nhwc = x.permute(0, 2, 3, 1).contiguous().to(dev(), dtype)
-    wt = w.permute(0, 2, 3, 1).reshape(cout, 9 * cin).contiguous().to(dev(), dtype)
+    case = kcases.conv3x3_s2(n, H, cin, cout, dtype)
+    x, w, b = (case.inputs[k] for k in ("x", "w", "b"))
+    x_nhwc = D(x.permute(0, 2, 3, 1).contiguous(), dtype)
+    wt = D(w.permute(0, 2, 3, 1).reshape(cout, 9 * cin).contiguous(), dtype)
     out = torch.zeros((n, H // 2, H // 2, cout), dtype=dtype, device=dev())
     gemm(dtype, _lib.A_IM2COL3_S2, _lib.EPI_BIAS_ACT, x_nhwc, wt, out, n * (H // 2) ** 2, cout, 9 * cin, ldc=cout,
-         bias=b.to(dev()), act=3, H=H, W=H, cin_log2=int(math.log2(cin)))
-    assert_close(out, want, tol(dtype, 2.0), "conv3 s2")
+         bias=D(b), act=3, H=H, W=H, cin_log2=int(math.log2(cin)))
+    case.assert_close(out)
 
 
 @pytest.mark.parametrize("dt", ALL)
@@ -162,16 +162,14 @@ def test_conv3x3_stride2_leaky(dt, n, H, cin, cout):
 def test_conv_transpose_2x2(dt, n, H, cin, cout, act):
     """ED / VAE decoder ConvTranspose2d(k=2,s=2) layers (genconvit_ed.py:44-55, genconvit_vae.py:68-76)."""
     dtype = DTYPES[dt]
-    x = q(rnd((n, cin, H, H), 1), dtype)
-    w = q(rnd((cin, cout, 2, 2), 2, 1 / math.sqrt(cin)), dtype)
-    b = rnd((cout,), 3, 0.1)
-    want = act_ref(F.conv_transpose2d(x, w, b, stride=2), act).permute(0, 2, 3, 1)
-    x_nhwc = x.permute(0, 2, 3, 1).contiguous().to(dev(), dtype)
-    wt = w.permute(2, 3, 1, 0).reshape(4 * cout, cin).contiguous().to(dev(), dtype)    # ((dy,dx,co), ci)
+    case = kcases.conv_transpose2x2(n, H, cin, cout, act, dtype)
+    x, w, b = (case.inputs[k] for k in ("x", "w", "b"))
+    x_nhwc = D(x.permute(0, 2, 3, 1).contiguous(), dtype)
+    wt = D(w.permute(2, 3, 1, 0).reshape(4 * cout, cin).contiguous(), dtype)           # ((dy,dx,co), ci)
     out = torch.zeros((n, 2 * H, 2 * H, cout), dtype=dtype, device=dev())
-    gemm(dtype, _lib.A_PLAIN, _lib.EPI_CONVT, x_nhwc, wt, out, n * H * H, 4 * cout, cin, lda=cin, bias=b.to(dev()),
+    gemm(dtype, _lib.A_PLAIN, _lib.EPI_CONVT, x_nhwc, wt, out, n * H * H, 4 * cout, cin, lda=cin, bias=D(b),
          act=act, H=H, W=H, cout_log2=int(math.log2(cout)))
-    assert_close(out, want, tol(dtype, 2.0), "convT")
+    case.assert_close(out)
 
 
 # ----------------------------------------------------------------------------- ConvNeXt pieces
@@ -237,28 +235,15 @@ def test_stem_valu_kernel_in_16bit_storage(dt, C, layout, path):
 @pytest.mark.parametrize("C,H,n", dwcases.SQUARE)
 def test_dwconv7x7_layernorm(dt, C, H, n):
     """ConvNeXt block front half: depthwise 7x7 p3 + LayerNorm(C, eps 1e-6), NHWC."""
-    dtype = DTYPES[dt]
-    x = q(rnd((n, C, H, H), 1, 2.0), dtype)
-    w = rnd((C, 1, 7, 7), 2, 0.25)
-    b, lw, lb = rnd((C,), 3, 0.1), rnd((C,), 4, 0.5) + 1.0, rnd((C,), 5, 0.1)
-    y = F.conv2d(x, w, b, padding=3, groups=C).permute(0, 2, 3, 1)
-    want = F.layer_norm(y, (C,), lw, lb, 1e-6)
-    xd = x.permute(0, 2, 3, 1).contiguous().to(dev(), dtype)
-    wdw = w.reshape(C, 49).t().contiguous().to(dev())
-    out = torch.zeros((n, H, H, C), dtype=dtype, device=dev())
-    kutil.call("gcv_k_dwconv7_ln", _lib.dtype_code(dtype), ptr(xd), ptr(wdw), ptr(D(b)), ptr(D(lw)),
-               ptr(D(lb)), ptr(out), n, H, H, C, 1e-6)
-    assert_close(out, want, tol(dtype, 3.0), "dwconv_ln")
+    _dw_case(DTYPES[dt], C, H, H, n)
 
 
 def _dw_case(dtype, C, H, W, n, shift=0):
-    """gcv_k_dwconv7_ln on n maps of H x W x C against F.conv2d + F.layer_norm (fp32, CPU).  The output buffer is one image
-    longer than the launch and pre-filled with a sentinel: nothing behind the last image — and, with `shift` elements of
-    offset from the allocation's start, nothing in front of the first — may be written."""
-    x = q(rnd((n, C, H, W), 1, 2.0), dtype)
-    w = rnd((C, 1, 7, 7), 2, 0.25)
-    b, lw, lb = rnd((C,), 3, 0.1), rnd((C,), 4, 0.5) + 1.0, rnd((C,), 5, 0.1)
-    want = F.layer_norm(F.conv2d(x, w, b, padding=3, groups=C).permute(0, 2, 3, 1), (C,), lw, lb, 1e-6)
+    """gcv_k_dwconv7_ln on n maps of H x W x C against the float64 conv + LayerNorm of kcases.dwconv7_ln.  The output buffer
+    is one image longer than the launch and pre-filled with a sentinel: nothing behind the last image — and, with `shift`
+    elements of offset from the allocation's start, nothing in front of the first — may be written."""
+    case = kcases.dwconv7_ln(C, H, W, n, dtype, aligned=shift == 0)
+    x, w, b, lw, lb = (case.inputs[k] for k in ("x", "w", "b", "lw", "lb"))
     img = H * W * C
     xbuf = torch.zeros((shift + n * img,), dtype=dtype, device=dev())
     xbuf[shift:] = x.permute(0, 2, 3, 1).reshape(-1).to(dev(), dtype)
@@ -269,7 +254,7 @@ def _dw_case(dtype, C, H, W, n, shift=0):
     kutil.call("gcv_k_dwconv7_ln", _lib.dtype_code(dtype), ptr(xd), ptr(wdw), ptr(D(b)), ptr(D(lw)), ptr(D(lb)), ptr(out),
                n, H, W, C, 1e-6)
     assert (ybuf[:shift].float() == 7.0).all() and (out[n * img:].float() == 7.0).all(), "written outside the n images"
-    assert_close(out[:n * img].reshape(n, H, W, C), want, tol(dtype, 3.0), f"dwconv_ln C={C} {H}x{W} n={n}")
+    case.assert_close(out[:n * img].reshape(n, H, W, C))
 
 
 @pytest.mark.parametrize("dt", ALL)
@@ -490,6 +475,21 @@ def test_vote_sigmoid_mean():
     assert_close(got, torch.sigmoid(logits).mean(0), 1e-6, "vote")
 
 
+@pytest.mark.parametrize("rows", [1, 256, 257, 1000])
+def test_vote_sigmoid_mean_across_waves_and_loop_trips(rows):
+    """vote_kernel is one 256-thread block: the 37 rows above are one wave and one trip of its stride loop.  256 rows fill
+    all four waves once, 257 and 1000 take further trips, so the cross-wave sum and the loop carry weight; 1 row is the
+    mean's degenerate case.  Logits span +-30 (fp32 sigmoid is 0 or 1 beyond about +-17) in seeded random order; against
+    float64."""
+    logits = torch.linspace(-30.0, 30.0, 2 * rows)[torch.randperm(2 * rows, generator=torch.Generator().manual_seed(1))]
+    logits = logits.reshape(rows, 2).contiguous()
+    got = _lib.vote(logits.to(dev()))
+    torch.cuda.synchronize()
+    want = torch.sigmoid(logits.double()).mean(0)
+    err = (got.double().cpu() - want).abs().max().item()
+    assert err <= 1e-6, f"vote over {rows} rows: max abs err {err:.3e} > 1e-6"
+
+
 # ----------------------------------------------------------------------------- error behaviour
 def test_errors_are_raised_not_swallowed():
     with pytest.raises(_lib.GenConViTHipError, match="multiple of the 16-byte chunk"):
@@ -564,18 +564,20 @@ def test_mean_over_tokens(dt):
                                  (384, 60013)])     # ... 235 token tiles: unsplit pw1, full-width 256x384 pw2 tiles, ragged last block
 def test_fused_mlp_layerscale_residual(dt, C, M):
     """timm ConvNeXtBlock tail: fc1 -> exact GELU -> fc2 -> * gamma -> + shortcut, hidden kept on chip."""
-    dtype = DTYPES[dt]
-    x = q(rnd((M, C), 1, 1.5), dtype)
-    w1 = q(rnd((4 * C, C), 2, 1 / math.sqrt(C)), dtype)
-    w2 = q(rnd((C, 4 * C), 3, 1 / math.sqrt(4 * C)), dtype)
-    b1, b2, gamma = rnd((4 * C,), 4, 0.1), rnd((C,), 5, 0.1), rnd((C,), 6, 0.5)
-    res = q(rnd((M, C), 7), dtype)
-    h = q(F.gelu(x @ w1.t() + b1), dtype)          # the kernel rounds the hidden activation to T for GEMM2
-    want = res + gamma * (h @ w2.t() + b2)
-    out = D(res, dtype).clone()
-    kutil.call("gcv_k_fused_mlp", _lib.dtype_code(dtype), C, ptr(D(x, dtype)), ptr(D(w1, dtype)), ptr(D(b1)),
-               ptr(D(w2)), ptr(D(b2)), ptr(D(gamma)), ptr(out), ptr(out), M)
-    assert_close(out, want, tol(dtype, 2.0), "fused mlp")
+    mlp_case(DTYPES[dt], C, M)
+
+
+def mlp_case(dtype, C, M, **kw):
+    """gcv_k_fused_mlp in place on the shortcut, against kcases.fused_mlp; the rows behind M carry a sentinel.  Also used
+    by tests/test_mlp_bias_init_gpu.py"""
+    case = kcases.fused_mlp(C, M, dtype, **kw)
+    i = case.inputs
+    out = torch.full((M + 8, C), 7.0, dtype=dtype, device=dev())
+    out[:M] = i["res"].to(dev(), dtype)
+    kutil.call("gcv_k_fused_mlp", _lib.dtype_code(dtype), C, ptr(D(i["x"], dtype)), ptr(D(i["w1"], dtype)), ptr(D(i["b1"])),
+               ptr(D(i["w2"])), ptr(D(i["b2"])), ptr(D(i["gamma"])), ptr(out), ptr(out), M)
+    assert (out[M:].float() == 7.0).all(), "rows past M were written"
+    case.assert_close(out[:M])
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
@@ -583,19 +585,7 @@ def test_fused_mlp_layerscale_residual(dt, C, M):
 def test_fused_mlp_at_a_handful_of_tokens(dt, C, M):
     """One frame at res 32 is 64 / 16 / 4 / 1 tokens at stages 0 - 3: the fused MLP kinds (Fused96, Xs192, Pair384) far below
     one token tile, and one token above a 32- and a 128-token tile.  The rows behind M carry a sentinel."""
-    dtype = DTYPES[dt]
-    x = q(rnd((M, C), 1, 1.5), dtype)
-    w1 = q(rnd((4 * C, C), 2, 1 / math.sqrt(C)), dtype)
-    w2 = q(rnd((C, 4 * C), 3, 1 / math.sqrt(4 * C)), dtype)
-    b1, b2, gamma = rnd((4 * C,), 4, 0.1), rnd((C,), 5, 0.1), rnd((C,), 6, 0.5)
-    res = q(rnd((M, C), 7), dtype)
-    want = res + gamma * (q(F.gelu(x @ w1.t() + b1), dtype) @ w2.t() + b2)
-    out = torch.full((M + 8, C), 7.0, dtype=dtype, device=dev())
-    out[:M] = res.to(dev(), dtype)
-    kutil.call("gcv_k_fused_mlp", _lib.dtype_code(dtype), C, ptr(D(x, dtype)), ptr(D(w1, dtype)), ptr(D(b1)),
-               ptr(D(w2)), ptr(D(b2)), ptr(D(gamma)), ptr(out), ptr(out), M)
-    assert (out[M:].float() == 7.0).all(), "rows past M were written"
-    assert_close(out[:M], want, tol(dtype, 2.0), f"fused mlp C={C} M={M}")
+    mlp_case(DTYPES[dt], C, M)
 
 
 @pytest.mark.parametrize("dt", ALL)
@@ -662,36 +652,29 @@ def test_fused_mlp_layernorm_patchify_epilogue(dt, C, segs):
     """Last block of ConvNeXt stage 0 / 1 as the network runs it in 16-bit storage: MLP + layer scale + shortcut, then the
     stage boundary's LayerNorm2d and the 2x2 space-to-depth of its stride-2 conv in the same kernel's epilogue (timm
     ConvNeXtStage.downsample; fused_mlp_res_kernel<T, true> at C = 96, xs_mlp_kernel<T, 192, true>).  Checked element-wise
-    against plain torch: F.layer_norm of the fp32 MLP output, then the patch gather, per segment."""
-    dtype = DTYPES[dt]
+    against kcases.fused_mlp(segs=...): float64 LayerNorm of the float64 MLP output, then the patch gather, per segment."""
+    mlp_lnp_case(DTYPES[dt], C, segs)
+
+
+def mlp_lnp_case(dtype, C, segs, **kw):
+    """gcv_k_fused_mlp_lnp on the segments (images, H, W); also used by tests/test_mlp_bias_init_gpu.py"""
     M = sum(n * h * w for n, h, w in segs)
-    x = q(rnd((M, C), 1, 1.5), dtype)
-    w1 = q(rnd((4 * C, C), 2, 1 / math.sqrt(C)), dtype)
-    w2 = q(rnd((C, 4 * C), 3, 1 / math.sqrt(4 * C)), dtype)
-    b1, b2, gamma = rnd((4 * C,), 4, 0.1), rnd((C,), 5, 0.1), rnd((C,), 6, 0.5)
-    res = q(rnd((M, C), 7), dtype)
-    lw, lb = rnd((C,), 8, 0.5) + 1.0, rnd((C,), 9, 0.1)
-    h = q(F.gelu(x @ w1.t() + b1), dtype)
-    y = res + gamma * (h @ w2.t() + b2)            # the residual stream the kernel keeps in registers (fp32)
-    yn = F.layer_norm(y, (C,), lw, lb, 1e-6)
-    want, tok0, hw, wd, out0, t = [], [], [], [], [], 0
+    case = kcases.fused_mlp(C, M, dtype, segs=segs, **kw)
+    i = case.inputs
+    tok0, hw, wd, out0, t = [], [], [], [], 0
     for n, H, W in segs:
         tok0.append(t); hw.append(H * W); wd.append(W); out0.append(t // 4)
-        v = yn[t:t + n * H * W].reshape(n, H // 2, 2, W // 2, 2, C).permute(0, 1, 3, 2, 4, 5)
-        want.append(v.reshape(n * (H // 2) * (W // 2), 4 * C))
         t += n * H * W
-    want = torch.cat(want)
     out = torch.full((M // 4 + 3, 4 * C), 7.0, dtype=dtype, device=dev())
     arr = lambda v: (ctypes.c_int * 4)(*(v + [0] * (4 - len(v))))
     a_tok0, a_hw, a_wd, a_out0 = arr(tok0), arr(hw), arr(wd), arr(out0)
-    resd = D(res, dtype)
-    kutil.call("gcv_k_fused_mlp_lnp", _lib.dtype_code(dtype), C, ptr(D(x, dtype)), ptr(D(w1, dtype)), ptr(D(b1)),
-               ptr(D(w2)), ptr(D(b2)), ptr(D(gamma)), ptr(resd), ptr(D(lw)), ptr(D(lb)), 1e-6, len(segs), a_tok0, a_hw, a_wd,
-               a_out0, ptr(out), M)
-    assert torch.equal(resd.cpu(), res.to(dtype)), "the residual stream must not be written"
+    resd = D(i["res"], dtype)
+    kutil.call("gcv_k_fused_mlp_lnp", _lib.dtype_code(dtype), C, ptr(D(i["x"], dtype)), ptr(D(i["w1"], dtype)),
+               ptr(D(i["b1"])), ptr(D(i["w2"])), ptr(D(i["b2"])), ptr(D(i["gamma"])), ptr(resd), ptr(D(i["lw"])),
+               ptr(D(i["lb"])), 1e-6, len(segs), a_tok0, a_hw, a_wd, a_out0, ptr(out), M)
+    assert torch.equal(resd.cpu(), i["res"].to(dtype)), "the residual stream must not be written"
     assert (out[M // 4:].float() == 7.0).all(), "rows behind the last patch row were written"
-    # y ~ U(-1, 1) + small: LayerNorm output of magnitude ~3 (lw up to 1.5, |z| up to ~2.5) -> scale 4
-    assert_close(out[:M // 4], want, tol(dtype, 4.0), "fused mlp + LN-patchify")
+    case.assert_close(out[:M // 4])
 
 
 # ----------------------------------------------------------------------------- LDS-DMA pipelined GEMM
@@ -716,14 +699,7 @@ def test_gemm_lds_dma_pipeline_bias_act(dt, M, N, K, act):
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
 @pytest.mark.parametrize("M,N,K", [(1000, 384, 1536), (257, 768, 3072), (640, 192, 768)])
 def test_gemm_lds_dma_pipeline_residual(dt, M, N, K):
-    dtype = DTYPES[dt]
-    A, W = q(rnd((M, K), 1), dtype), q(rnd((N, K), 2, 1 / math.sqrt(K)), dtype)
-    bias, gamma = rnd((N,), 3, 0.1), rnd((N,), 4, 0.5)
-    X = q(rnd((M, N), 5), dtype)
-    Xd = D(X, dtype).clone()
-    gemm(dtype, _lib.A_PLAIN, _lib.EPI_RESID, D(A, dtype), D(W, dtype), Xd, M, N, K, lda=K, ldc=N, bias=D(bias),
-         gamma=D(gamma), resid=Xd)
-    assert_close(Xd, X + gamma * (A @ W.t() + bias), tol(dtype, 2.0), "glds gemm resid")
+    _resid_case(DTYPES[dt], M, N, K)
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
@@ -743,14 +719,7 @@ def test_gemm_lds_dma_many_tiles_bias_act(dt, M, N, K, act):
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
 @pytest.mark.parametrize("M,N,K", [(32868, 384, 1536), (16500, 768, 3072)])
 def test_gemm_lds_dma_many_tiles_residual(dt, M, N, K):
-    dtype = DTYPES[dt]
-    A, W = q(rnd((M, K), 1), dtype), q(rnd((N, K), 2, 1 / math.sqrt(K)), dtype)
-    bias, gamma = rnd((N,), 3, 0.1), rnd((N,), 4, 0.5)
-    X = q(rnd((M, N), 5), dtype)
-    Xd = D(X, dtype).clone()
-    gemm(dtype, _lib.A_PLAIN, _lib.EPI_RESID, D(A, dtype), D(W, dtype), Xd, M, N, K, lda=K, ldc=N, bias=D(bias),
-         gamma=D(gamma), resid=Xd)
-    assert_close(Xd, X + gamma * (A @ W.t() + bias), tol(dtype, 2.0), "glds gemm resid (many tiles)")
+    _resid_case(DTYPES[dt], M, N, K)
 
 
 def test_preprocess_frame_on_device_matches_reference_semantics():
