@@ -80,6 +80,9 @@ SIGNATURES = {
     "gcv_track_match": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gcv_frame_hist": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gcv_hist_diff": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "gcv_frame_cells": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gcv_blend_fit": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gcv_hist_diff_lag": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gcv_vote_segments": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "gcv_vote_windows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "gcv_tap_set": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t]),
@@ -715,6 +718,80 @@ def hist_diff(hist):
         check(load().gcv_hist_diff(hist.data_ptr(), nf, CUT_REGIONS[[r * r for r in CUT_REGIONS].index(rr)], dist.data_ptr(),
                                 current_stream_ptr(hist.device)), "gcv_hist_diff")
     return dist
+
+
+def hist_diff_lag(hist, lag):
+    """``hist_diff`` between frames p and p + ``lag`` (``gcv_hist_diff_lag``): (max(F - lag, 0), R^2) int32 on the device,
+    nothing launched when it is empty.  ``lag``: an integer >= 1; ``lag`` = 1 is ``hist_diff``."""
+    import torch
+    if not (torch.is_tensor(hist) and hist.is_cuda and hist.dtype == torch.int32 and hist.dim() == 3
+            and hist.shape[0] >= 1 and hist.shape[2] == CUT_BINS and hist.shape[1] in [r * r for r in CUT_REGIONS]):
+        raise GenConViTHipError("hist_diff_lag expects an int32 device tensor of shape (F, R^2, 64), F >= 1, R in 1, 2, 4, 8")
+    if isinstance(lag, bool) or not isinstance(lag, int) or lag < 1:
+        raise GenConViTHipError(f"hist_diff_lag: lag {lag} must be an integer >= 1")
+    hist = hist.contiguous()
+    nf, rr, _ = hist.shape
+    dist = torch.empty((max(nf - lag, 0), rr), dtype=torch.int32, device=hist.device)
+    if nf > lag:
+        check(load().gcv_hist_diff_lag(hist.data_ptr(), nf, CUT_REGIONS[[r * r for r in CUT_REGIONS].index(rr)], lag,
+                                    dist.data_ptr(), current_stream_ptr(hist.device)), "gcv_hist_diff_lag")
+    return dist
+
+
+CELL_GRIDS, CELL_MAX_PIXELS, FIT_LAGS = (8, 16, 32), 1 << 25, (2, 32)
+
+
+def frame_cells(frames_u8, grid=16, out=None):
+    """Luma sums of the ``grid`` x ``grid`` cells of every frame (``gcv_frame_cells``, include/genconvit_hip.h: the arithmetic
+    is stated there).  ``frames_u8``: (F,H,W,3) uint8 device tensor (RGB), F >= 1; a slice such as ``frames[1:]`` is used in
+    place, whatever its alignment.  Returns (F, grid^2) int32 on the device: the C entry's uint32 sums, which stay below
+    2^29.  ``out``: write into this contiguous int32 tensor of that shape on the same device instead of a new one (the rows
+    of one group of frames in a whole video's buffer).  ``grid`` other than 8, 16, 32, a frame lower or narrower than
+    ``grid``, more than 2^25 pixels a frame (the bound that keeps ``blend_fit``'s 64-bit sums exact), a host tensor and a
+    wrong shape or dtype are errors."""
+    import torch
+    if not (torch.is_tensor(frames_u8) and frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4
+            and frames_u8.shape[3] == 3 and frames_u8.shape[0] >= 1):
+        raise GenConViTHipError("frame_cells expects a uint8 device tensor of shape (F,H,W,3), F >= 1")
+    if isinstance(grid, bool) or not isinstance(grid, int) or grid not in CELL_GRIDS:
+        raise GenConViTHipError(f"frame_cells: grid {grid}; accepted values are 8, 16 and 32")
+    frames_u8 = frames_u8.contiguous()
+    nf, h, w, _ = frames_u8.shape
+    if h < grid or w < grid or h * w > CELL_MAX_PIXELS:
+        raise GenConViTHipError(f"frame_cells: frames of {h}x{w} pixels; each side must be at least grid = {grid} and a "
+                                f"frame hold at most 2^25 pixels")
+    shape = (nf, grid * grid)
+    if out is None:
+        cells = torch.empty(shape, dtype=torch.int32, device=frames_u8.device)
+    elif (torch.is_tensor(out) and out.dtype == torch.int32 and out.device == frames_u8.device and tuple(out.shape) == shape
+          and out.is_contiguous()):
+        cells = out
+    else:
+        raise GenConViTHipError(f"frame_cells: out must be a contiguous int32 tensor of shape {shape} on {frames_u8.device}")
+    check(load().gcv_frame_cells(frames_u8.data_ptr(), nf, h, w, grid, cells.data_ptr(), current_stream_ptr(frames_u8.device)),
+          "gcv_frame_cells")
+    return cells
+
+
+def blend_fit(cells, lag):
+    """How well the frames inside every span of ``lag`` frames lie on the line between the span's ends
+    (``gcv_blend_fit``, include/genconvit_hip.h).  ``cells``: (F, G^2) int32 device tensor as ``frame_cells`` returns it, G in
+    8, 16, 32, entries non-negative and every row's sum of squares below 2^62 (rows of ``frame_cells`` are); ``lag``: an
+    integer in 2 ... 32.  Returns (max(F - lag, 0), 2 lag - 1) int64 on the device, rows [Sdd, Smd_1 ... Smd_(lag-1),
+    Smm_1 ... Smm_(lag-1)], exact; nothing is launched when it is empty."""
+    import torch
+    if not (torch.is_tensor(cells) and cells.is_cuda and cells.dtype == torch.int32 and cells.dim() == 2
+            and cells.shape[0] >= 1 and cells.shape[1] in [g * g for g in CELL_GRIDS]):
+        raise GenConViTHipError("blend_fit expects an int32 device tensor of shape (F, G^2), F >= 1, G in 8, 16, 32")
+    if isinstance(lag, bool) or not isinstance(lag, int) or not FIT_LAGS[0] <= lag <= FIT_LAGS[1]:
+        raise GenConViTHipError(f"blend_fit: lag {lag} must be an integer in {FIT_LAGS[0]} ... {FIT_LAGS[1]}")
+    cells = cells.contiguous()
+    nf, gg = cells.shape
+    fit = torch.empty((max(nf - lag, 0), 2 * lag - 1), dtype=torch.int64, device=cells.device)
+    if nf > lag:
+        check(load().gcv_blend_fit(cells.data_ptr(), nf, CELL_GRIDS[[g * g for g in CELL_GRIDS].index(gg)], lag, fit.data_ptr(),
+                                current_stream_ptr(cells.device)), "gcv_blend_fit")
+    return fit
 
 
 _JET = {}

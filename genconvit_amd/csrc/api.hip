@@ -757,6 +757,21 @@ int gcv_hist_diff(const uint32_t* hist_u32, int nframes, int regions, uint32_t* 
   return launch_hist_diff(hist_u32, nframes, regions, dist_u32, (hipStream_t)s);
 }
 
+int gcv_hist_diff_lag(const uint32_t* hist_u32, int nframes, int regions, int lag, uint32_t* dist_u32, gcv_stream s) {
+  GCV_REQUIRE((lag > 0 && nframes > 0 && nframes <= lag) || (hist_u32 && dist_u32), "hist diff: null pointer");
+  return launch_hist_diff_lag(hist_u32, nframes, regions, lag, dist_u32, (hipStream_t)s);
+}
+
+int gcv_frame_cells(const void* frames_u8_nhwc, int nframes, int H, int W, int grid, uint32_t* cells_u32, gcv_stream s) {
+  GCV_REQUIRE(frames_u8_nhwc && cells_u32, "frame cells: null pointer");
+  return launch_frame_cells((const unsigned char*)frames_u8_nhwc, nframes, H, W, grid, cells_u32, (hipStream_t)s);
+}
+
+int gcv_blend_fit(const uint32_t* cells_u32, int nframes, int grid, int lag, int64_t* fit_i64, gcv_stream s) {
+  GCV_REQUIRE((lag > 0 && nframes > 0 && nframes <= lag) || (cells_u32 && fit_i64), "blend fit: null pointer");
+  return launch_blend_fit(cells_u32, nframes, grid, lag, fit_i64, (hipStream_t)s);
+}
+
 int gcv_k_fused_mlp(int dtype, int C, const void* x, const void* w1, const float* b1, const float* w2_f32,
                     const float* b2, const float* gamma, const void* resid, void* out, int M, gcv_stream s) {
   GCV_REQUIRE(dtype == GCV_F16 || dtype == GCV_BF16, "the MLP kernels are built for 16-bit storage");

@@ -4,7 +4,8 @@ Same names and argument meaning (``load_genconvit``, ``preprocess_frame``, ``pre
 ``max_prediction_value``, ``real_or_fake``, ``df_face``, ``face_rec``, ``extract_frames``,
 ``is_video``, ``set_result``, ``store_result``), plus what the reference lacks: evidence maps (``explain_*``) and the
 whole-video scan with per-track sliding-window verdicts (``scan_frames``, ``scan_video``; ``follow_tracks`` moves the
-boxes of frames the detector skipped onto the face, ``shot_cuts`` finds the hard cuts at which tracks end).  ``prediction.py`` star-imports this module and
+boxes of frames the detector skipped onto the face, ``shot_cuts`` finds the hard cuts at which tracks end, ``shot_transitions`` the fades and dissolves whose frames stay out
+of them).  ``prediction.py`` star-imports this module and
 relies on ``torch``/``os``/``np`` coming along, so they stay module globals.  The heavy CPU-side
 dependencies (dlib, face_recognition, decord) are imported lazily inside the video / face
 functions so the model path imports on a box without them; cv2 is not needed any more (the crop +
@@ -384,7 +385,8 @@ def shot_cuts(frames, threshold=0.4, regions=4, max_frames=128, dev=None):
     Returns ``(cuts, scores)``: ``scores`` float64 numpy (F - 1,), and ``cuts`` the ascending frame numbers c = p + 1 with
     scores[p] >= ``threshold`` — a new shot starts at frame c.  F <= 1 gives ([], empty) and launches nothing; a
     ``threshold`` outside (0, 1] is a ValueError.
-    What this does not do: fades and dissolves are not detected, only hard cuts; a one-frame flash gives two adjacent
+    What this does not do: only hard cuts are found here — linear fades and dissolves are ``shot_transitions``'s to find,
+    eased ones and wipes nobody's; a one-frame flash gives two adjacent
     cuts; two shots with the same luma distribution in every part are not separated.  The default threshold is a starting
     value from synthetic material (about 0.05 inside a shot, about 0.7 at a cut); no accuracy is claimed — look at the
     scores and choose."""
@@ -397,20 +399,136 @@ def shot_cuts(frames, threshold=0.4, regions=4, max_frames=128, dev=None):
     nf, h, w = (int(v) for v in fr.shape[:3])
     if nf <= 1:
         return [], np.empty((0,), dtype=np.float64)
+    return _cuts_of(_frame_stats(fr, regions, None, max_frames, dev)[0], h, w, regions, threshold)
+
+
+def _frame_stats(fr, regions, grid, max_frames, dev):
+    """One pass over the frames (F >= 1) for ``shot_cuts`` and ``shot_transitions``: ``(hist, cells)``, the (F, R^2, 64)
+    histograms of ``_lib.frame_hist`` and the (F, G^2) cell sums of ``_lib.frame_cells``; ``regions`` or ``grid`` None leaves
+    that one out.  Device frames are used in place; host frames are uploaded once each, in consecutive groups of at most
+    ``max_frames``, and every group fills its rows of the two device buffers."""
     if fr.is_cuda:
-        hist = _lib.frame_hist(fr, regions)
-    else:
-        hist = torch.empty((nf, regions * regions, _lib.CUT_BINS), dtype=torch.int32, device=dev or device)
-        for g in range(0, nf, max_frames):
-            _lib.frame_hist(fr[g:g + max_frames].to(hist.device), regions, out=hist[g:g + max_frames])
-    dist = _lib.hist_diff(hist).cpu().numpy().view(np.uint32).astype(np.int64)              # (F - 1, R^2)
+        return (_lib.frame_hist(fr, regions) if regions else None), (_lib.frame_cells(fr, grid) if grid else None)
+    nf, d = int(fr.shape[0]), dev or device
+    hist = torch.empty((nf, regions * regions, _lib.CUT_BINS), dtype=torch.int32, device=d) if regions else None
+    cells = torch.empty((nf, grid * grid), dtype=torch.int32, device=d) if grid else None
+    for g in range(0, nf, max_frames):
+        slab = fr[g:g + max_frames].to(d)
+        if regions:
+            _lib.frame_hist(slab, regions, out=hist[g:g + max_frames])
+        if grid:
+            _lib.frame_cells(slab, grid, out=cells[g:g + max_frames])
+    return hist, cells
+
+
+def _hist_scores(dist, h, w, regions):
+    """The score of every row of a ``hist_diff`` / ``hist_diff_lag`` result, as ``shot_cuts`` defines it: float64 (rows,)."""
+    dist = dist.cpu().numpy().view(np.uint32).astype(np.int64)                                # (rows, R^2)
     ey = [(u * h) // regions for u in range(regions + 1)]
     ex = [(v * w) // regions for v in range(regions + 1)]
     pixels = np.array([(ey[u + 1] - ey[u]) * (ex[v + 1] - ex[v]) for u in range(regions) for v in range(regions)],
                       dtype=np.int64)
     kept = np.argsort(dist, axis=1, kind="stable")[:, :max(1, regions * regions // 2)]       # ties: the lower r
-    scores = np.take_along_axis(dist, kept, 1).sum(1) / (2.0 * pixels[kept].sum(1))
+    return np.take_along_axis(dist, kept, 1).sum(1) / (2.0 * pixels[kept].sum(1))
+
+
+def _cuts_of(hist, h, w, regions, threshold):
+    """``shot_cuts``'s result from the histograms of F >= 2 frames"""
+    scores = _hist_scores(_lib.hist_diff(hist), h, w, regions)
     return [int(p) + 1 for p in np.nonzero(scores >= threshold)[0]], scores
+
+
+TRANSITION_DEFAULTS = dict(lags=(4, 8), grid=16, h_min=0.25, rho_max=0.05, a_lo=0.1, a_hi=0.9, slack=0.05)
+
+
+def _check_transitions(what, regions, lags, grid, h_min, rho_max, a_lo, a_hi, slack):
+    integer = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    if not integer(regions) or regions not in _lib.CUT_REGIONS:
+        raise ValueError(f"{what}: regions {regions} must be 1, 2, 4 or 8")
+    if not integer(grid) or grid not in _lib.CELL_GRIDS:
+        raise ValueError(f"{what}: grid {grid} must be 8, 16 or 32")
+    if not (isinstance(lags, (list, tuple)) and len(lags) > 0 and all(integer(v) and 3 <= v <= _lib.FIT_LAGS[1] for v in lags)
+            and len(set(lags)) == len(lags)):
+        raise ValueError(f"{what}: lags {lags} must be distinct integers in 3 ... {_lib.FIT_LAGS[1]} (a span needs two frames "
+                         f"between its ends)")
+    number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v)
+    if not (all(number(v) for v in (h_min, rho_max, a_lo, a_hi, slack)) and 0.0 <= h_min <= 1.0 and rho_max >= 0.0
+            and 0.0 <= a_lo < a_hi <= 1.0 and slack >= 0.0):
+        raise ValueError(f"{what}: h_min {h_min} must lie in [0, 1], rho_max {rho_max} and slack {slack} be at least 0 and "
+                         f"0 <= a_lo {a_lo} < a_hi {a_hi} <= 1")
+
+
+def _transitions_of(hist, cells, nf, h, w, regions, lags, h_min, rho_max, a_lo, a_hi, slack):
+    """``shot_transitions``'s result from the histograms and the cells of the ``nf`` frames (both unused, and possibly None,
+    when no lag is below ``nf``)."""
+    marked, info = set(), {}
+    for lag in (int(v) for v in lags):
+        if nf > lag:
+            fit = _lib.blend_fit(cells, lag).cpu().numpy()                                    # (F - L, 2 L - 1) int64
+            scores = _hist_scores(_lib.hist_diff_lag(hist, lag), h, w, regions)
+        else:
+            fit, scores = np.zeros((0, 2 * lag - 1), dtype=np.int64), np.zeros((0,), dtype=np.float64)
+        some = fit[:, 0] > 0
+        sdd = np.where(some, fit[:, 0].astype(np.float64), 1.0)[:, None]
+        smd, smm = fit[:, 1:lag].astype(np.float64), fit[:, lag:].astype(np.float64)          # floats before any product
+        a = np.where(some[:, None], smd / sdd, 0.0)
+        rho = np.where(some[:, None], (smm - smd * smd / sdd) / sdd, np.inf)
+        inside = (a >= a_lo) & (a <= a_hi)
+        blend = (some & (scores >= h_min) & (rho.max(1) <= rho_max) & (a[:, 1:] >= a[:, :-1] - slack).all(1) &
+                 (inside.sum(1) >= 2))
+        for p in np.nonzero(blend)[0]:
+            marked |= {int(p) + 1 + int(k) for k in np.nonzero(inside[p])[0]}
+        info[lag] = {"scores": scores, "a": a, "rho": rho, "blend": blend}
+    out = []
+    for f in sorted(marked):
+        if out and out[-1][1] == f - 1:
+            out[-1] = (out[-1][0], f)
+        else:
+            out.append((f, f))
+    return out, info
+
+
+def shot_transitions(frames, lags=(4, 8), grid=16, regions=4, h_min=0.25, rho_max=0.05, a_lo=0.1, a_hi=0.9, slack=0.05,
+                     max_frames=128, dev=None):
+    """Where the fades and dissolves of a video are.  A linear dissolve makes every frame between its ends a pixelwise
+    blend (1 - a) A + a B of the two end pictures with a rising (a fade is a dissolve to or from a flat frame), so on a
+    ``grid`` x ``grid`` lattice of luma sums (``_lib.frame_cells``, G = 8, 16 or 32) the cell vector of a middle frame lies on
+    the straight line between the cell vectors of the ends; motion, cuts and flashes leave that line.  For every lag L of
+    ``lags`` (integers in 3 ... 32) and every span p of frames p ... p + L, ``_lib.blend_fit`` gives the exact integer sums
+    Sdd, Smd_k, Smm_k of D = cells[p + L] - cells[p] and M_k = cells[p + k] - cells[p], k = 1 ... L - 1, from which, in
+    float64 (the integers are converted before anything is multiplied),
+        a_k = Smd_k / Sdd               where frame p + k lies on the line, 0 at p and 1 at p + L
+        rho_k = (Smm_k - Smd_k^2 / Sdd) / Sdd   its squared distance from the line over the line's squared length.
+    Slow motion is linear in the cells to first order too, but keeps the luma distribution, which a blend does not: the
+    ends of a span must also differ by the score of ``shot_cuts`` taken at the lag L (``_lib.frame_hist`` on ``regions`` x
+    ``regions`` parts, ``_lib.hist_diff_lag``).  Span p is a blend span iff
+        Sdd > 0,  that score >= ``h_min``,  max_k rho_k <= ``rho_max``,  a_(k+1) >= a_k - ``slack`` for all k,
+        and at least two k have ``a_lo`` <= a_k <= ``a_hi``;
+    those frames p + k of it are marked.  The union over all spans and lags is taken, and the maximal runs of marked frames
+    are the transitions.
+    ``frames``: uint8 (F,H,W,3) RGB, numpy or a tensor.  Frames on the GPU are used in place.  Host frames are uploaded (to
+    ``dev``, by default this module's ``device``) once each, in consecutive groups of at most ``max_frames``, every group one
+    ``frame_cells`` and one ``frame_hist`` launch into its rows of a single (F, G^2) and a single (F, R^2, 64) device buffer;
+    the fits then run over the whole buffers, so device memory for pixels is bounded by the group, not the video.
+    Returns ``(transitions, info)``: ``transitions`` the list of (first, last), frames inclusive and ascending, and
+    ``info[L]`` for every lag a dict of ``scores`` (F - L,), ``a`` and ``rho`` (F - L, L - 1), all float64 (a = 0 and rho = inf
+    where Sdd = 0), and ``blend`` (F - L,) bool: which spans passed — to look at and choose thresholds by.  A lag that is
+    not below F gives empty arrays and launches nothing.  Bad ``lags``, ``grid``, ``regions`` or thresholds are a ValueError.
+    What this does not do: non-linear (eased) dissolves, whose a_k still rise but whose frames this marks only as far as
+    they stay near the line; wipes; transitions shorter than 3 frames (a span needs two frames strictly between its ends); a
+    pan whose content change passes ``h_min`` is not told from a blend.  The defaults are starting values from synthetic
+    material (there the accepted spans have rho <= 0.038 and scores >= 0.79, the spans of moving shots that pass every
+    other test rho >= 0.058, and a pan of one pixel a frame scores <= 0.19); no accuracy is claimed — look at ``info`` and
+    choose."""
+    _check_transitions("shot_transitions", regions, lags, grid, h_min, rho_max, a_lo, a_hi, slack)
+    if max_frames < 1:
+        raise ValueError(f"shot_transitions: max_frames {max_frames} must be at least 1")
+    fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
+    if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
+        raise _lib.GenConViTHipError("shot_transitions: frames must be uint8 of shape (F,H,W,3)")
+    nf, h, w = (int(v) for v in fr.shape[:3])
+    hist, cells = _frame_stats(fr, regions, grid, max_frames, dev) if nf > min(lags) else (None, None)
+    return _transitions_of(hist, cells, nf, h, w, regions, lags, h_min, rho_max, a_lo, a_hi, slack)
 
 
 def _verdict(m):
@@ -419,7 +537,8 @@ def _verdict(m):
 
 
 def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3, window=15, stride=1, max_batch=128,
-                eps=None, follow=False, follow_grid=64, follow_radius=16, cuts=None, cut_threshold=0.4, cut_regions=4):
+                eps=None, follow=False, follow_grid=64, follow_radius=16, cuts=None, cut_threshold=0.4, cut_regions=4,
+                transitions=None, transition_args=None):
     """When is a video fake, and whose face: every face of every frame is scored, linked into per-person tracks, and voted
     over sliding windows of each track.  ``frames``: uint8 (F,H,W,3) RGB, numpy or a tensor on either device.  ``boxes``:
     rows (frame, top, right, bottom, left); by default the detector — ``locate``, else ``face_locations(..., keep_all=True)``
@@ -459,10 +578,39 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
     segment and no ``follow`` job, straddles a cut.  The result gains ``cuts``, and ``cut_scores`` (float64 (F - 1,)) when
     they were computed here: the default threshold is a starting value, not a tuned one.  With ``detect_every`` > 1 a face
     goes unscored between its last detection before a cut and its first detection after it: tracks are not extended past
-    a detection.  Fades and dissolves are not found, and a one-frame flash gives two adjacent cuts."""
+    a detection.  ``cuts`` finds hard cuts only, and a one-frame flash gives two adjacent cuts; linear fades and dissolves
+    are what ``transitions`` is for.
+    ``transitions`` (``None`` by default: nothing changes): the fades and dissolves of edited footage.  A dissolve from one
+    talking head to another leaves a box where a box was, so IoU joins the two people, and the frames inside it show a
+    blended face that is no evidence of anything.  ``True``: ``shot_transitions(frames, regions=cut_regions,
+    max_frames=max_batch, **transition_args)`` over ALL scanned frames (``transition_args``: a dict of its ``lags``,
+    ``grid``, ``h_min``, ``rho_max``, ``a_lo``, ``a_hi``, ``slack``; None: its defaults) — with ``cuts=True`` as well, every
+    group of host frames is uploaded once and feeds both; a list: (first, last) pairs of integers, frames inclusive, 0 <=
+    first <= last < F, anything else is a ValueError.  The boxes on the frames of a transition are dropped before tracking
+    — they are not cut, scored or voted, and ``eps`` counts the crops that remain — and first and last + 1 join the cuts
+    handed to ``track_boxes`` where they lie in [1, F - 1], so no track, window, segment or ``follow`` job reaches into or
+    across a transition.  The result gains ``transitions`` (sorted), and ``transition_info`` (``shot_transitions``'s
+    ``info``) when they were computed here; ``cuts`` keeps holding the hard cuts alone.  Linear blends of at least 3
+    frames only: eased dissolves and wipes are not found, a fast pan can pass for one, and the thresholds are starting
+    values, not tuned ones."""
     fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
     if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
         raise _lib.GenConViTHipError("scan_frames: frames must be uint8 of shape (F,H,W,3)")
+    targs = dict(TRANSITION_DEFAULTS)
+    if transitions is True:
+        if transition_args is not None:
+            if not (isinstance(transition_args, dict) and set(transition_args) <= set(targs)):
+                raise ValueError(f"scan_frames: transition_args must be a dict with keys among {sorted(targs)}")
+            targs.update(transition_args)
+        _check_transitions("scan_frames", cut_regions, **targs)
+    elif transitions is not None:
+        given = list(transitions) if isinstance(transitions, (list, tuple)) else None
+        whole = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+        if given is None or not all(isinstance(t, (list, tuple)) and len(t) == 2 and whole(t[0]) and whole(t[1]) and
+                                    0 <= t[0] <= t[1] < fr.shape[0] for t in given):
+            raise ValueError(f"scan_frames: transitions must be True or a list of (first, last) integer pairs with "
+                             f"0 <= first <= last <= {fr.shape[0] - 1}")
+        transitions = sorted({(int(t[0]), int(t[1])) for t in given})
     if cuts is True:
         _check_cuts("scan_frames", cut_threshold, cut_regions)
     elif cuts is not None:
@@ -483,15 +631,27 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
     boxes = [tuple(int(v) for v in b) for b in boxes]
     _lib._check_boxes("scan_frames", boxes, *fr.shape[:3])
     p = next(model.parameters())
-    cut_scores = None
-    if cuts is True:
+    cut_scores = transition_info = None
+    if transitions is True:
+        nf, h, w = (int(v) for v in fr.shape[:3])
+        lags, grid = targs.pop("lags"), targs.pop("grid")
+        hist, cells = (_frame_stats(fr, cut_regions, grid, max_batch, p.device)                    # one upload feeds both
+                       if nf > (1 if cuts is True else min(lags)) else (None, None))
+        transitions, transition_info = _transitions_of(hist, cells, nf, h, w, cut_regions, lags, **targs)
+        if cuts is True:
+            cuts, cut_scores = _cuts_of(hist, h, w, cut_regions, cut_threshold) if nf > 1 else ([], np.empty((0,), np.float64))
+    elif cuts is True:
         cuts, cut_scores = shot_cuts(fr, cut_threshold, cut_regions, max_frames=max_batch, dev=p.device)
+    ends = cuts
+    if transitions is not None:
+        boxes = [b for b in boxes if not any(first <= b[0] <= last for first, last in transitions)]
+        ends = sorted(set(cuts or []) | {c for first, last in transitions for c in (first, last + 1) if 1 <= c < fr.shape[0]})
     if follow:
-        tracks, anchors = track_boxes(boxes, iou=iou, max_gap=detect_every, return_anchors=True, cuts=cuts)
+        tracks, anchors = track_boxes(boxes, iou=iou, max_gap=detect_every, return_anchors=True, cuts=ends)
         tracks, moved = follow_tracks(fr, tracks, anchors, grid=follow_grid, radius=follow_radius,
                                       max_frames=max(max_batch, 3), dev=p.device)
     else:
-        tracks = track_boxes(boxes, iou=iou, max_gap=detect_every, cuts=cuts)
+        tracks = track_boxes(boxes, iou=iou, max_gap=detect_every, cuts=ends)
     rows = [b for tr in tracks for b in tr]
     offsets = [0] + [int(v) for v in np.cumsum([len(tr) for tr in tracks])]
     n = len(rows)
@@ -503,6 +663,10 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
         res["cuts"] = cuts
         if cut_scores is not None:
             res["cut_scores"] = cut_scores
+    if transitions is not None:
+        res["transitions"] = transitions
+        if transition_info is not None:
+            res["transition_info"] = transition_info
     if n == 0:
         res["frame_scores"] = torch.empty((0, 2), dtype=torch.float32, device=p.device)
         res["window_means"] = torch.empty((0, 2), dtype=torch.float32, device=p.device)

@@ -284,11 +284,55 @@ int gcv_track_match(const void* frames_u8_nhwc, int nframes, int H, int W, const
  * frames, R = 1 or 2), several per region whose counts are merged by integer atomic adds into the output, which a
  * hipMemsetAsync on the stream zeroes first — integer adds commute, so the result is the same whatever the order.
  * gcv_hist_diff is one launch.  Neither call allocates, copies or synchronises anything.
- * Not done here: fades and dissolves (only a hard cut changes every region at once), and two shots whose regions have the
- * same luma distribution are not told apart. */
+ * Not done here: fades and dissolves (only a hard cut changes every region at once; the three entries below are for
+ * those), and two shots whose regions have the same luma distribution are not told apart. */
 int gcv_frame_hist(const void* frames_u8_nhwc, int nframes, int H, int W, int regions, uint32_t* hist_u32,
                    gcv_stream stream);
 int gcv_hist_diff(const uint32_t* hist_u32, int nframes, int regions, uint32_t* dist_u32, gcv_stream stream);
+
+/* Fades and dissolves: luma sums on a grid of cells (gcv_frame_cells), the least-squares sums of every frame of a span
+ * against the line between the span's two ends (gcv_blend_fit), and the histogram distance between those ends
+ * (gcv_hist_diff_lag).  A linear dissolve makes every frame between its ends a pixelwise blend (1 - a) A + a B, so the
+ * cell vector of a middle frame lies on the straight line between the cell vectors of the ends; motion, cuts and flashes
+ * leave that line.  pred_func.shot_transitions turns the sums into transitions, whose frames a scan keeps out of tracks.
+ *   frames   as for gcv_frame_hist: any alignment, and no byte outside [frames, frames + nframes H W 3) is read
+ *   grid     G: 8, 16 or 32; a frame is cut into G x G cells
+ *   cells    (nframes, G G) uint32: cells[f][u G + v] = the sum of Y over the pixels of cell (u, v) of frame f.  Every
+ *            element is written
+ *   lag      L: the span p has the ends p and p + L.  gcv_blend_fit: 2 ... 32; gcv_hist_diff_lag: any L >= 1
+ *   fit      (nframes - L, 2 L - 1) int64; with A = cells[p], B = cells[p + L], D = B - A and M_k = cells[p + k] - A for
+ *            k = 1 ... L - 1 (differences of integers, signed), the row p is
+ *              [ Sdd, Smd_1 ... Smd_(L-1), Smm_1 ... Smm_(L-1) ],
+ *              Sdd = sum over the cells of D D,  Smd_k = sum of M_k D,  Smm_k = sum of M_k M_k
+ *            The least-squares position of frame p + k on the line is a_k = Smd_k / Sdd, and its squared distance from the
+ *            line, relative to the line's squared length, rho_k = (Smm_k - Smd_k^2 / Sdd) / Sdd — the caller's to compute, in
+ *            floating point (Smd_k^2 does not fit 64 bits)
+ *   dist     (nframes - L, R R) uint32: dist[p][r] = sum over b of |hist[p + L][r][b] - hist[p][r][b]|; L = 1 is
+ *            gcv_hist_diff
+ * Arithmetic (fixed and all-integer, so that a CPU restatement is bit-equal: tests/transutil.py); a // b is floor division:
+ *   cell (u, v)       rows [(u H) // G, ((u + 1) H) // G) and columns [(v W) // G, ((v + 1) W) // G), the region rule of
+ *                     gcv_frame_hist.  H >= G and W >= G, so no cell is empty
+ *   luma of a pixel   Y = (77 R + 150 G + 29 B + 128) >> 8, as above
+ *   the sums          exact in int64 whenever every row of cells has a sum of squares below 2^62: then Sdd <= |A|^2 + |B|^2
+ *                     < 2^63 (the entries are non-negative), Smm_k alike, and |Smd_k| <= sqrt(Smm_k Sdd) < 2^63.  Rows
+ *                     from gcv_frame_cells meet this: a side of a cell is ceil(H / G) < 2 H / G pixels at most, so a cell
+ *                     holds n < 4 H W / G^2 <= H W / 16 of them, and the sum of squares of a row is at most
+ *                     255^2 max(n) sum(n) < 255^2 (H W)^2 / 16 <= 65025 * 2^46 < 2^62 for H W <= 2^25 — the bound
+ *                     gcv_frame_cells enforces (a cell is then below 2^29, and fits 32 bits with room to spare).  Rows
+ *                     from elsewhere are the caller's to check
+ * Refused before anything is launched (gcv_last_error() says why): grid not 8, 16 or 32; nframes, H or W not positive;
+ * H < grid or W < grid; H W > 2^25; lag outside 2 ... 32 (blend fit) or below 1 (hist diff); regions not 1, 2, 4 or 8; a
+ * null pointer.  gcv_blend_fit and gcv_hist_diff_lag with nframes <= lag launch nothing, write nothing and return 0.
+ * gcv_frame_cells reads every pixel once: one workgroup per row of G cells of a frame, or, where that leaves the chip idle
+ * (few frames), several per row, merged by integer atomic adds into the output, which a hipMemsetAsync on the stream
+ * zeroes first.  gcv_blend_fit is one launch, a workgroup per span; gcv_hist_diff_lag is gcv_hist_diff's kernel.  None of
+ * the calls allocates, copies or synchronises anything.
+ * Not done here: non-linear (eased) dissolves, wipes, and telling a slow pan from a blend — the cells of a slow pan are
+ * close to linear too, which is why pred_func.shot_transitions also asks the ends of a span to differ in gcv_hist_diff_lag. */
+int gcv_frame_cells(const void* frames_u8_nhwc, int nframes, int H, int W, int grid, uint32_t* cells_u32,
+                    gcv_stream stream);
+int gcv_blend_fit(const uint32_t* cells_u32, int nframes, int grid, int lag, int64_t* fit_i64, gcv_stream stream);
+int gcv_hist_diff_lag(const uint32_t* hist_u32, int nframes, int regions, int lag, uint32_t* dist_u32, gcv_stream stream);
 
 /* pred_vid's reduction (model/pred_func.py:120,125): mean2[c] = mean_r sigmoid(logits[r][c]). */
 int gcv_vote(const float* logits, int rows, float* mean2, gcv_stream stream);
