@@ -669,6 +669,12 @@ int gcv_k_pool_ln(int dtype, const void* x, const float* w, const float* b, void
   DISPATCH_DT(dtype, launch_pool_ln<T>((const T*)x, w, b, (T*)out, nimg, HW, C, eps, (hipStream_t)s));
 }
 
+int gcv_k_pool_ln_rows(int dtype, const void* x, const float* w, const float* b, void* out, int nimg, int HW, int C,
+                       float eps, int seg_n, int row_stride, int row0, gcv_stream s) {
+  DISPATCH_DT(dtype, launch_pool_ln<T>((const T*)x, w, b, (T*)out, nimg, HW, C, eps, (hipStream_t)s, seg_n, row_stride,
+                                       row0));
+}
+
 int gcv_k_conv3_first(int dtype, const void* x, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* wp,
                       const float* bias, void* out, int nimg, int H, int W, int pool, int act, gcv_stream s) {
   DISPATCH_DT(dtype, launch_conv3_first<T>((const T*)x, sb, sc, sy, sx, wp, bias, (T*)out, nimg, H, W, pool != 0, act,

@@ -449,6 +449,10 @@ int gcv_k_layernorm_rows(int dtype, const void* x, const float* w, const float* 
                          float eps, gcv_stream s);
 int gcv_k_pool_ln(int dtype, const void* x, const float* w, const float* b, void* out, int nimg, int HW, int C,
                   float eps, gcv_stream s);
+/* gcv_k_pool_ln with the row mapping the networks use: image b of the launch -> output row
+ * (b % seg_n) * row_stride + row0 + b / seg_n (seg_n <= 0: plain order, as gcv_k_pool_ln) */
+int gcv_k_pool_ln_rows(int dtype, const void* x, const float* w, const float* b, void* out, int nimg, int HW, int C,
+                       float eps, int seg_n, int row_stride, int row0, gcv_stream s);
 int gcv_k_conv3_first(int dtype, const void* x, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* wp,
                       const float* bias, void* out, int nimg, int H, int W, int pool, int act, gcv_stream s);
 int gcv_k_convt2_small(int dtype, const void* x, const float* wp, const float* bias, void* out, int nimg, int H,

@@ -1,9 +1,11 @@
 """Per-kernel parity on the MI355X: every HIP kernel (called through the C ABI's gcv_k_* entry
 points) against a plain PyTorch fp32 CPU reference of the same op.  fp32 storage must agree to
 ~1e-5; 16-bit storage is checked against the same fp32 math on inputs rounded to that dtype.
-The families that feed the verdict (fused MLPs, the GEMM epilogues, conv-as-GEMM, dw7x7 + LN) take inputs, float64
-reference and per-element comparator from tests/kcases.py; tests/test_kernel_sensitivity_cpu.py shows, without a GPU,
-which planted defects that comparator rejects."""
+The families that feed the verdict (fused MLPs, the GEMM epilogues, conv-as-GEMM, dw7x7 + LN, and the small kernels between a
+frame and the two logits: stem, LN-patchify, pool + LN, first conv, last convT, reparam, head tail, resize + MSE) take inputs,
+float64 reference and per-element comparator from tests/kcases.py; tests/test_kernel_sensitivity_cpu.py shows, without a GPU,
+which planted defects that comparator rejects.  Where a case is meant for one kernel of a launcher, the test asserts the
+launcher's own rule on the pointers, strides and shape it passes.  The Swin kernels keep the fp32 reference and flat bound."""
 import ctypes
 import math
 
@@ -173,27 +175,85 @@ def test_conv_transpose_2x2(dt, n, H, cin, cout, act):
 
 
 # ----------------------------------------------------------------------------- ConvNeXt pieces
+H16 = ["bf16", "f16"]
+SENT = 7.0
+
+
+def _stem_takes_matrix_pipe(dtype, x_ptr, out_ptr, sb, sc, sy, sx, total):
+    """launch_stem_ln_c's own test (csrc/kernels_impl.h): stem_ln_mfma_kernel for 16-bit storage, x 8-byte and `out` 16-byte
+    aligned, sb and sy multiples of 4, and NCHW (sx = 1, sc a multiple of 4) or NHWC (sc = 1, sx = 3); else stem_ln_kernel"""
+    if dtype == torch.float32:
+        return False
+    al = x_ptr % 8 == 0 and (sb | sy) % 4 == 0 and out_ptr % 16 == 0
+    return al and ((sx == 1 and sc % 4 == 0) or (sc == 1 and sx == 3)) and total < 1 << 30
+
+
+def _stem_case(dtype, C, n, Ho, Wo, layout, kernel, pad=0, xs=0, os_=0, entry="gcv_k_stem_ln_c"):
+    """the stem on n frames of 4 Ho x 4 Wo against kcases.stem.  `pad`: the NCHW frames are cut out of a buffer whose rows are
+    `pad` elements longer (filled with 3); xs / os_: x / out that many elements off their allocation's start.  `kernel`
+    ("mfma" / "valu") is asserted by the launcher's own rule.  Sentinels in front of and behind the T tokens of `out`."""
+    case = kcases.stem(C, n, Ho, Wo, layout, dtype)
+    i = case.inputs
+    H, W, T = 4 * Ho, 4 * Wo, n * Ho * Wo
+    if layout == "nchw":
+        frame = torch.full((n, 3, H, W + pad), 3.0)
+        frame[..., :W] = i["x"]
+        st = (3 * H * (W + pad), H * (W + pad), W + pad, 1)
+    else:
+        assert pad == 0
+        frame, st = i["x"].permute(0, 2, 3, 1).contiguous(), (H * W * 3, 1, W * 3, 3)
+    xbuf = torch.zeros((xs + frame.numel(),), dtype=dtype, device=dev())
+    xbuf[xs:] = frame.reshape(-1).to(dev(), dtype)
+    obuf = torch.full((os_ + (T + 8) * C,), SENT, dtype=dtype, device=dev())
+    xd, out = xbuf[xs:], obuf[os_:]
+    assert xd.data_ptr() % 8 == (xs * xd.element_size()) % 8 and out.data_ptr() % 16 == (os_ * out.element_size()) % 16
+    takes = _stem_takes_matrix_pipe(dtype, xd.data_ptr(), out.data_ptr(), *st, T)
+    assert takes == (kernel == "mfma"), f"this launch does not reach the {kernel} kernel"
+    wp = D(i["w"].reshape(C, 48).t().contiguous())
+    assert wp.data_ptr() % 16 == 0
+    args = (_lib.dtype_code(dtype), ptr(xd), *st, ptr(wp), ptr(D(i["bias"])), ptr(D(i["lw"])), ptr(D(i["lb"])), ptr(out),
+            n, Ho, Wo)
+    if entry == "gcv_k_stem_ln":
+        assert C == 96
+        kutil.call(entry, *args, 1e-6)
+    else:
+        kutil.call(entry, *args, C, 1e-6)
+    assert (obuf[:os_].float() == SENT).all() and (out[T * C:].float() == SENT).all(), "written outside the T tokens"
+    case.assert_close(out[:T * C].reshape(T, C))
+
+
 @pytest.mark.parametrize("dt", ALL)
 @pytest.mark.parametrize("layout,res", [("nchw", 224), ("nhwc", 112), ("nchw", 32), ("nchw", 20), ("nhwc", 20)])   # 20: a 25-token tail tile
 def test_stem_conv4x4_layernorm(dt, layout, res):
     dtype = DTYPES[dt]
-    n = 2
-    x = q(rnd((n, 3, res, res), 1, 2.0), dtype)
-    w = q(rnd((96, 3, 4, 4), 2, 0.2), dtype)          # 16-bit storage runs the stem on the matrix pipe: 16-bit weights
-    b, lw, lb = rnd((96,), 3, 0.1), rnd((96,), 4, 0.5) + 1.0, rnd((96,), 5, 0.1)
-    y = F.conv2d(x, w, b, stride=4).permute(0, 2, 3, 1)
-    want = F.layer_norm(y, (96,), lw, lb, 1e-6)
-    wp = w.reshape(96, 48).t().contiguous().to(dev())
-    if layout == "nchw":
-        xd = x.to(dev(), dtype)
-        st = (3 * res * res, res * res, res, 1)
-    else:
-        xd = x.permute(0, 2, 3, 1).contiguous().to(dev(), dtype)
-        st = (res * res * 3, 1, res * 3, 3)
-    out = torch.zeros((n, res // 4, res // 4, 96), dtype=dtype, device=dev())
-    kutil.call("gcv_k_stem_ln", _lib.dtype_code(dtype), ptr(xd), *st, ptr(wp), ptr(D(b)), ptr(D(lw)),
-               ptr(D(lb)), ptr(out), n, res // 4, res // 4, 1e-6)
-    assert_close(out, want, tol(dtype, 3.0), "stem")
+    _stem_case(dtype, 96, 2, res // 4, res // 4, layout, "valu" if dtype == torch.float32 else "mfma", entry="gcv_k_stem_ln")
+
+
+# (n, Ho, Wo, layout, pad): one token (every lane clamps to total - 1); 243 tokens (a ragged eighth tile, two workgroups);
+# a non-square frame; NCHW frames cut out of a buffer 8 elements wider than the row (sy = W + 8, sc = H sy, sb = 3 sc)
+_STEM_FRAMES = [(1, 1, 1, "nchw", 0), (1, 1, 1, "nhwc", 0), (3, 9, 9, "nchw", 0), (3, 9, 9, "nhwc", 0),
+                (2, 5, 8, "nchw", 0), (2, 5, 8, "nhwc", 0), (2, 5, 8, "nchw", 8)]
+
+
+@pytest.mark.parametrize("dt", H16)
+@pytest.mark.parametrize("C", [96, 192])
+@pytest.mark.parametrize("n,Ho,Wo,layout,pad", _STEM_FRAMES)
+def test_stem_matrix_pipe_kernel(dt, C, n, Ho, Wo, layout, pad):
+    """stem_ln_mfma_kernel<T, C / 32> at both widths and frame layouts"""
+    _stem_case(DTYPES[dt], C, n, Ho, Wo, layout, "mfma", pad=pad)
+
+
+def test_stem_matrix_pipe_kernel_second_trip_of_the_stride_loop():
+    """One frame of 513 x 513 tokens: 8225 tiles of 32 tokens on the grid's 2048 x 4 = 8192 waves, so 33 waves take a second trip
+    (the prefetch of tile + stride lands in a live tile) and the last tile is ragged (one token)."""
+    _stem_case(torch.bfloat16, 96, 1, 513, 513, "nchw", "mfma")
+
+
+@pytest.mark.parametrize("C", [96, 192])
+@pytest.mark.parametrize("layout,pad", [("nchw", 0), ("nhwc", 0), ("nchw", 8)])
+def test_stem_valu_kernel_fp32_off_square_and_strided_frames(C, layout, pad):
+    """stem_ln_kernel<float, C> on the non-square frame and on the frame with a row stride larger than the row"""
+    _stem_case(torch.float32, C, 2, 5, 8, layout, "valu", pad=pad)
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
@@ -207,28 +267,8 @@ def test_stem_valu_kernel_in_16bit_storage(dt, C, layout, path):
                and the strides only); the output is written one element at a time (`o[i] = from_f<T>(...)`).
       x+1elem: x one element off -> the per-element staging (`to_f(x[...])`); `out` aligned.
     res 36: 9 x 9 tokens per image, so the last workgroup's token tile is ragged.  Sentinels in front of and behind `out`."""
-    dtype = DTYPES[dt]
-    n, res = 3, 36
     xs, os_ = (0, 4) if path == "out+8B" else (1, 0)
-    x = q(rnd((n, 3, res, res), 1, 2.0), dtype)
-    w = q(rnd((C, 3, 4, 4), 2, 0.2), dtype)
-    b, lw, lb = rnd((C,), 3, 0.1), rnd((C,), 4, 0.5) + 1.0, rnd((C,), 5, 0.1)
-    want = F.layer_norm(F.conv2d(x, w, b, stride=4).permute(0, 2, 3, 1), (C,), lw, lb, 1e-6)
-    wp = w.reshape(C, 48).t().contiguous().to(dev())
-    if layout == "nchw":
-        flat, st = x, (3 * res * res, res * res, res, 1)
-    else:
-        flat, st = x.permute(0, 2, 3, 1).contiguous(), (res * res * 3, 1, res * 3, 3)
-    xbuf = torch.zeros((xs + flat.numel(),), dtype=dtype, device=dev())
-    xbuf[xs:] = flat.reshape(-1).to(dev(), dtype)
-    T = n * (res // 4) ** 2
-    obuf = torch.full((os_ + (T + 8) * C,), 7.0, dtype=dtype, device=dev())
-    out = obuf[os_:]
-    assert xbuf[xs:].data_ptr() % 8 == 2 * xs and out.data_ptr() % 16 == 2 * os_
-    kutil.call("gcv_k_stem_ln_c", _lib.dtype_code(dtype), ptr(xbuf[xs:]), *st, ptr(wp), ptr(D(b)), ptr(D(lw)), ptr(D(lb)),
-               ptr(out), n, res // 4, res // 4, C, 1e-6)
-    assert (obuf[:os_].float() == 7.0).all() and (out[T * C:].float() == 7.0).all(), "written outside the T tokens"
-    assert_close(out[:T * C].reshape(n, res // 4, res // 4, C), want, tol(dtype, 3.0), "stem (VALU kernel)")
+    _stem_case(DTYPES[dt], C, 3, 9, 9, layout, "valu", xs=xs, os_=os_)
 
 
 @pytest.mark.parametrize("dt", ALL)
@@ -284,37 +324,38 @@ def test_dwconv7x7_layernorm_band_kernels_off_square(dt, C, H, W, n):
     _dw_case(DTYPES[dt], C, H, W, n)
 
 
+def _lnp_case(dtype, C, H, W, n, kernel, shift=0):
+    """gcv_k_ln_patchify against kcases.ln_patchify; x `shift` elements off its allocation's start.  `kernel` ("vec" /
+    "generic") is asserted by launch_ln_patchify's own rule: ln_patchify_vec_kernel for 16-bit storage at C = 96 / 192 / 384
+    with x and out 4-byte aligned.  One image of sentinel behind the output."""
+    case = kcases.ln_patchify(C, H, W, n, dtype)
+    i = case.inputs
+    Ho, Wo = H // 2, W // 2
+    xbuf = torch.zeros((shift + i["x"].numel(),), dtype=dtype, device=dev())
+    xbuf[shift:] = i["x"].reshape(-1).to(dev(), dtype)
+    out = torch.full((n + 1, Ho, Wo, 4 * C), SENT, dtype=dtype, device=dev())
+    vec = dtype != torch.float32 and C in (96, 192, 384) and (xbuf[shift:].data_ptr() | out.data_ptr()) % 4 == 0
+    assert vec == (kernel == "vec"), f"this launch does not reach the {kernel} kernel"
+    kutil.call("gcv_k_ln_patchify", _lib.dtype_code(dtype), ptr(xbuf[shift:]), ptr(D(i["lw"])), ptr(D(i["lb"])), ptr(out),
+               n, H, W, C, 1e-6)
+    assert (out[n].float() == SENT).all(), "written beyond the last image"
+    case.assert_close(out[:n])
+
+
 @pytest.mark.parametrize("dt", ALL)
 @pytest.mark.parametrize("C,H", [(96, 56), (192, 28), (384, 14), (384, 7), (192, 14)])
 def test_layernorm2d_space_to_depth(dt, C, H):
     """Downsample front half: LayerNorm2d + 2x2 patch gather; odd sizes drop the last row/col (7 -> 3)."""
     dtype = DTYPES[dt]
-    n = 2
-    x = q(rnd((n, H, H, C), 1, 2.0), dtype)
-    lw, lb = rnd((C,), 4, 0.5) + 1.0, rnd((C,), 5, 0.1)
-    y = F.layer_norm(x, (C,), lw, lb, 1e-6)
-    Ho = H // 2
-    y = y[:, :2 * Ho, :2 * Ho]
-    want = y.reshape(n, Ho, 2, Ho, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(n, Ho, Ho, 4 * C)
-    out = torch.zeros((n, Ho, Ho, 4 * C), dtype=dtype, device=dev())
-    kutil.call("gcv_k_ln_patchify", _lib.dtype_code(dtype), ptr(D(x, dtype)), ptr(D(lw)),
-               ptr(D(lb)), ptr(out), n, H, H, C, 1e-6)
-    assert_close(out, want, tol(dtype, 3.0), "ln_patchify")
+    _lnp_case(dtype, C, H, H, 2, "generic" if dtype == torch.float32 else "vec")
 
 
-def _lnp_case(dtype, C, H, W, n, shift=0):
-    x = q(rnd((n, H, W, C), 1, 2.0), dtype)
-    lw, lb = rnd((C,), 4, 0.5) + 1.0, rnd((C,), 5, 0.1)
-    Ho, Wo = H // 2, W // 2
-    y = F.layer_norm(x, (C,), lw, lb, 1e-6)[:, :2 * Ho, :2 * Wo]
-    want = y.reshape(n, Ho, 2, Wo, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(n, Ho, Wo, 4 * C)
-    xbuf = torch.zeros((shift + x.numel(),), dtype=dtype, device=dev())
-    xbuf[shift:] = x.reshape(-1).to(dev(), dtype)
-    out = torch.full((n + 1, Ho, Wo, 4 * C), 7.0, dtype=dtype, device=dev())
-    kutil.call("gcv_k_ln_patchify", _lib.dtype_code(dtype), ptr(xbuf[shift:]), ptr(D(lw)), ptr(D(lb)), ptr(out), n, H, W, C,
-               1e-6)
-    assert (out[n].float() == 7.0).all(), "written beyond the last image"
-    assert_close(out[:n], want, tol(dtype, 3.0), f"ln_patchify C={C} {H}x{W}")
+@pytest.mark.parametrize("dt", H16)
+@pytest.mark.parametrize("C,H,W,n", [(96, 3, 5, 1),       # 15 pixels: fewer than one block's 16
+                                     (192, 2, 2, 1), (384, 7, 7, 2), (96, 6, 10, 3)])
+def test_layernorm2d_space_to_depth_vector_kernel(dt, C, H, W, n):
+    """ln_patchify_vec_kernel<T, C> at its three widths: less than one block, one patch row, odd and non-square maps"""
+    _lnp_case(DTYPES[dt], C, H, W, n, "vec")
 
 
 @pytest.mark.parametrize("dt", ALL)
@@ -322,7 +363,8 @@ def _lnp_case(dtype, C, H, W, n, shift=0):
 def test_layernorm2d_space_to_depth_generic_kernel(dt, C, H, W):
     """ln_patchify_kernel<T> in every storage dtype: C = 768 (ConvNeXt-L's stage 2 -> 3 boundary) has no vectorised kernel,
     so 16-bit storage runs the generic one too.  Even and odd maps (last row / column dropped) and a non-square one."""
-    _lnp_case(DTYPES[dt], C, H, W, 3)
+    dtype = DTYPES[dt]
+    _lnp_case(dtype, C, H, W, 3, "generic" if (dtype == torch.float32 or C == 768) else "vec")
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
@@ -331,21 +373,49 @@ def test_layernorm2d_space_to_depth_2byte_aligned_input(dt, H):
     """16-bit storage at C = 96 with x two bytes off a 4-byte boundary: launch_ln_patchify's own `al` test ((x | out) & 3)
     skips ln_patchify_vec_kernel for the generic kernel, which reads `src[c]` and writes `dst[c]` one element at a time
     (csrc/kernels_dev.h, ln_patchify_kernel)."""
-    _lnp_case(DTYPES[dt], 96, H, H, 2, shift=1)
+    _lnp_case(DTYPES[dt], 96, H, H, 2, "generic", shift=1)
+
+
+def _pool_case(dtype, C, HW, nimg, **rows_kw):
+    """gcv_k_pool_ln, or gcv_k_pool_ln_rows with the row mapping of `rows_kw`, against kcases.pool_ln.  The output buffer is
+    sentinel-filled and two rows longer than the last mapped row: only the mapped rows may be written."""
+    case = kcases.pool_ln(C, HW, nimg, dtype, **rows_kw)
+    i = case.inputs
+    nrows = max(case.rows) + 3
+    out = torch.full((nrows, C), SENT, dtype=dtype, device=dev())
+    args = (_lib.dtype_code(dtype), ptr(D(i["x"], dtype)), ptr(D(i["lw"])), ptr(D(i["lb"])), ptr(out), nimg, HW, C, 1e-6)
+    if rows_kw:
+        kutil.call("gcv_k_pool_ln_rows", *args, rows_kw["seg_n"], rows_kw["row_stride"], rows_kw["row0"])
+    else:
+        kutil.call("gcv_k_pool_ln", *args)
+    others = [r for r in range(nrows) if r not in case.rows]
+    assert (out[others].float() == SENT).all(), f"a row outside {case.rows} was written"
+    case.assert_close(out[case.rows])
 
 
 @pytest.mark.parametrize("dt", ALL)
 @pytest.mark.parametrize("HW", [49, 9])
 def test_avgpool_layernorm(dt, HW):
-    dtype = DTYPES[dt]
-    n, C = 5, 768
-    x = q(rnd((n, HW, C), 1, 2.0), dtype)
-    lw, lb = rnd((C,), 4, 0.5) + 1.0, rnd((C,), 5, 0.1)
-    want = F.layer_norm(x.mean(1), (C,), lw, lb, 1e-6)
-    out = torch.zeros((n, C), dtype=dtype, device=dev())
-    kutil.call("gcv_k_pool_ln", _lib.dtype_code(dtype), ptr(D(x, dtype)), ptr(D(lw)), ptr(D(lb)),
-               ptr(out), n, HW, C, 1e-6)
-    assert_close(out, want, tol(dtype, 3.0), "pool_ln")
+    _pool_case(DTYPES[dt], 768, HW, 5)
+
+
+@pytest.mark.parametrize("dt", ALL)
+@pytest.mark.parametrize("C,HW,nimg", [(768, 1, 3), (1536, 9, 2), (1536, 49, 4)])
+def test_avgpool_layernorm_single_token_and_wide(dt, C, HW, nimg):
+    """a single token (res 32), and pool_ln_kernel<T, 6> (ConvNeXt-L, C = 1536)"""
+    _pool_case(DTYPES[dt], C, HW, nimg)
+
+
+@pytest.mark.parametrize("dt", ALL)
+@pytest.mark.parametrize("C", [768, 1536])
+@pytest.mark.parametrize("nimg,seg_n,row_stride,row0", [(6, 3, 2, 0),       # rows 0, 2, 4, 1, 3, 5
+                                                        (3, 3, 2, 1)])      # rows 1, 3, 5; rows 0, 2, 4 keep the sentinel
+def test_avgpool_layernorm_row_mapping(dt, C, nimg, seg_n, row_stride, row0):
+    """The mapping the networks use to interleave their passes' rows (csrc/net_impl.h): image b -> row
+    (b % seg_n) * row_stride + row0 + b / seg_n, through gcv_k_pool_ln_rows."""
+    _pool_case(DTYPES[dt], C, 9, nimg, seg_n=seg_n, row_stride=row_stride, row0=row0)
+
+
 
 
 @pytest.mark.parametrize("dt", ALL)
@@ -363,109 +433,212 @@ def test_layernorm_rows(dt, C):
 
 
 # ----------------------------------------------------------------------------- AE / VAE small kernels
+def _conv3_takes_matrix_pipe(dtype, x_ptr, out_ptr, bias_ptr, sb, sc, sy, sx, H, W):
+    """launch_conv3_first's own test (csrc/kernels_impl.h): conv3_first_mfma_kernel for 16-bit storage, unit column stride,
+    W a multiple of 32 up to 224, H a multiple of 8, strides that are multiples of 8, x and bias 16-byte and `out` 8-byte
+    aligned; else conv3_first_kernel"""
+    return (dtype != torch.float32 and sx == 1 and W % 32 == 0 and W <= 224 and H % 8 == 0 and (sb | sc | sy) % 8 == 0
+            and x_ptr % 16 == 0 and out_ptr % 8 == 0 and bias_ptr % 16 == 0)
+
+
+def _conv3_case(dtype, n, H, W, pool, kernel, pad=0, strides="nchw"):
+    """gcv_k_conv3_first against kcases.conv3_first.  `pad`: NCHW frames cut out of a buffer whose rows are `pad` elements
+    longer (filled with 3); strides "nhwc": the frame uploaded channels-last (sc = 1, sx = 3).  `kernel` ("mfma" / "valu") is
+    asserted by the launcher's own rule.  Eight pixels of sentinel behind the output."""
+    case = kcases.conv3_first(n, H, W, pool, dtype, strides)
+    i = case.inputs
+    if strides == "nchw":
+        frame = torch.full((n, 3, H, W + pad), 3.0)
+        frame[..., :W] = i["x"]
+        st = (3 * H * (W + pad), H * (W + pad), W + pad, 1)
+    else:
+        assert pad == 0
+        frame, st = i["x"].permute(0, 2, 3, 1).contiguous(), (H * W * 3, 1, W * 3, 3)
+    xd, bias = D(frame, dtype), D(i["bias"])
+    P = n * (H // 2) * (W // 2)
+    out = torch.full((P + 8, 16), SENT, dtype=dtype, device=dev())
+    takes = _conv3_takes_matrix_pipe(dtype, xd.data_ptr(), out.data_ptr(), bias.data_ptr(), *st, H, W)
+    assert takes == (kernel == "mfma"), f"this launch does not reach the {kernel} kernel"
+    wp = D(i["w"].permute(2, 3, 1, 0).reshape(27, 16).contiguous())
+    kutil.call("gcv_k_conv3_first", _lib.dtype_code(dtype), ptr(xd), *st, ptr(wp), ptr(bias), ptr(out), n, H, W, int(pool),
+               1 if pool else 3)
+    assert (out[P:].float() == SENT).all(), "written behind the last pixel"
+    case.assert_close(out[:P].reshape(n, H // 2, W // 2, 16))
+
+
 @pytest.mark.parametrize("dt", ALL)
 @pytest.mark.parametrize("pool", [True, False])
 @pytest.mark.parametrize("H", [32, 224, 20])          # 20: not a multiple of 8 -> the VALU kernel for every dtype
 def test_first_conv_3_to_16(dt, pool, H):
     dtype = DTYPES[dt]
-    n = 2
-    x = q(rnd((n, 3, H, H), 1, 2.0), dtype)
-    w = q(rnd((16, 3, 3, 3), 2, 0.3), dtype)          # 16-bit storage runs on the matrix pipe: 16-bit weights
-    b = rnd((16,), 3, 0.1)
-    if pool:
-        want = F.max_pool2d(F.relu(F.conv2d(x, w, b, padding=1)), 2)
-        act = 1
-    else:
-        want = F.leaky_relu(F.conv2d(x, w, b, stride=2, padding=1), 0.01)
-        act = 3
-    want = want.permute(0, 2, 3, 1)
-    wp = w.permute(2, 3, 1, 0).reshape(27, 16).contiguous().to(dev())
-    out = torch.zeros((n, H // 2, H // 2, 16), dtype=dtype, device=dev())
-    kutil.call("gcv_k_conv3_first", _lib.dtype_code(dtype), ptr(D(x, dtype)), 3 * H * H, H * H, H, 1, ptr(wp),
-               ptr(D(b)), ptr(out), n, H, H, int(pool), act)
-    assert_close(out, want, tol(dtype, 3.0), "conv3_first")
+    _conv3_case(dtype, 2, H, H, pool, "valu" if (dtype == torch.float32 or H == 20) else "mfma")
+
+
+@pytest.mark.parametrize("dt", H16)
+@pytest.mark.parametrize("pool", [True, False])
+@pytest.mark.parametrize("n,H,W,pad", [(1, 8, 32, 0),         # one band, one column group
+                                       (3, 16, 96, 0),        # three column groups (it / ncg with ncg no power of two), two bands
+                                       (2, 24, 64, 0),        # a middle band: no zero rows above or below
+                                       (1, 8, 224, 0),        # the widest frame the LDS band holds
+                                       (2, 16, 32, 8)])       # row stride W + 8
+def test_first_conv_matrix_pipe_kernel(dt, pool, n, H, W, pad):
+    """conv3_first_mfma_kernel<T, POOL> off the square frames: non-square, several column groups and bands, a row stride
+    that is not the width"""
+    _conv3_case(DTYPES[dt], n, H, W, pool, "mfma", pad=pad)
+
+
+@pytest.mark.parametrize("dt", ALL)
+@pytest.mark.parametrize("pool", [True, False])
+@pytest.mark.parametrize("n,H,W", [(2, 20, 28),      # 280 pooled pixels: two blocks, the second mostly dead lanes
+                                   (1, 34, 18)])
+def test_first_conv_valu_kernel(dt, pool, n, H, W):
+    _conv3_case(DTYPES[dt], n, H, W, pool, "valu")
+
+
+@pytest.mark.parametrize("dt", H16)
+@pytest.mark.parametrize("pool", [True, False])
+def test_first_conv_valu_kernel_16bit_width_no_multiple_of_32(dt, pool):
+    """W = 48: W % 32 != 0 keeps an otherwise eligible 16-bit launch off the matrix pipe"""
+    _conv3_case(DTYPES[dt], 2, 8, 48, pool, "valu")
+
+
+@pytest.mark.parametrize("pool", [True, False])
+def test_first_conv_valu_kernel_fp32_channels_last_frame(pool):
+    """the frame addressed with NHWC strides (sc = 1, sx = 3)"""
+    _conv3_case(torch.float32, 2, 20, 28, pool, "valu", strides="nhwc")
+
+
+def _convt2_case(dtype, n, H, W, act):
+    """gcv_k_convt2_small against kcases.convt2_small; eight pixels of sentinel behind the output"""
+    case = kcases.convt2_small(n, H, W, act, dtype)
+    i = case.inputs
+    P = n * 2 * H * 2 * W
+    out = torch.full((P + 8, 3), SENT, dtype=dtype, device=dev())
+    kutil.call("gcv_k_convt2_small", _lib.dtype_code(dtype), ptr(D(i["x"].permute(0, 2, 3, 1).contiguous(), dtype)),
+               ptr(D(i["w"].permute(0, 2, 3, 1).reshape(16, 12).contiguous())), ptr(D(i["bias"])), ptr(out), n, H, W, act)
+    assert (out[P:].float() == SENT).all(), "written behind the last pixel"
+    case.assert_close(out[:P].reshape(n, 2 * H, 2 * W, 3))
 
 
 @pytest.mark.parametrize("dt", ALL)
 @pytest.mark.parametrize("act", [1, 3])
 def test_last_conv_transpose_16_to_3(dt, act):
-    dtype = DTYPES[dt]
-    n, H = 2, 12
-    x = q(rnd((n, 16, H, H), 1, 2.0), dtype)
-    w = rnd((16, 3, 2, 2), 2, 0.3)
-    b = rnd((3,), 3, 0.1)
-    want = act_ref(F.conv_transpose2d(x, w, b, stride=2), act).permute(0, 2, 3, 1)
-    wp = w.permute(0, 2, 3, 1).reshape(16, 12).contiguous().to(dev())
-    out = torch.zeros((n, 2 * H, 2 * H, 3), dtype=dtype, device=dev())
-    kutil.call("gcv_k_convt2_small", _lib.dtype_code(dtype), ptr(D(x.permute(0, 2, 3, 1).contiguous(), dtype)),
-               ptr(wp), ptr(D(b)), ptr(out), n, H, H, act)
-    assert_close(out, want, tol(dtype, 3.0), "convt2_small")
+    _convt2_case(DTYPES[dt], 2, 12, 12, act)
+
+
+@pytest.mark.parametrize("dt", ALL)
+@pytest.mark.parametrize("act", [1, 3])
+@pytest.mark.parametrize("n,H,W", [(1, 1, 1), (3, 5, 7), (1, 3, 90)])
+def test_last_conv_transpose_16_to_3_one_pixel_and_odd_maps(dt, act, n, H, W):
+    """one pixel; odd non-square maps of 105 and 270 pixels: a ragged block, and a second one"""
+    _convt2_case(DTYPES[dt], n, H, W, act)
+
+
+def _reparam_case(dtype, B, S, with_mu=True):
+    case = kcases.reparam(B, S, dtype)
+    i = case.inputs
+    N = kcases.REPARAM_N
+    mu_out = torch.full((B + 1, N), SENT, dtype=torch.float32, device=dev()) if with_mu else None
+    zout = torch.full((B + 1, N), SENT, dtype=dtype, device=dev())
+    kutil.call("gcv_k_reparam", _lib.dtype_code(dtype), ptr(D(i["part"])), S, ptr(D(i["bias"])), ptr(D(i["eps"])),
+               ptr(mu_out), ptr(zout), B, N)
+    assert (zout[B].float() == SENT).all() and (mu_out is None or (mu_out[B] == SENT).all()), "written behind row B"
+    case.assert_close({"z": zout[:B], **({"mu": mu_out[:B]} if with_mu else {})})
 
 
 @pytest.mark.parametrize("dt", ALL)
 def test_reparameterise_from_splitk(dt):
     """z = eps*exp(0.5*mu) + mu with std taken from mu (model/genconvit_vae.py:45-47), written NHWC."""
-    dtype = DTYPES[dt]
-    B, N, S = 3, 12544, 4
-    part = rnd((S, B, N), 1, 0.4)
-    bias, eps = rnd((N,), 2, 0.1), torch.randn((B, N), generator=torch.Generator().manual_seed(3))
-    mu = part.sum(0) + bias
-    z = eps * torch.exp(0.5 * mu) + mu
-    want = z.reshape(B, 256, 49).permute(0, 2, 1).reshape(B, N)
-    mu_out = torch.zeros((B, N), dtype=torch.float32, device=dev())
-    zout = torch.zeros((B, N), dtype=dtype, device=dev())
-    kutil.call("gcv_k_reparam", _lib.dtype_code(dtype), ptr(D(part)), S, ptr(D(bias)), ptr(D(eps)),
-               ptr(mu_out), ptr(zout), B, N)
-    assert_close(mu_out, mu, 1e-5, "mu")
-    assert_close(zout, want, tol(dtype, 8.0), "z")
+    _reparam_case(DTYPES[dt], 3, 4)
+
+
+@pytest.mark.parametrize("dt", ALL)
+def test_reparameterise_one_row_one_slab(dt):
+    _reparam_case(DTYPES[dt], 1, 1)
+
+
+@pytest.mark.parametrize("dt", ALL)
+def test_reparameterise_without_mu_output(dt):
+    """mu_out = NULL: z alone"""
+    _reparam_case(DTYPES[dt], 3, 4, with_mu=False)
+
+
+def _head_tail_case(dtype, B, K):
+    case = kcases.head_tail(B, K, dtype)
+    i = case.inputs
+    out = torch.full((B + 1, 2), SENT, dtype=torch.float32, device=dev())
+    kutil.call("gcv_k_head_tail", _lib.dtype_code(dtype), ptr(D(i["h"], dtype)), ptr(D(i["w"])), ptr(D(i["b"])),
+               ptr(out), B, K)
+    assert (out[B] == SENT).all(), "written behind row B"
+    case.assert_close(out[:B])
 
 
 @pytest.mark.parametrize("dt", ALL)
 def test_head_tail(dt):
-    dtype = DTYPES[dt]
-    B, K = 9, 500
-    h = q(rnd((B, K), 1), dtype)
-    w, b = rnd((2, K), 2, 0.05), rnd((2,), 3, 0.1)
-    out = torch.zeros((B, 2), dtype=torch.float32, device=dev())
-    kutil.call("gcv_k_head_tail", _lib.dtype_code(dtype), ptr(D(h, dtype)), ptr(D(w)), ptr(D(b)),
-               ptr(out), B, K)
-    assert_close(out, h @ w.t() + b, 1e-5, "head tail")
+    _head_tail_case(DTYPES[dt], 9, 500)       # 9 rows: a third workgroup with one live wave
+
+
+@pytest.mark.parametrize("dt", ALL)
+@pytest.mark.parametrize("B,K", [(1, 500), (6, 64)])       # K = 64: one trip of the lane-stride loop
+def test_head_tail_one_row_and_one_trip(dt, B, K):
+    _head_tail_case(DTYPES[dt], B, K)
+
+
+def _head_splitk_case(dtype, B, K, S, act):
+    """The head as the networks run it: fc's split-K partials summed, + bias, ReLU (vae) / exact GELU (ed), rounded to the
+    storage dtype, then fc2 (model/genconvit_ed.py:87, model/genconvit_vae.py:114).  In 16-bit storage the bound of a row
+    allows for its hidden units next to a rounding tie (kcases.head_tail_splitk)."""
+    case = kcases.head_tail_splitk(B, K, S, act, dtype)
+    i = case.inputs
+    out = torch.full((B + 1, 2), SENT, dtype=torch.float32, device=dev())
+    kutil.call("gcv_k_head_tail_splitk", _lib.dtype_code(dtype), ptr(D(i["part"])), S, ptr(D(i["b1"])), act, ptr(D(i["w"])),
+               ptr(D(i["b"])), ptr(out), B, K)
+    assert (out[B] == SENT).all(), "written behind row B"
+    case.assert_close(out[:B])
 
 
 @pytest.mark.parametrize("dt", ALL)
 @pytest.mark.parametrize("act", [1, 2])
 def test_head_tail_with_splitk_reduce(dt, act):
-    """The head as the networks run it: fc's split-K partials summed, + bias, ReLU (vae) / exact GELU (ed), rounded to the
-    storage dtype, then fc2 (model/genconvit_ed.py:87, model/genconvit_vae.py:114)."""
-    dtype = DTYPES[dt]
-    B, K, S = 37, 500, 8
-    part = rnd((S, B, K), 1, 0.5)
-    b1 = rnd((K,), 2, 0.1)
-    w, b = rnd((2, K), 3, 0.05), rnd((2,), 4, 0.1)
-    h = q(act_ref(part.sum(0) + b1, act), dtype)
-    out = torch.zeros((B, 2), dtype=torch.float32, device=dev())
-    kutil.call("gcv_k_head_tail_splitk", _lib.dtype_code(dtype), ptr(D(part)), S, ptr(D(b1)), act, ptr(D(w)), ptr(D(b)),
-               ptr(out), B, K)
-    # (a hidden value that sits on a rounding boundary of the storage dtype may round the other way: one ulp of h times w)
-    assert_close(out, h @ w.t() + b, {torch.float32: 1e-5, torch.float16: 2e-4, torch.bfloat16: 2e-3}[dtype], "head tail split-K")
+    _head_splitk_case(DTYPES[dt], 37, 500, 8, act)
+
+
+@pytest.mark.parametrize("dt", ALL)
+@pytest.mark.parametrize("act", [1, 2])
+@pytest.mark.parametrize("B,K,S", [(1, 500, 1), (5, 300, 3)])
+def test_head_tail_with_splitk_reduce_one_slab_and_short_rows(dt, act, B, K, S):
+    """one row of one slab; K = 300: the second trip of the thread-stride loop has 44 live threads"""
+    _head_splitk_case(DTYPES[dt], B, K, S, act)
 
 
 @pytest.mark.parametrize("dt", ALL)
 def test_bilinear_resize_and_mse(dt):
-    """transforms.Resize((224,224)) of x_hat (genconvit_vae.py:116) + per-frame MSE (train/train_vae.py:24)."""
+    """transforms.Resize((224,224)) of x_hat (genconvit_vae.py:116) + per-frame MSE (train/train_vae.py:24): the three ways
+    the launcher is called.  Both outputs, msepart compared block by block; no recon; no mse, where msepart must stay
+    untouched."""
     dtype = DTYPES[dt]
     B = 2
-    xhat = q(rnd((B, 3, 112, 112), 1, 2.0), dtype)
-    img = q(rnd((B, 3, 224, 224), 2, 2.0), dtype)
-    want = F.interpolate(xhat, size=(224, 224), mode="bilinear", align_corners=False, antialias=True)
-    recon = torch.zeros((B, 3, 224, 224), dtype=dtype, device=dev())
-    msepart = torch.zeros((B, 196), dtype=torch.float32, device=dev())
-    mse = torch.zeros((B,), dtype=torch.float32, device=dev())
-    kutil.call("gcv_k_resize_mse", _lib.dtype_code(dtype), ptr(D(xhat.permute(0, 2, 3, 1).contiguous(), dtype)),
-               ptr(D(img, dtype)), ptr(recon), ptr(msepart), ptr(mse), B)
-    assert_close(recon, want, tol(dtype, 3.0), "resize")
-    want_mse = ((want - img) ** 2).flatten(1).mean(1)
-    assert_close(mse, want_mse, 1e-4 * float(want_mse.max()), "mse")
+    case = kcases.resize_mse(B, dtype)
+    xhat, img = D(case.inputs["xhat"].permute(0, 2, 3, 1).contiguous(), dtype), D(case.inputs["img"], dtype)
+
+    def launch(with_recon, with_mse):
+        recon = torch.full((B + 1, 3, 224, 224), SENT, dtype=dtype, device=dev()) if with_recon else None
+        msepart = torch.full((B + 1, 196), SENT, dtype=torch.float32, device=dev())
+        mse = torch.full((B + 1,), SENT, dtype=torch.float32, device=dev()) if with_mse else None
+        kutil.call("gcv_k_resize_mse", _lib.dtype_code(dtype), ptr(xhat), ptr(img), ptr(recon), ptr(msepart), ptr(mse), B)
+        assert recon is None or (recon[B].float() == SENT).all(), "recon written behind frame B"
+        assert (msepart[B] == SENT).all() and (mse is None or mse[B] == SENT), "msepart / mse written behind frame B"
+        return recon, msepart, mse
+
+    recon, msepart, mse = launch(True, True)
+    case.assert_close({"recon": recon[:B], "msepart": msepart[:B], "mse": mse[:B]})
+    _, msepart, mse = launch(False, True)
+    case.assert_close({"msepart": msepart[:B], "mse": mse[:B]})
+    recon, msepart, _ = launch(True, False)
+    assert (msepart == SENT).all(), "msepart written by a launch without mse"
+    case.assert_close({"recon": recon[:B]})
+
+
 
 
 def test_vote_sigmoid_mean():
