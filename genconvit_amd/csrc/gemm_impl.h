@@ -1,6 +1,7 @@
 // Tile-config selection + launch for gemm_kernel (included by gemm_{f32,f16,bf16}.hip).
 #pragma once
 #include "gemm.h"
+#include "conv_direct.h"
 #include "gemm_glds_impl.h"
 
 namespace gcv {
@@ -113,6 +114,8 @@ template <typename T> int launch_gemm(const GemmArgs& g, int a_mode, int epi, hi
   }
   if (a_mode == A_IM2COL3_POOL && epi == EPI_POOL4) {
     GCV_REQUIRE(g.act == ACT_RELU, "conv3x3+pool is built for ReLU");
+    // 16-bit storage, 16 / 32 input channels, N = 32 / 64: both MFMA operands straight from memory (conv_direct.h)
+    if (conv_direct_applicable<T>(g, a_mode, epi)) return launch_conv_direct<T>(g, a_mode, s);
     // K = 144 / 288 (16 / 32 input channels): 32-deep K tiles instead of a 64-deep one that is three quarters / half padding
     // (round 4, paired runs on one box: ed.enc 0.200 -> 0.171 ms, vae.enc 0.077 -> 0.068 ms per step)
     if (short_k && GCV_IM2COL_SHORTK) {
@@ -125,6 +128,7 @@ template <typename T> int launch_gemm(const GemmArgs& g, int a_mode, int epi, hi
   }
   if (a_mode == A_IM2COL3_S2 && epi == EPI_BIAS_ACT) {
     GCV_REQUIRE(g.act == ACT_LEAKY, "conv3x3 stride 2 is built for LeakyReLU");
+    if (conv_direct_applicable<T>(g, a_mode, epi)) return launch_conv_direct<T>(g, a_mode, s);
     if (short_k && GCV_IM2COL_SHORTK) {
       if (g.N <= 32) return launch_cfg<T, 128, 32, 32, 32, 64, A_IM2COL3_S2, EPI_BIAS_ACT, ACT_LEAKY>(g, s);
       if (g.N <= 64) return launch_cfg<T, 128, 64, 32, 64, 64, A_IM2COL3_S2, EPI_BIAS_ACT, ACT_LEAKY>(g, s);
