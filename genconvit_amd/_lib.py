@@ -83,6 +83,7 @@ SIGNATURES = {
     "gcv_frame_cells": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gcv_blend_fit": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gcv_hist_diff_lag": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gcv_face_quality": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "gcv_vote_segments": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "gcv_vote_windows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "gcv_tap_set": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t]),
@@ -667,6 +668,46 @@ def track_match(frames_u8, jobs, grid=64, radius=16):
     check(lib.gcv_track_match(frames_u8.data_ptr(), nf, h, w, jd.data_ptr(), n, grid, radius, out.data_ptr(),
                               current_stream_ptr(frames_u8.device)), "gcv_track_match")
     return out
+
+
+def face_quality(frames_u8, boxes, grid=64):
+    """Is a face crop usable (``gcv_face_quality``, include/genconvit_hip.h: the arithmetic is stated there): sums over a
+    ``grid`` x ``grid`` lattice of mean-luma cells of every box, all boxes in one launch.  ``frames_u8``: (F,H,W,3) uint8
+    device tensor (RGB); a slice such as ``frames[1:]`` is used in place, whatever its alignment.  ``boxes``: (n,5) integers
+    (frame index, top, right, bottom, left).  Returns (n,8) int64 on the device: (G, S1, S2, L2, GX, GY, dark, bright) — the
+    sum and the sum of squares of the cells, the energy of their Laplacian and of their differences along the rows and
+    down the columns, and the number of cells below 16 and above 239.  A ``grid`` other than 16, 32, 64, a box outside its
+    frame and a box lower or narrower than ``grid`` are errors here, before anything is launched (the zeros row is the C
+    entry's guard); none give an empty tensor."""
+    import torch
+    lib = load()
+    grid = int(grid)
+    if grid not in TRACK_GRIDS:
+        raise GenConViTHipError(f"face_quality: grid {grid}; accepted values are 16, 32 and 64")
+    if not (torch.is_tensor(frames_u8) and frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4
+            and frames_u8.shape[3] == 3):
+        raise GenConViTHipError("face_quality expects a uint8 device tensor of shape (F,H,W,3)")
+    frames_u8 = frames_u8.contiguous()
+    nf, h, w, _ = frames_u8.shape
+    b = _check_quality_boxes("face_quality", boxes, nf, h, w, grid)
+    n = b.shape[0]
+    out = torch.empty((n, 8), dtype=torch.int64, device=frames_u8.device)
+    if n == 0:
+        return out
+    bd = b.contiguous().to(frames_u8.device)
+    check(lib.gcv_face_quality(frames_u8.data_ptr(), nf, h, w, bd.data_ptr(), n, grid, out.data_ptr(),
+                               current_stream_ptr(frames_u8.device)), "gcv_face_quality")
+    return out
+
+
+def _check_quality_boxes(what, boxes, nf, h, w, grid):
+    """``_check_boxes``, and a box lower or narrower than ``grid`` is an error too."""
+    b = _check_boxes(what, boxes, nf, h, w)
+    if b.numel():
+        small = ((b[:, 3] - b[:, 1]) < grid) | ((b[:, 2] - b[:, 4]) < grid)
+        if bool(small.any()):
+            raise GenConViTHipError(f"{what}: box {int(small.nonzero()[0])} is smaller than grid = {grid} a side")
+    return b
 
 
 CUT_REGIONS, CUT_BINS = (1, 2, 4, 8), 64

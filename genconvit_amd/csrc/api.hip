@@ -778,6 +778,12 @@ int gcv_blend_fit(const uint32_t* cells_u32, int nframes, int grid, int lag, int
   return launch_blend_fit(cells_u32, nframes, grid, lag, fit_i64, (hipStream_t)s);
 }
 
+int gcv_face_quality(const void* frames_u8_nhwc, int nframes, int H, int W, const int* boxes5, int n, int grid,
+                     int64_t* out8, gcv_stream s) {
+  GCV_REQUIRE(n <= 0 || (frames_u8_nhwc && boxes5 && out8), "face quality: null pointer");
+  return launch_face_quality((const unsigned char*)frames_u8_nhwc, nframes, H, W, boxes5, n, grid, out8, (hipStream_t)s);
+}
+
 int gcv_k_fused_mlp(int dtype, int C, const void* x, const void* w1, const float* b1, const float* w2_f32,
                     const float* b2, const float* gamma, const void* resid, void* out, int M, gcv_stream s) {
   GCV_REQUIRE(dtype == GCV_F16 || dtype == GCV_BF16, "the MLP kernels are built for 16-bit storage");

@@ -20,6 +20,7 @@
 #include <cstdint>
 
 #include "common.h"
+#include "luma_cells.h"                                   // TmBox, tm_box_ok, tm_cell
 
 namespace gcv {
 
@@ -27,25 +28,6 @@ constexpr int TM_THREADS = 256;
 constexpr int TM_RMAX = 32;
 
 struct alignas(4) TmOut { int v[4]; };
-
-struct TmBox { int f, top, right, bottom, left; };
-
-__device__ __forceinline__ bool tm_box_ok(const TmBox& b, int nframes, int H, int W, int G) {
-  return b.f >= 0 && b.f < nframes && b.top >= 0 && b.left >= 0 && b.bottom <= H && b.right <= W && b.top <= b.bottom &&
-         b.left <= b.right && b.bottom - b.top >= G && b.right - b.left >= G;
-}
-
-// (sum of Y over rows [y0, y1) x columns [x0, x1) + cnt / 2) / cnt with Y = (77 R + 150 G + 29 B + 128) >> 8
-__device__ __forceinline__ unsigned tm_cell(const unsigned char* __restrict__ frame, int64_t rs, int y0, int y1, int x0,
-                                            int x1) {
-  unsigned sum = 0;
-  for (int y = y0; y < y1; ++y) {
-    const unsigned char* p = frame + (int64_t)y * rs + (int64_t)x0 * 3;
-    for (int x = x0; x < x1; ++x, p += 3) sum += (77u * p[0] + 150u * p[1] + 29u * p[2] + 128u) >> 8;
-  }
-  const unsigned cnt = (unsigned)(y1 - y0) * (unsigned)(x1 - x0);
-  return (sum + cnt / 2u) / cnt;
-}
 
 template <int G>
 __global__ void __launch_bounds__(TM_THREADS) track_match_kernel(const unsigned char* __restrict__ frames, int nframes,

@@ -89,6 +89,10 @@ int launch_hist_diff(const uint32_t* hist, int nframes, int regions, uint32_t* d
 int launch_hist_diff_lag(const uint32_t* hist, int nframes, int regions, int lag, uint32_t* dist, hipStream_t s);
 int launch_frame_cells(const unsigned char* frames, int nframes, int H, int W, int grid, uint32_t* cells, hipStream_t s);
 int launch_blend_fit(const uint32_t* cells, int nframes, int grid, int lag, int64_t* fit, hipStream_t s);
+// quality.hip: sharpness, gradient and exposure sums of n face boxes on a grid x grid lattice of mean-luma cells ->
+// n rows (G, S1, S2, L2, GX, GY, dark, bright)
+int launch_face_quality(const unsigned char* frames, int nframes, int H, int W, const int* boxes5, int n, int grid,
+                        int64_t* out8, hipStream_t s);
 int launch_kl(const float* partial, int splitk, const float* bias, const float* mu, float* rowsum, float* kl, int B,
               int N, hipStream_t s);
 int launch_vote(const float* logits, int rows, float* mean2, hipStream_t s);

@@ -531,6 +531,116 @@ def shot_transitions(frames, lags=(4, 8), grid=16, regions=4, h_min=0.25, rho_ma
     return _transitions_of(hist, cells, nf, h, w, regions, lags, h_min, rho_max, a_lo, a_hi, slack)
 
 
+QUALITY_DEFAULTS = dict(grid=64, sharp_rel=0.5, sharp_min=0.0, clip_max=0.5)
+
+
+def _check_quality(what, grid=64, sharp_rel=0.5, sharp_min=0.0, clip_max=0.5):
+    if isinstance(grid, bool) or not isinstance(grid, (int, np.integer)) or grid not in _lib.TRACK_GRIDS:
+        raise ValueError(f"{what}: grid {grid} must be 16, 32 or 64")
+    number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v)
+    if not (all(number(v) for v in (sharp_rel, sharp_min, clip_max)) and 0.0 <= sharp_rel <= 1.0 and sharp_min >= 0.0
+            and 0.0 < clip_max <= 1.0):
+        raise ValueError(f"{what}: sharp_rel {sharp_rel} must lie in [0, 1], sharp_min {sharp_min} be at least 0 and clip_max "
+                         f"{clip_max} lie in (0, 1]")
+
+
+def face_quality(frames, boxes, grid=64, max_frames=128, dev=None):
+    """How usable is each face crop.  A face smeared by motion or defocus, blown out by a flash or lost in the dark still
+    gets a crop and a score, and the score is noise at best.  Every box is measured on its own ``grid`` x ``grid`` lattice
+    of mean-luma cells c[u][v] (``_lib.face_quality``, G = 16, 32 or 64; include/genconvit_hip.h states the integer
+    arithmetic): L2, the sum of squares of the cells' discrete Laplacian over the interior, which blur removes first; GX
+    and GY, the sums of squared differences along the rows and down the columns, whose ratio tells the direction of a
+    motion blur; the sum and the sum of squares of the cells; and the numbers of cells below 16 and above 239.
+    ``frames``: uint8 (F,H,W,3) RGB, numpy or a tensor.  Frames on the GPU are used in place, all boxes in one launch.  Of
+    host frames the boxes go in frame order in groups launched one after another, a group being a run of boxes that lie
+    on at most ``max_frames`` (>= 1) distinct frames: only those are uploaded (to ``dev``, by default this module's
+    ``device``), so device memory is bounded by the group, not the video.  ``boxes``: rows (frame, top, right, bottom, left)
+    inside their frames.  A box lower or narrower than ``grid`` pixels is not sent: it comes back unmeasured.
+    Returns a dict of numpy arrays in the order of ``boxes``:
+      raw          (n,8) int64 rows (G, S1, S2, L2, GX, GY, dark, bright); zeros where not measured
+      measured     bool
+      sharpness    L2 / (G - 2)^2, the mean squared Laplacian of an interior cell
+      gx, gy       GX / (G (G - 1)) and GY / (G (G - 1)), the mean squared difference between neighbours in a row, in a column
+      mean         S1 / G^2
+      contrast     S2 / G^2 - mean^2, the variance of the cells
+      dark, bright the fractions of the G^2 cells below 16 and above 239
+    all float64 but the first two, and NaN where ``measured`` is false.  No box: empty arrays, nothing is launched.
+    What the grid cannot see: blur finer than a cell (box side / G pixels) is invisible, so ``grid`` should follow the face
+    size.  On the CPU restatement of the arithmetic, a 9-pixel box blur of a texture with 4-pixel features lowers L2 of
+    a 200-pixel face about 30-fold at G = 64 (a cell is 3 pixels) and about 2-fold at G = 16 (a cell is 12:
+    tests/test_quality_cpu.py).  Nothing here judges: the
+    thresholds are ``quality_keep``'s, and the caller's to choose."""
+    _check_quality("face_quality", grid=grid)
+    if max_frames < 1:
+        raise ValueError(f"face_quality: max_frames {max_frames} must be at least 1")
+    fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
+    if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
+        raise _lib.GenConViTHipError("face_quality: frames must be uint8 of shape (F,H,W,3)")
+    grid = int(grid)
+    rows = [tuple(int(v) for v in b) for b in boxes]
+    _lib._check_boxes("face_quality", rows, *fr.shape[:3])
+    n = len(rows)
+    raw = np.zeros((n, 8), dtype=np.int64)
+    big = [i for i, b in enumerate(rows) if b[3] - b[1] >= grid and b[2] - b[4] >= grid]
+    if big and fr.is_cuda:
+        raw[big] = _lib.face_quality(fr, [rows[i] for i in big], grid=grid).cpu().numpy()
+    elif big:
+        groups, used = [], set()
+        for i in sorted(big, key=lambda i: (rows[i][0], i)):
+            if not groups or len(used | {rows[i][0]}) > max_frames:
+                groups.append([])
+                used = set()
+            groups[-1].append(i)
+            used.add(rows[i][0])
+        for ids in groups:
+            used = sorted({rows[i][0] for i in ids})
+            at = {f: k for k, f in enumerate(used)}
+            slab = fr.index_select(0, torch.as_tensor(used)).to(dev or device)
+            raw[ids] = _lib.face_quality(slab, [(at[rows[i][0]], *rows[i][1:]) for i in ids], grid=grid).cpu().numpy()
+    measured = np.zeros(n, dtype=bool)
+    measured[big] = True
+    g = float(grid)
+    value = lambda v: np.where(measured, v, np.nan)
+    s1, s2, l2, gx, gy, dark, bright = (raw[:, k].astype(np.float64) for k in range(1, 8))
+    mean = s1 / (g * g)
+    return {"raw": raw, "measured": measured, "sharpness": value(l2 / ((g - 2) * (g - 2))),
+            "gx": value(gx / (g * (g - 1))), "gy": value(gy / (g * (g - 1))), "mean": value(mean),
+            "contrast": value(s2 / (g * g) - mean * mean), "dark": value(dark / (g * g)), "bright": value(bright / (g * g))}
+
+
+def quality_keep(quality, track_offsets, sharp_rel=0.5, sharp_min=0.0, clip_max=0.5):
+    """Which rows of ``face_quality``'s result are fit to be scored: a bool array, True = keep.  ``quality``: that dict, over
+    the rows of all tracks concatenated; ``track_offsets``: track t owns the rows [track_offsets[t], track_offsets[t + 1]),
+    from 0 to the number of rows.  A measured row is dropped when any of these holds:
+      sharpness < ``sharp_rel`` x the median sharpness of the measured rows of its track (``numpy.median``: the mean of the
+                  two middle values of an even count) — the track's own median cancels the person, the lighting and the
+                  face size, which set the absolute level;
+      sharpness < ``sharp_min``, an absolute floor (0 by default: off);
+      dark > ``clip_max`` or bright > ``clip_max``: more than that fraction of the cells is below 16, or above 239.
+    Unmeasured rows (a face smaller than the grid) are kept: nothing is known against them.  ``sharp_rel`` outside [0, 1], a
+    negative ``sharp_min``, ``clip_max`` outside (0, 1] and offsets that do not cover the rows are a ValueError.
+    The three defaults are starting values from synthetic material (a noise texture with 4-pixel features, box blurs of 9
+    and 15 pixels, flat, black and white patches); no accuracy on real footage is claimed — the numbers are in ``quality``:
+    look at them and choose."""
+    _check_quality("quality_keep", sharp_rel=sharp_rel, sharp_min=sharp_min, clip_max=clip_max)
+    measured = np.asarray(quality["measured"], dtype=bool)
+    sharp, dark, bright = (np.asarray(quality[k], dtype=np.float64) for k in ("sharpness", "dark", "bright"))
+    offs = [int(v) for v in track_offsets]
+    n = len(measured)
+    if not (len(offs) >= 1 and offs[0] == 0 and offs[-1] == n and all(a <= b for a, b in zip(offs, offs[1:]))):
+        raise ValueError(f"quality_keep: track_offsets must rise from 0 to the {n} rows of quality")
+    keep = np.ones(n, dtype=bool)
+    for lo, hi in zip(offs, offs[1:]):
+        m = measured[lo:hi]
+        if not m.any():
+            continue
+        s = np.where(m, sharp[lo:hi], 0.0)
+        bad = (s < sharp_rel * np.median(s[m])) | (s < sharp_min) | (np.where(m, dark[lo:hi], 0.0) > clip_max) | \
+              (np.where(m, bright[lo:hi], 0.0) > clip_max)
+        keep[lo:hi] = ~(m & bad)
+    return keep
+
+
 def _verdict(m):
     """(y, y_val) of a mean pair, as ``max_prediction_value`` / ``pred_vids`` compute it."""
     return int(torch.argmax(m).item()), m[0].item() if m[0] > m[1] else abs(1 - m[1]).item()
@@ -538,7 +648,7 @@ def _verdict(m):
 
 def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3, window=15, stride=1, max_batch=128,
                 eps=None, follow=False, follow_grid=64, follow_radius=16, cuts=None, cut_threshold=0.4, cut_regions=4,
-                transitions=None, transition_args=None):
+                transitions=None, transition_args=None, quality=None, quality_args=None):
     """When is a video fake, and whose face: every face of every frame is scored, linked into per-person tracks, and voted
     over sliding windows of each track.  ``frames``: uint8 (F,H,W,3) RGB, numpy or a tensor on either device.  ``boxes``:
     rows (frame, top, right, bottom, left); by default the detector — ``locate``, else ``face_locations(..., keep_all=True)``
@@ -592,10 +702,33 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
     across a transition.  The result gains ``transitions`` (sorted), and ``transition_info`` (``shot_transitions``'s
     ``info``) when they were computed here; ``cuts`` keeps holding the hard cuts alone.  Linear blends of at least 3
     frames only: eased dissolves and wipes are not found, a fast pan can pass for one, and the thresholds are starting
-    values, not tuned ones."""
+    values, not tuned ones.
+    ``quality`` (``None`` by default: nothing changes): faces that are themselves unusable — smeared by a head turn, out of
+    focus, blown out by a flash, lost in the dark — get a crop, a score and a full vote like any other, and blur is what a
+    blended face looks like.  ``True``: after tracking, and after ``follow`` so that the final boxes are the ones measured,
+    ``face_quality(frames, rows, grid, max_frames=max_batch, dev=the model's device)`` measures every row and
+    ``quality_keep`` says which stay (``quality_args``: a dict with keys among ``grid``, ``sharp_rel``, ``sharp_min``,
+    ``clip_max``; None: their defaults; anything else is a ValueError, raised before anything runs).  The dropped rows
+    leave their tracks before anything is cropped: they are not cut, scored or voted, and ``eps`` counts the crops that
+    remain; a track that loses every row is removed, and a track that loses rows in its middle keeps one window over the
+    hole.  ``tracks``, ``boxes``, ``track_offsets`` and everything after them describe the kept rows, and the result gains
+    ``quality``: ``face_quality``'s dict over the rows before the gate, plus ``kept`` (bool per such row), ``boxes`` (those
+    rows) and ``track_map`` (for each remaining track, its number before the gate).  The track column of ``follow`` counts
+    the tracks before the gate.  With no face nothing is launched.  Host frames on which a measured box lies are uploaded
+    a second time for this pass: the upload is not shared with the crops'.  The thresholds are starting values from
+    synthetic material, not tuned ones, and blur finer than a cell of the grid is not seen."""
     fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
     if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
         raise _lib.GenConViTHipError("scan_frames: frames must be uint8 of shape (F,H,W,3)")
+    if quality is not None and not isinstance(quality, bool):
+        raise ValueError(f"scan_frames: quality {quality!r} must be None or True")
+    qargs = dict(QUALITY_DEFAULTS)
+    if quality:
+        if quality_args is not None:
+            if not (isinstance(quality_args, dict) and set(quality_args) <= set(qargs)):
+                raise ValueError(f"scan_frames: quality_args must be a dict with keys among {sorted(qargs)}")
+            qargs.update(quality_args)
+        _check_quality("scan_frames", **qargs)
     targs = dict(TRANSITION_DEFAULTS)
     if transitions is True:
         if transition_args is not None:
@@ -652,6 +785,15 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
                                       max_frames=max(max_batch, 3), dev=p.device)
     else:
         tracks = track_boxes(boxes, iou=iou, max_gap=detect_every, cuts=ends)
+    measures = None
+    if quality:
+        before = [b for tr in tracks for b in tr]
+        measures = face_quality(fr, before, grid=qargs.pop("grid"), max_frames=max_batch, dev=p.device)
+        kept = quality_keep(measures, np.cumsum([0] + [len(tr) for tr in tracks]), **qargs)
+        left = iter(kept.tolist())
+        tracks = [[b for b in tr if next(left)] for tr in tracks]
+        measures.update(kept=kept, boxes=before, track_map=[t for t, tr in enumerate(tracks) if tr])
+        tracks = [tr for tr in tracks if tr]
     rows = [b for tr in tracks for b in tr]
     offsets = [0] + [int(v) for v in np.cumsum([len(tr) for tr in tracks])]
     n = len(rows)
@@ -667,6 +809,8 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
         res["transitions"] = transitions
         if transition_info is not None:
             res["transition_info"] = transition_info
+    if measures is not None:
+        res["quality"] = measures
     if n == 0:
         res["frame_scores"] = torch.empty((0, 2), dtype=torch.float32, device=p.device)
         res["window_means"] = torch.empty((0, 2), dtype=torch.float32, device=p.device)

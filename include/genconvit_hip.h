@@ -334,6 +334,44 @@ int gcv_frame_cells(const void* frames_u8_nhwc, int nframes, int H, int W, int g
 int gcv_blend_fit(const uint32_t* cells_u32, int nframes, int grid, int lag, int64_t* fit_i64, gcv_stream stream);
 int gcv_hist_diff_lag(const uint32_t* hist_u32, int nframes, int regions, int lag, uint32_t* dist_u32, gcv_stream stream);
 
+/* Is a face crop usable: sharpness, gradient and exposure sums of n face boxes in one launch.  A whole-video scan scores
+ * every face of every frame; a face smeared by motion or defocus, blown out by a flash or lost in the dark still gets a
+ * crop, a score and a vote.  pred_func.face_quality turns the sums into per-box measures and pred_func.quality_keep into
+ * the rows a scan drops: the policy stays in Python, the numbers are returned.
+ *   frames  (nframes,H,W,3) uint8 RGB on the device, as for gcv_face_crop_resize; the pointer may have any alignment, and
+ *           no byte outside [frames, frames + nframes H W 3) is read
+ *   boxes5  int32 device array of n rows (frame, top, right, bottom, left), as for gcv_face_crop_resize
+ *   grid    G: 16, 32 or 64 cells a side
+ *   out8    (n,8) int64: (G, S1, S2, L2, GX, GY, dark, bright)
+ * Arithmetic (fixed and all-integer, so that a CPU restatement is bit-equal: tests/qualityutil.py); a // b is floor
+ * division.  Luma, cell edges and cell value are gcv_track_match's, with h = bottom - top and w = right - left:
+ *   luma of a pixel   Y = (77 R + 150 G + 29 B + 128) >> 8
+ *   cell edges        e_h(u) = (u h) // G; cell (u, v), u, v in [0, G), covers the rows [top + e_h(u), top + e_h(u + 1)) and
+ *                     the columns [left + e_w(v), left + e_w(v + 1)): the cells tile the box exactly
+ *   precondition      h >= G and w >= G, so that no cell is empty
+ *   cell value        c[u][v] = (sum of Y over the cell's pixel rectangle + cnt // 2) // cnt, cnt the rectangle's pixels:
+ *                     0 ... 255
+ *   S1                sum over all cells of c                                          <= 255 G^2 <= 1.1e6
+ *   S2                sum over all cells of c^2                                        <= 255^2 G^2 <= 2.7e8
+ *   L2                sum over the interior u, v in [1, G - 1) of
+ *                     (4 c[u][v] - c[u-1][v] - c[u+1][v] - c[u][v-1] - c[u][v+1])^2    <= 62^2 1020^2 ~ 4.0e9: past a signed
+ *                     32 bits, hence int64 outputs; 16 terms (a lane's, at G = 64) stay below 2^24, a wave's below 2^31
+ *   GX                sum over u in [0, G), v in [0, G - 1) of (c[u][v+1] - c[u][v])^2   <= 255^2 G (G - 1) <= 2.7e8
+ *   GY                sum over u in [0, G - 1), v in [0, G) of (c[u+1][v] - c[u][v])^2   <= 2.7e8
+ *   dark, bright      the number of cells with c < 16, and with c > 239
+ * L2 is the energy of the discrete Laplacian, which blur removes first; GX against GY tells the direction of a motion blur
+ * (a horizontal smear lowers GX, the differences along a row, and leaves GY).  All of it is relative to the cell: blur
+ * finer than a cell (h / G by w / G pixels) is invisible, so the grid should follow the face size.
+ * A bad row — a frame index out of range, a box outside the frame, h or w below G — reads nothing and gives eight zeros:
+ * out[0] == 0 marks it (a good row has out[0] == G).  The Python binding refuses such rows instead.
+ * Refused before anything is launched (gcv_last_error() says why): grid not 16, 32 or 64; nframes, H or W not positive;
+ * H W > 2^30 (a cell's sum is 32 bits); a null pointer with n > 0.  n == 0 launches nothing and writes nothing.
+ * One launch, one workgroup of 256 threads per box; the call allocates, copies and synchronises nothing.
+ * Not done here: any judgement (thresholds are the caller's), blur finer than a cell, a per-box choice of the grid, colour
+ * casts and compression artefacts. */
+int gcv_face_quality(const void* frames_u8_nhwc, int nframes, int H, int W, const int* boxes5, int n, int grid,
+                     int64_t* out8, gcv_stream stream);
+
 /* pred_vid's reduction (model/pred_func.py:120,125): mean2[c] = mean_r sigmoid(logits[r][c]). */
 int gcv_vote(const float* logits, int rows, float* mean2, gcv_stream stream);
 
