@@ -84,6 +84,8 @@ SIGNATURES = {
     "gcv_blend_fit": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gcv_hist_diff_lag": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gcv_face_quality": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "gcv_face_signature": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "gcv_sig_link": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "gcv_vote_segments": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "gcv_vote_windows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "gcv_tap_set": (c_int, [c_void_p, c_char_p, c_void_p, c_size_t]),
@@ -708,6 +710,82 @@ def _check_quality_boxes(what, boxes, nf, h, w, grid):
         if bool(small.any()):
             raise GenConViTHipError(f"{what}: box {int(small.nonzero()[0])} is smaller than grid = {grid} a side")
     return b
+
+
+SIG_GRID, SIG_BYTES, SIG_MAX_ROWS, SIG_MAX_TRACKS, SIG_NONE = 16, 384, 65536, 4096, 0xFFFFFFFF
+
+
+def face_signature(frames_u8, boxes):
+    """What does a face crop look like (``gcv_face_signature``, include/genconvit_hip.h: the arithmetic is stated there): per
+    box 384 bytes — the mean-luma cells of a 16 x 16 grid with the box's own mean and spread taken out, then Cb and Cr on
+    an 8 x 8 grid — all boxes in one launch.  ``frames_u8``: (F,H,W,3) uint8 device tensor (RGB); a slice such as
+    ``frames[1:]`` is used in place, whatever its alignment.  ``boxes``: (n,5) integers (frame index, top, right, bottom,
+    left).  Returns (n,384) uint8 on the device.  A box outside its frame and a box lower or narrower than 16 pixels are
+    errors here, before anything is launched (the zeros row is the C entry's guard); none give an empty tensor."""
+    import torch
+    lib = load()
+    if not (torch.is_tensor(frames_u8) and frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4
+            and frames_u8.shape[3] == 3):
+        raise GenConViTHipError("face_signature expects a uint8 device tensor of shape (F,H,W,3)")
+    frames_u8 = frames_u8.contiguous()
+    nf, h, w, _ = frames_u8.shape
+    b = _check_quality_boxes("face_signature", boxes, nf, h, w, SIG_GRID)
+    n = b.shape[0]
+    out = torch.empty((n, SIG_BYTES), dtype=torch.uint8, device=frames_u8.device)
+    if n == 0:
+        return out
+    bd = b.contiguous().to(frames_u8.device)
+    check(lib.gcv_face_signature(frames_u8.data_ptr(), nf, h, w, bd.data_ptr(), n, out.data_ptr(),
+                                 current_stream_ptr(frames_u8.device)), "gcv_face_signature")
+    return out
+
+
+def _check_sig_link(what, sig, owner, tracks):
+    """``owner`` as an (n,) int32 host tensor and ``tracks`` as an int; the shapes, the limits of ``gcv_sig_link`` and an
+    owner outside [-1, tracks) are errors."""
+    import torch
+    if not (torch.is_tensor(sig) and sig.dtype == torch.uint8 and sig.dim() == 2 and sig.shape[1] == SIG_BYTES):
+        raise GenConViTHipError(f"{what} expects the signatures as a uint8 tensor of shape (n,{SIG_BYTES})")
+    if isinstance(tracks, bool) or int(tracks) != tracks or not 0 <= int(tracks) <= SIG_MAX_TRACKS:
+        raise GenConViTHipError(f"{what}: tracks {tracks} outside 0 ... {SIG_MAX_TRACKS}")
+    tracks = int(tracks)
+    o = torch.as_tensor(owner, dtype=torch.int32).reshape(-1).cpu()
+    n = sig.shape[0]
+    if o.numel() != n:
+        raise GenConViTHipError(f"{what}: {o.numel()} owners for {n} signatures")
+    if n > SIG_MAX_ROWS:
+        raise GenConViTHipError(f"{what}: {n} signatures; at most {SIG_MAX_ROWS} go into one call")
+    if n and not bool(((o >= -1) & (o < tracks)).all()):
+        bad = int(((o < -1) | (o >= tracks)).nonzero()[0])
+        raise GenConViTHipError(f"{what}: owner {int(o[bad])} of row {bad} is neither -1 nor a track in [0, {tracks})")
+    return o, tracks
+
+
+def sig_link(sig, owner, tracks):
+    """How alike are two tracks at their best (``gcv_sig_link``, include/genconvit_hip.h): ``out[a][b]``, a != b, is the
+    smallest L1 distance between a signature of track a and one of track b, over all such pairs of rows.  ``sig``: (n,384)
+    uint8 device tensor (``face_signature``); ``owner``: n integers, the track of each row in [0, ``tracks``) or -1 for a
+    row that takes no part, in any order; ``tracks``: T.  Returns (T,T) int64 on the device — torch has no arithmetic on
+    uint32, and int64 holds the C entry's 0xFFFFFFFF (``SIG_NONE``: the diagonal, and every pair one of whose tracks has no
+    row) as itself; every other value is at most 384 * 255 = 97 920.  More than 65 536 rows or 4 096 tracks, an owner
+    outside [-1, T), a host tensor and a wrong shape are errors here, before anything is launched; no row or T = 0
+    launches nothing."""
+    import torch
+    lib = load()
+    o, tracks = _check_sig_link("sig_link", sig, owner, tracks)
+    if not sig.is_cuda:
+        raise GenConViTHipError("sig_link expects the signatures as a device tensor")
+    n = sig.shape[0]
+    if n == 0 or tracks == 0:
+        return torch.full((tracks, tracks), SIG_NONE, dtype=torch.int64, device=sig.device)
+    sig = sig.contiguous()
+    if sig.data_ptr() % 16:
+        sig = sig.clone()                                   # a view that starts inside an allocation, off a 16-byte boundary
+    od = o.contiguous().to(sig.device)
+    out = torch.empty((tracks, tracks), dtype=torch.int32, device=sig.device)       # the C entry's uint32, bit for bit
+    check(lib.gcv_sig_link(sig.data_ptr(), od.data_ptr(), n, tracks, out.data_ptr(), current_stream_ptr(sig.device)),
+          "gcv_sig_link")
+    return out.to(torch.int64) & SIG_NONE
 
 
 CUT_REGIONS, CUT_BINS = (1, 2, 4, 8), 64

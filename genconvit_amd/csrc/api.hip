@@ -784,6 +784,18 @@ int gcv_face_quality(const void* frames_u8_nhwc, int nframes, int H, int W, cons
   return launch_face_quality((const unsigned char*)frames_u8_nhwc, nframes, H, W, boxes5, n, grid, out8, (hipStream_t)s);
 }
 
+int gcv_face_signature(const void* frames_u8_nhwc, int nframes, int H, int W, const int* boxes5, int n, void* sig384,
+                       gcv_stream s) {
+  GCV_REQUIRE(n <= 0 || (frames_u8_nhwc && boxes5 && sig384), "face signature: null pointer");
+  return launch_face_signature((const unsigned char*)frames_u8_nhwc, nframes, H, W, boxes5, n, (unsigned char*)sig384,
+                               (hipStream_t)s);
+}
+
+int gcv_sig_link(const void* sig384, const int* owner, int n, int tracks, uint32_t* out_u32, gcv_stream s) {
+  GCV_REQUIRE(n <= 0 || tracks <= 0 || (sig384 && owner && out_u32), "sig link: null pointer");
+  return launch_sig_link((const unsigned char*)sig384, owner, n, tracks, out_u32, (hipStream_t)s);
+}
+
 int gcv_k_fused_mlp(int dtype, int C, const void* x, const void* w1, const float* b1, const float* w2_f32,
                     const float* b2, const float* gamma, const void* resid, void* out, int M, gcv_stream s) {
   GCV_REQUIRE(dtype == GCV_F16 || dtype == GCV_BF16, "the MLP kernels are built for 16-bit storage");

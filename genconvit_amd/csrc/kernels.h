@@ -93,6 +93,11 @@ int launch_blend_fit(const uint32_t* cells, int nframes, int grid, int lag, int6
 // n rows (G, S1, S2, L2, GX, GY, dark, bright)
 int launch_face_quality(const unsigned char* frames, int nframes, int H, int W, const int* boxes5, int n, int grid,
                         int64_t* out8, hipStream_t s);
+// persons.hip: n face boxes -> n appearance signatures of 384 bytes, and the (T, T) minimum L1 distance between the rows
+// of every two tracks
+int launch_face_signature(const unsigned char* frames, int nframes, int H, int W, const int* boxes5, int n,
+                          unsigned char* out384, hipStream_t s);
+int launch_sig_link(const unsigned char* sig, const int* owner, int n, int T, uint32_t* out, hipStream_t s);
 int launch_kl(const float* partial, int splitk, const float* bias, const float* mu, float* rowsum, float* kl, int B,
               int N, hipStream_t s);
 int launch_vote(const float* logits, int rows, float* mean2, hipStream_t s);

@@ -544,6 +544,23 @@ def _check_quality(what, grid=64, sharp_rel=0.5, sharp_min=0.0, clip_max=0.5):
                          f"{clip_max} lie in (0, 1]")
 
 
+def _box_groups(rows, ids, max_frames):
+    """The boxes ``ids`` of ``rows`` in frame order, cut into runs that lie on at most ``max_frames`` distinct frames; per run
+    (its ids, its frames in rising order, its rows with the frame counted within those frames): what one upload of host
+    frames serves."""
+    groups, used = [], set()
+    for i in sorted(ids, key=lambda i: (rows[i][0], i)):
+        if not groups or len(used | {rows[i][0]}) > max_frames:
+            groups.append([])
+            used = set()
+        groups[-1].append(i)
+        used.add(rows[i][0])
+    for group in groups:
+        used = sorted({rows[i][0] for i in group})
+        at = {f: k for k, f in enumerate(used)}
+        yield group, used, [(at[rows[i][0]], *rows[i][1:]) for i in group]
+
+
 def face_quality(frames, boxes, grid=64, max_frames=128, dev=None):
     """How usable is each face crop.  A face smeared by motion or defocus, blown out by a flash or lost in the dark still
     gets a crop and a score, and the score is noise at best.  Every box is measured on its own ``grid`` x ``grid`` lattice
@@ -585,18 +602,9 @@ def face_quality(frames, boxes, grid=64, max_frames=128, dev=None):
     if big and fr.is_cuda:
         raw[big] = _lib.face_quality(fr, [rows[i] for i in big], grid=grid).cpu().numpy()
     elif big:
-        groups, used = [], set()
-        for i in sorted(big, key=lambda i: (rows[i][0], i)):
-            if not groups or len(used | {rows[i][0]}) > max_frames:
-                groups.append([])
-                used = set()
-            groups[-1].append(i)
-            used.add(rows[i][0])
-        for ids in groups:
-            used = sorted({rows[i][0] for i in ids})
-            at = {f: k for k, f in enumerate(used)}
+        for ids, used, local in _box_groups(rows, big, max_frames):
             slab = fr.index_select(0, torch.as_tensor(used)).to(dev or device)
-            raw[ids] = _lib.face_quality(slab, [(at[rows[i][0]], *rows[i][1:]) for i in ids], grid=grid).cpu().numpy()
+            raw[ids] = _lib.face_quality(slab, local, grid=grid).cpu().numpy()
     measured = np.zeros(n, dtype=bool)
     measured[big] = True
     g = float(grid)
@@ -641,14 +649,140 @@ def quality_keep(quality, track_offsets, sharp_rel=0.5, sharp_min=0.0, clip_max=
     return keep
 
 
+PERSON_DEFAULTS = dict(link_max=9082, per_track=64)
+
+
+def _check_persons(what, link_max=PERSON_DEFAULTS["link_max"], per_track=PERSON_DEFAULTS["per_track"]):
+    number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v)
+    if not (number(link_max) and link_max >= 0):
+        raise ValueError(f"{what}: link_max {link_max} must be a number of at least 0")
+    if isinstance(per_track, bool) or not isinstance(per_track, (int, np.integer)) or per_track < 1:
+        raise ValueError(f"{what}: per_track {per_track} must be an integer of at least 1")
+
+
+def face_signatures(frames, boxes, max_frames=128, dev=None):
+    """What each face crop looks like, for telling people apart: per box the 384 bytes of ``_lib.face_signature`` (the
+    mean-luma cells of a 16 x 16 grid with the box's own mean and spread taken out, which cancels the gain and offset of a
+    shot's exposure, then Cb and Cr on an 8 x 8 grid; include/genconvit_hip.h states the integer arithmetic).
+    ``frames``: uint8 (F,H,W,3) RGB, numpy or a tensor.  Frames on the GPU are used in place, all boxes in one launch.  Of
+    host frames the boxes go in frame order in groups launched one after another, a group being a run of boxes that lie
+    on at most ``max_frames`` (>= 1) distinct frames: only those are uploaded (to ``dev``, by default this module's
+    ``device``), as in ``face_quality``.  ``boxes``: rows (frame, top, right, bottom, left) inside their frames.  A box lower
+    or narrower than 16 pixels is not sent: it comes back unmeasured.  Returns a dict in the order of ``boxes``:
+      sig        (n,384) uint8 on the device; zeros where not measured
+      measured   bool (n,), numpy
+    No box: empty arrays, nothing is launched.  The signature is a coarse picture of the box, not an identity embedding:
+    two people in like clothes before one wall at one pose can come close, and one person in profile and en face does
+    not."""
+    if max_frames < 1:
+        raise ValueError(f"face_signatures: max_frames {max_frames} must be at least 1")
+    fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
+    if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
+        raise _lib.GenConViTHipError("face_signatures: frames must be uint8 of shape (F,H,W,3)")
+    rows = [tuple(int(v) for v in b) for b in boxes]
+    _lib._check_boxes("face_signatures", rows, *fr.shape[:3])
+    n, g = len(rows), _lib.SIG_GRID
+    to = fr.device if fr.is_cuda else (dev or device)
+    big = [i for i, b in enumerate(rows) if b[3] - b[1] >= g and b[2] - b[4] >= g]
+    measured = np.zeros(n, dtype=bool)
+    measured[big] = True
+    if not big:
+        return {"sig": torch.empty((0, _lib.SIG_BYTES), dtype=torch.uint8, device=to) if n == 0 else
+                torch.zeros((n, _lib.SIG_BYTES), dtype=torch.uint8, device=to), "measured": measured}
+    if fr.is_cuda:
+        parts, order = [_lib.face_signature(fr, [rows[i] for i in big])], list(big)
+    else:
+        parts, order = [], []
+        for ids, used, local in _box_groups(rows, big, max_frames):
+            parts.append(_lib.face_signature(fr.index_select(0, torch.as_tensor(used)).to(to), local))
+            order += ids
+    got = torch.cat(parts)
+    if order == list(range(n)):
+        return {"sig": got, "measured": measured}
+    sig = torch.zeros((n, _lib.SIG_BYTES), dtype=torch.uint8, device=got.device)
+    sig[torch.as_tensor(order, device=got.device)] = got
+    return {"sig": sig, "measured": measured}
+
+
+def link_tracks(dist, tracks, link_max=PERSON_DEFAULTS["link_max"]):
+    """Which tracks are one person: ``persons``, a list of sorted lists of track numbers, ordered by each person's lowest
+    track.  ``dist``: (T,T) integers, ``dist[a][b]`` the distance between the two most alike crops of the tracks a and b
+    (``_lib.sig_link``; read above the diagonal); ``tracks``: the T tracks, lists of rows (frame, ...).  Single linkage with
+    a veto: the pairs a < b with ``dist[a][b] <= link_max`` are taken in ascending (dist, a, b) order, and the clusters of
+    a and b become one unless the two clusters have a frame number in common — two faces in one frame are two people,
+    however alike, and so is everything already joined to either.  A pair that is vetoed stays apart even if a later
+    pair lies close: clusters only grow, so what shares a frame once shares it for good.  ``0xFFFFFFFF``
+    (no measured crop in one of the tracks) never links, whatever ``link_max``.  A ``dist`` that is not (T,T) and a
+    negative ``link_max`` are a ValueError.
+    The default ``link_max`` is a starting value from synthetic material (tests/personutil.py: smooth random colour
+    patterns seen again under gain 0.8 ... 1.15, offset +-20, shifts of a few pixels, box sides 64 ... 200 and noise of
+    sigma 3): there the largest distance between two shots of one pattern is 5 804 and the smallest between shots of two
+    patterns 12 361, and 9 082 is the integer midway.  No accuracy on real faces is claimed — ``scan_frames`` returns the
+    matrix: look at it and choose."""
+    _check_persons("link_tracks", link_max=link_max)
+    T = len(tracks)
+    d = np.asarray(dist.cpu() if torch.is_tensor(dist) else dist, dtype=np.int64).reshape(-1)
+    if d.size != T * T:
+        raise ValueError(f"link_tracks: dist holds {d.size} values for {T} tracks")
+    d = d.reshape(T, T)
+    pairs = sorted((int(d[a, b]), a, b) for a in range(T) for b in range(a + 1, T)
+                   if d[a, b] <= link_max and d[a, b] != _lib.SIG_NONE)
+    root = list(range(T))
+    members = [[t] for t in range(T)]
+    seen = [{int(r[0]) for r in tr} for tr in tracks]
+
+    def find(t):
+        while root[t] != t:
+            t = root[t]
+        return t
+    for _, a, b in pairs:
+        ra, rb = find(a), find(b)
+        if ra == rb or seen[ra] & seen[rb]:
+            continue
+        lo, hi = min(ra, rb), max(ra, rb)
+        root[hi] = lo
+        members[lo] += members[hi]
+        seen[lo] |= seen[hi]
+    return [sorted(members[t]) for t in range(T) if root[t] == t]
+
+
 def _verdict(m):
     """(y, y_val) of a mean pair, as ``max_prediction_value`` / ``pred_vids`` compute it."""
     return int(torch.argmax(m).item()), m[0].item() if m[0] > m[1] else abs(1 - m[1]).item()
 
 
+def _scan_persons(fr, tracks, rows, offsets, logits, nets, max_batch, dev, link_max, per_track):
+    """``scan_frames``'s ``persons`` (its docstring says what the keys hold); ``logits``: [net 0 all crops; net 1 all crops]
+    in the order of ``rows``."""
+    n, T = len(rows), len(tracks)
+    sampled, owner = [], []
+    for t, tr in enumerate(tracks):
+        m = min(per_track, len(tr))
+        sampled += [offsets[t] + (k * len(tr)) // m for k in range(m)]
+        owner += [t] * m
+    sigs = face_signatures(fr, [rows[i] for i in sampled], max_frames=max_batch, dev=dev)
+    owner = [t if ok else -1 for t, ok in zip(owner, sigs["measured"].tolist())]
+    distance = _lib.sig_link(sigs["sig"], owner, T).cpu().numpy().astype(np.int64)
+    linked = link_tracks(distance, tracks, link_max)
+    of_track = [0] * T
+    perm, ranges = [], []
+    for k, person in enumerate(linked):
+        lo = len(perm)
+        for t in person:
+            of_track[t] = k
+            perm += range(offsets[t], offsets[t + 1])
+        ranges.append((lo, len(perm)))
+    pick = torch.as_tensor([k * n + i for k in range(nets) for i in perm], device=logits.device)
+    _, mean2 = _lib.vote_windows(logits.index_select(0, pick), n, nets, ranges)
+    means = mean2.cpu()
+    return {"tracks": linked, "of_track": of_track, "verdicts": [_verdict(means[k]) for k in range(len(linked))],
+            "means": mean2, "distance": distance, "rows": sampled, "measured": sigs["measured"]}
+
+
 def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3, window=15, stride=1, max_batch=128,
                 eps=None, follow=False, follow_grid=64, follow_radius=16, cuts=None, cut_threshold=0.4, cut_regions=4,
-                transitions=None, transition_args=None, quality=None, quality_args=None):
+                transitions=None, transition_args=None, quality=None, quality_args=None, persons=None,
+                person_args=None):
     """When is a video fake, and whose face: every face of every frame is scored, linked into per-person tracks, and voted
     over sliding windows of each track.  ``frames``: uint8 (F,H,W,3) RGB, numpy or a tensor on either device.  ``boxes``:
     rows (frame, top, right, bottom, left); by default the detector — ``locate``, else ``face_locations(..., keep_all=True)``
@@ -716,7 +850,30 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
     rows) and ``track_map`` (for each remaining track, its number before the gate).  The track column of ``follow`` counts
     the tracks before the gate.  With no face nothing is launched.  Host frames on which a measured box lies are uploaded
     a second time for this pass: the upload is not shared with the crops'.  The thresholds are starting values from
-    synthetic material, not tuned ones, and blur finer than a cell of the grid is not seen."""
+    synthetic material, not tuned ones, and blur finer than a cell of the grid is not seen.
+    ``persons`` (``None`` by default: nothing changes): tracks end at every cut and transition, so an interview that cuts
+    between two speakers comes back as dozens of short tracks, each with one weak vote, and nothing says which of them
+    are one person.  ``True``: after tracking, ``follow`` and the ``quality`` gate, so that the final rows are the ones
+    described, at most ``per_track`` rows of every track are sampled (row ``(k * len) // m`` for k < m = min(per_track,
+    len)), ``face_signatures(frames, those rows, max_frames=max_batch, dev=the model's device)`` describes them, ONE
+    ``_lib.sig_link`` gives the distance between the two most alike crops of every two tracks, ``link_tracks`` joins the
+    tracks whose distance is at most ``link_max`` unless they share a frame, and a second ``_lib.vote_windows`` call votes
+    over each person's rows (the logits ``index_select``-ed so that a person's rows are contiguous, in (track, frame)
+    order).  ``person_args``: a dict with keys among ``link_max`` and ``per_track``; None: ``PERSON_DEFAULTS``; anything
+    else is a ValueError, raised before anything runs.  The result gains ``persons``, a dict:
+      tracks     the sorted track numbers of each person, ordered by each person's lowest track
+      of_track   the person of each track
+      verdicts   [(y, y_val), ...]: ``pred_vid`` over each person's crops (ALL rows of its tracks, not only the sampled)
+      means      (P, 2) fp32 on the device: the mean pair behind each verdict
+      distance   (T, T) int64 numpy: ``_lib.sig_link``'s matrix; 0xFFFFFFFF on the diagonal and for a track without a
+                 measured row
+      rows       the sampled crop rows, indices into ``boxes``
+      measured   bool per sampled row: False for a box lower or narrower than 16 pixels, which takes no part
+    With no face these are empty and nothing is launched.  Host frames on which a sampled row lies are uploaded once more
+    for this pass: the upload is not shared with the crops'.  The default ``link_max`` (9 082) is a starting value from
+    synthetic material — the largest distance between two shots of one pattern there is 5 804, the smallest between two
+    patterns 12 361 (``link_tracks``) — not a tuned one: no accuracy on real faces is claimed, and ``distance`` is returned so
+    that the caller can choose."""
     fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
     if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
         raise _lib.GenConViTHipError("scan_frames: frames must be uint8 of shape (F,H,W,3)")
@@ -729,6 +886,15 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
                 raise ValueError(f"scan_frames: quality_args must be a dict with keys among {sorted(qargs)}")
             qargs.update(quality_args)
         _check_quality("scan_frames", **qargs)
+    if persons is not None and not isinstance(persons, bool):
+        raise ValueError(f"scan_frames: persons {persons!r} must be None or True")
+    pargs = dict(PERSON_DEFAULTS)
+    if persons:
+        if person_args is not None:
+            if not (isinstance(person_args, dict) and set(person_args) <= set(pargs)):
+                raise ValueError(f"scan_frames: person_args must be a dict with keys among {sorted(pargs)}")
+            pargs.update(person_args)
+        _check_persons("scan_frames", **pargs)
     targs = dict(TRANSITION_DEFAULTS)
     if transitions is True:
         if transition_args is not None:
@@ -814,6 +980,10 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
     if n == 0:
         res["frame_scores"] = torch.empty((0, 2), dtype=torch.float32, device=p.device)
         res["window_means"] = torch.empty((0, 2), dtype=torch.float32, device=p.device)
+        if persons:
+            res["persons"] = {"tracks": [], "of_track": [], "verdicts": [], "distance": np.empty((0, 0), dtype=np.int64),
+                              "means": torch.empty((0, 2), dtype=torch.float32, device=p.device), "rows": [],
+                              "measured": np.zeros(0, dtype=bool)}
         return res
     if eps is not None and eps.shape[0] != n:
         raise ValueError(f"scan_frames: eps holds {eps.shape[0]} rows for {n} crops")
@@ -845,6 +1015,8 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
                 wins.append((t, tr[lo][0], tr[hi - 1][0]))
         ranges += [(offsets[t], offsets[t + 1]) for t in range(len(tracks))] + [(0, n)]
         frame_p, mean2 = _lib.vote_windows(logits, n, nets, ranges)
+        if persons:
+            res["persons"] = _scan_persons(fr, tracks, rows, offsets, logits, nets, max_batch, p.device, **pargs)
     means = mean2.cpu()
     nw = len(wins)
     res["frame_scores"], res["window_means"] = frame_p, mean2[:nw]

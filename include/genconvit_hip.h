@@ -372,6 +372,53 @@ int gcv_hist_diff_lag(const uint32_t* hist_u32, int nframes, int regions, int la
 int gcv_face_quality(const void* frames_u8_nhwc, int nframes, int H, int W, const int* boxes5, int n, int grid,
                      int64_t* out8, gcv_stream stream);
 
+/* Who is it: an appearance signature of n face boxes in one launch (gcv_face_signature), and for every pair of tracks the
+ * distance of their two most alike crops (gcv_sig_link).  A whole-video scan ends a track at every cut and at both ends of
+ * every dissolve, so edited footage comes back as many short tracks; position cannot link them across a cut, appearance
+ * can.  pred_func.link_tracks turns the distances into persons: the policy stays in Python, the numbers are returned.
+ *   frames   (nframes,H,W,3) uint8 RGB on the device, as for gcv_face_quality; the pointer may have any alignment, and no
+ *            byte outside [frames, frames + nframes H W 3) is read
+ *   boxes5   int32 device array of n rows (frame, top, right, bottom, left), as for gcv_face_quality
+ *   sig384   (n,384) uint8, every row: bytes 0 ... 255 the normalised luma N[u][v] of a 16 x 16 grid, 256 ... 319 Cb of an
+ *            8 x 8 grid, 320 ... 383 Cr of the same grid, each row-major
+ * Arithmetic of the signature (fixed and all-integer, so that a CPU restatement is bit-equal: tests/personutil.py); a // b
+ * is floor division, of non-negative integers throughout; h = bottom - top, w = right - left:
+ *   cell edges        16-grid: ey[i] = (i h) >> 4, ex[i] = (i w) >> 4, i = 0 ... 16; 8-grid: (i h) >> 3, (i w) >> 3, i = 0 ... 8.
+ *                     Cell (u, v) covers the rows [top + ey[u], top + ey[u + 1]) and the columns [left + ex[v],
+ *                     left + ex[v + 1]).  (i h) >> 3 = (2 i h) >> 4: a cell of the 8-grid is four cells of the 16-grid
+ *   precondition      h >= 16 and w >= 16, so that no cell is empty
+ *   luma cells        c[u][v] on the 16-grid: gcv_track_match's cell value, (sum of Y + cnt // 2) // cnt with
+ *                     Y = (77 R + 150 G + 29 B + 128) >> 8
+ *   normalisation     cancels the gain and the offset of a shot's exposure.  S1 = sum of c over the 256 cells,
+ *                     d = 256 c - S1 (256 times the distance from the mean, exactly), A = sum of |d|;
+ *                     N = clamp(128 + sgn(d) ((8192 |d| + A // 2) // A), 0, 255), and N = 128 everywhere when A == 0.
+ *                     |d| <= 65280 and A <= 256 * 65280, so 8192 |d| + A // 2 < 2^31
+ *   chroma cells      per pixel Cb = (32896 - 43 R - 85 G + 128 B) >> 8 and Cr = (32896 + 128 R - 107 G - 21 B) >> 8, both
+ *                     in [1, 256], 256 only for the pixel (0, 0, 255) resp. (255, 0, 0).  The cell on the 8-grid is
+ *                     min((sum + cnt // 2) // cnt, 255): the minimum matters only for a cell of nothing but that pixel
+ * A bad row — a frame index out of range, a box outside the frame, h or w below 16 — reads nothing and gives 384 zero bytes
+ * (a good row never does: the luma bytes of a good row average 128).  The Python binding refuses such rows instead.
+ * Refused before anything is launched (gcv_last_error() says why): nframes, H or W not positive; H W > 2^28 (a chroma
+ * cell's sum is 32 bits); a null pointer with n > 0.  n == 0 launches nothing and writes nothing.
+ * One launch, one workgroup of 256 threads per box; the call allocates, copies and synchronises nothing.
+ *
+ *   sig      (n,384) uint8 on the device, 16-byte aligned: rows as above (any bytes will do: the distance is plain L1)
+ *   owner    int32 device array of n: the track of each row, in [0, T); -1 — or anything else outside [0, T) — for a row
+ *            that takes no part.  Need not be sorted
+ *   out      (T,T) uint32: out[a][b] = the minimum over the rows i of track a and the rows j of track b, a != b, of
+ *            sum over k = 0 ... 383 of |sig[i][k] - sig[j][k]|, at most 384 * 255 = 97 920.  Symmetric.  The diagonal, and
+ *            every pair one of whose tracks has no row, hold 0xFFFFFFFF.  Every element is written
+ * Refused: n outside 0 ... 65 536, T outside 0 ... 4 096, a null or misaligned pointer (n, T > 0).  n == 0 or T == 0
+ * launches nothing and writes nothing.  Otherwise a hipMemsetAsync on the stream sets out to 0xFF bytes and one launch
+ * follows: a workgroup per pair of 64-row tiles, the minima merged into out by unsigned integer atomic minima, whose
+ * result does not depend on their order.  The call allocates, copies and synchronises nothing.
+ * Not done here: any judgement (the threshold is the caller's), alignment of the face inside its box beyond what the
+ * detector gives, and any claim about real faces — the signature is a coarse picture of the box, not an identity
+ * embedding. */
+int gcv_face_signature(const void* frames_u8_nhwc, int nframes, int H, int W, const int* boxes5, int n, void* sig384,
+                       gcv_stream stream);
+int gcv_sig_link(const void* sig384, const int* owner, int n, int tracks, uint32_t* out_u32, gcv_stream stream);
+
 /* pred_vid's reduction (model/pred_func.py:120,125): mean2[c] = mean_r sigmoid(logits[r][c]). */
 int gcv_vote(const float* logits, int rows, float* mean2, gcv_stream stream);
 
