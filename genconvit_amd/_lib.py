@@ -78,6 +78,7 @@ SIGNATURES = {
     "gcv_cam_overlay": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_float,
                                 c_int, c_void_p, c_void_p]),
     "gcv_track_match": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gcv_track_chain": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gcv_frame_hist": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gcv_hist_diff": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "gcv_frame_cells": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
@@ -669,6 +670,62 @@ def track_match(frames_u8, jobs, grid=64, radius=16):
     jd = j.contiguous().to(frames_u8.device)
     check(lib.gcv_track_match(frames_u8.data_ptr(), nf, h, w, jd.data_ptr(), n, grid, radius, out.data_ptr(),
                               current_stream_ptr(frames_u8.device)), "gcv_track_match")
+    return out
+
+
+TRACK_CHAIN_STEPS_MAX, TRACK_CHAIN_NONE = 1024, (0, 0, -1, -1)
+
+
+def _check_chain_jobs(what, jobs, nf, h, w, grid):
+    """``jobs`` as an (n,11) int32 host tensor (``gcv_track_chain``, include/genconvit_hip.h); a frame index of the template
+    or of any step out of range, a template box or first prior box outside its (h, w) frame, a template lower or narrower
+    than ``grid``, a ``dir`` other than +-1, ``steps`` outside 1 ... 1024 and a negative ``stop`` are errors."""
+    import torch
+    j = torch.as_tensor(jobs, dtype=torch.int32).reshape(-1, 11).cpu()
+    if j.numel():
+        fa, top, right, bottom, left, fs, step, steps, py, px, stop = j.long().unbind(1)
+        last = fs + step * (steps - 1)
+        ok = (fa >= 0) & (fa < nf) & (top >= 0) & (left >= 0) & (bottom <= h) & (right <= w)
+        ok &= (bottom - top >= grid) & (right - left >= grid) & (step.abs() == 1)
+        ok &= (steps >= 1) & (steps <= TRACK_CHAIN_STEPS_MAX) & (fs >= 0) & (fs < nf) & (last >= 0) & (last < nf)
+        ok &= (top + py >= 0) & (bottom + py <= h) & (left + px >= 0) & (right + px <= w) & (stop >= 0)
+        if not bool(ok.all()):
+            raise GenConViTHipError(f"{what}: job {int((~ok).nonzero()[0])} has a frame index out of range, a template or "
+                                    f"first prior box outside its {h}x{w} frame or smaller than {grid} a side, a dir other "
+                                    f"than +-1, steps outside 1 ... {TRACK_CHAIN_STEPS_MAX} or a negative stop")
+    return j
+
+
+def track_chain(frames_u8, jobs, grid=64, radius=8):
+    """Where does the face go before its first or after its last detection (``gcv_track_chain``, include/genconvit_hip.h:
+    the arithmetic is stated there): ``track_match``'s search walked along consecutive frames, every step around the box the
+    step before found, against one template that is not updated.  ``frames_u8``: (F,H,W,3) uint8 device tensor (RGB);
+    ``jobs``: (n,11) integers, per row (fa, top, right, bottom, left) the template, (fs, dir, steps) the frames fs, fs + dir,
+    ..., (py, px) the offset of the first prior box from the template box and ``stop`` the cost above which the chain ends.
+    Returns (n, max(steps), 4) int32 on the device: per step (oy, ox, best cost, cost at zero displacement) with (oy, ox)
+    relative to that step's prior, and (0, 0, -1, -1) from the step that exceeded ``stop``, and from ``steps``, on.  A ``grid``
+    other than 16, 32, 64, a ``radius`` outside 0 ... 32 and a bad row are errors; no rows give an empty (0, 0, 4) tensor."""
+    import torch
+    lib = load()
+    if not (torch.is_tensor(frames_u8) and frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4
+            and frames_u8.shape[3] == 3):
+        raise GenConViTHipError("track_chain expects a uint8 device tensor of shape (F,H,W,3)")
+    grid, radius = int(grid), int(radius)
+    if grid not in TRACK_GRIDS:
+        raise GenConViTHipError(f"track_chain: grid {grid}; accepted values are 16, 32 and 64")
+    if not 0 <= radius <= TRACK_RADIUS_MAX:
+        raise GenConViTHipError(f"track_chain: radius {radius} outside 0 ... {TRACK_RADIUS_MAX}")
+    frames_u8 = frames_u8.contiguous()
+    nf, h, w, _ = frames_u8.shape
+    j = _check_chain_jobs("track_chain", jobs, nf, h, w, grid)
+    n = j.shape[0]
+    if n == 0:
+        return torch.empty((0, 0, 4), dtype=torch.int32, device=frames_u8.device)
+    max_steps = int(j[:, 7].max())
+    out = torch.empty((n, max_steps, 4), dtype=torch.int32, device=frames_u8.device)
+    jd = j.contiguous().to(frames_u8.device)
+    check(lib.gcv_track_chain(frames_u8.data_ptr(), nf, h, w, jd.data_ptr(), n, max_steps, grid, radius, out.data_ptr(),
+                              current_stream_ptr(frames_u8.device)), "gcv_track_chain")
     return out
 
 

@@ -753,6 +753,13 @@ int gcv_track_match(const void* frames_u8_nhwc, int nframes, int H, int W, const
                             (hipStream_t)s);
 }
 
+int gcv_track_chain(const void* frames_u8_nhwc, int nframes, int H, int W, const int* jobs11, int n, int max_steps, int grid,
+                    int radius, int* out4, gcv_stream s) {
+  GCV_REQUIRE(n <= 0 || (frames_u8_nhwc && jobs11 && out4), "track chain: null pointer");
+  return launch_track_chain((const unsigned char*)frames_u8_nhwc, nframes, H, W, jobs11, n, max_steps, grid, radius, out4,
+                            (hipStream_t)s);
+}
+
 int gcv_frame_hist(const void* frames_u8_nhwc, int nframes, int H, int W, int regions, uint32_t* hist_u32, gcv_stream s) {
   GCV_REQUIRE(frames_u8_nhwc && hist_u32, "frame hist: null pointer");
   return launch_frame_hist((const unsigned char*)frames_u8_nhwc, nframes, H, W, regions, hist_u32, (hipStream_t)s);

@@ -82,6 +82,10 @@ int launch_cam_overlay(const unsigned char* frames, int nframes, int H, int W, c
 // follow.hip: block matching of a face between two detector frames, n jobs of 17 ints -> n rows (oy, ox, cost, cost0)
 int launch_track_match(const unsigned char* frames, int nframes, int H, int W, const int* jobs17, int n, int grid,
                        int radius, int* out4, hipStream_t s);
+// the same search walked along a chain of frames, each step around the box of the step before: n jobs of 11 ints ->
+// n x max_steps rows (oy, ox, cost, cost0)
+int launch_track_chain(const unsigned char* frames, int nframes, int H, int W, const int* jobs11, int n, int max_steps,
+                       int grid, int radius, int* out4, hipStream_t s);
 // cuts.hip: 64-bin luma histograms of the regions x regions parts of every frame, and their L1 distance between
 // consecutive frames
 int launch_frame_hist(const unsigned char* frames, int nframes, int H, int W, int regions, uint32_t* hist, hipStream_t s);

@@ -308,8 +308,8 @@ def follow_tracks(frames, tracks, anchors, grid=64, radius=16, max_frames=128, d
     ``device``), so device memory is bounded by the group, not the video.
     Returns ``(tracks, follow)``: the tracks with the filled boxes moved, and an int32 (n_jobs, 6) array of (track, frame,
     oy, ox, cost, cost0) rows in (track, frame) order — cost0 is the cost at the interpolated position.
-    What this does not do: sub-cell refinement, a change of box size beyond the interpolation, extending a track past its
-    last detection."""
+    What this does not do: sub-cell refinement, a change of box size beyond the interpolation.  Extending a track past its
+    first and last detection is ``extend_tracks``'s."""
     _check_follow("follow_tracks", grid, radius)
     if max_frames < 3:
         raise ValueError(f"follow_tracks: max_frames {max_frames} must be at least 3 (a job reads three frames)")
@@ -359,6 +359,150 @@ def follow_tracks(frames, tracks, anchors, grid=64, radius=16, max_frames=128, d
         out[t][i] = (f, top + oy, right + ox, bottom + oy, left + ox)
         follow[n] = (t, f, oy, ox, res[n, 2], res[n, 3])
     return out, follow
+
+
+EXTEND_DEFAULTS = dict(grid=64, radius=8, steps=16, cost_max=18.7)
+
+
+def _check_extend(what, grid=EXTEND_DEFAULTS["grid"], radius=EXTEND_DEFAULTS["radius"], steps=EXTEND_DEFAULTS["steps"],
+                  cost_max=EXTEND_DEFAULTS["cost_max"]):
+    whole = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    if not (whole(grid) and grid in _lib.TRACK_GRIDS and whole(radius) and 0 <= radius <= _lib.TRACK_RADIUS_MAX):
+        raise ValueError(f"{what}: grid {grid} must be 16, 32 or 64 and radius {radius} lie in 0 ... {_lib.TRACK_RADIUS_MAX}")
+    if not (whole(steps) and 1 <= steps <= _lib.TRACK_CHAIN_STEPS_MAX):
+        raise ValueError(f"{what}: steps {steps} must be an integer in 1 ... {_lib.TRACK_CHAIN_STEPS_MAX}")
+    if not (isinstance(cost_max, (int, float, np.integer, np.floating)) and not isinstance(cost_max, bool) and
+            0 <= cost_max <= 255):
+        raise ValueError(f"{what}: cost_max {cost_max} must be a number in 0 ... 255 (grey levels per cell)")
+
+
+def extend_tracks(frames, tracks, ends=None, grid=EXTEND_DEFAULTS["grid"], radius=EXTEND_DEFAULTS["radius"],
+                  steps=EXTEND_DEFAULTS["steps"], cost_max=EXTEND_DEFAULTS["cost_max"], iou=0.3, max_frames=128, dev=None):
+    """Carry ``tracks`` past their first and last box.  A track starts at its first detection and ends at its last; with a
+    detector that runs on every k-th frame up to k - 1 frames at each end of every shot are never scored, and a detector
+    drop-out longer than the tracker's gap (a head turned to profile) ends a track although the face is still there.
+    Every track gets one forward chain from its last box and one backward chain from its first box (both are
+    detections when the tracks come from ``track_boxes``): ``_lib.track_chain`` searches frame after frame for the cells
+    of that box, each step around the box the step before found, at most ``radius`` cells of the ``grid`` x ``grid``
+    lattice either way, with the box's size unchanged and the template not updated.
+    A forward chain from a box in frame f covers the frames f + 1, f + 2, ...: at most ``steps`` of them, none past the last
+    frame of the video and none at or past the smallest entry of ``ends`` above f.  A backward chain covers f - 1, f - 2,
+    ...: at most ``steps``, none below 0 and none below the largest entry of ``ends`` that is <= f — it may include the
+    first frame of its shot.  ``ends``: the frame numbers at which a new shot starts (what ``scan_frames`` hands to
+    ``track_boxes``: the cuts and the borders of the transitions).  A track whose end box is lower or narrower than ``grid``
+    pixels gets no chain.  A chain ends at the first step whose best cost exceeds floor(``cost_max`` grid^2): ``cost_max``
+    is the mean absolute difference per cell, in grey levels.
+    The accepted steps are then cut where they run into another track: first the forward chains in track order, then the
+    backward chains in track order, and a chain ends before the first frame in which another track — its own boxes and
+    the extensions accepted so far — has a box with IoU >= ``iou`` against the chain's box.  Where a detector drop-out split
+    one face into two tracks, this keeps the face from being scored twice; the two tracks are not joined here
+    (``scan_frames(persons=True)`` can link them).
+    ``frames``: uint8 (F,H,W,3) RGB, numpy or a tensor.  Frames on the GPU are used in place, all chains in one launch.  Of
+    host frames the chains go in groups launched one after another, a group needing at most ``max_frames`` (>= 2) distinct
+    frames: only those are uploaded (to ``dev``, by default this module's ``device``).  A chain that does not fit is
+    continued in the next group from the sum of its offsets so far, which gives the same boxes as one launch.
+    Returns ``(tracks, extend)``: the tracks with the accepted boxes added in front and behind, still over consecutive
+    frames, and an int32 (n, 7) array of (track, frame, dir, oy, ox, cost, cost0) rows, one per accepted step — the forward
+    chains in track order, then the backward ones, each along its chain; (oy, ox) is the step from the chain's box in
+    the frame before (dir = 1) or after (dir = -1), cost0 the cost of not moving.
+    The default ``cost_max`` is a starting value from synthetic material (tests/extendutil.py: smooth random colour patterns
+    of tests/personutil.py's kind, 64 ... 120 pixels a side, moving up to 3 cells a frame over a drifting smooth background
+    under pixel noise of sigma 3, at grids 16, 32 and 64, the pattern removed part-way): there the largest cost per cell of
+    a step that still follows the pattern is 9.8 and the smallest of a step after it is gone 27.6, and 18.7 lies midway.
+    No accuracy on real faces is claimed — ``extend`` holds every cost: look at them and choose.
+    What this does not do: a change of box size along a chain, sub-cell refinement, template update, joining the tracks a
+    chain runs into."""
+    _check_extend("extend_tracks", grid, radius, steps, cost_max)
+    if max_frames < 2:
+        raise ValueError(f"extend_tracks: max_frames {max_frames} must be at least 2 (a chain reads its template's frame and a "
+                         f"frame to search)")
+    fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
+    if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
+        raise _lib.GenConViTHipError("extend_tracks: frames must be uint8 of shape (F,H,W,3)")
+    nf = int(fr.shape[0])
+    ends = sorted({int(e) for e in ends}) if ends is not None else []
+    out = [[tuple(int(v) for v in b) for b in tr] for tr in tracks]
+    _lib._check_boxes("extend_tracks", [tr[k] for tr in out if tr for k in (0, -1)], *fr.shape[:3])
+    stop = int(np.floor(float(cost_max) * grid * grid))
+    chains = []                                             # (track, dir, the template box, number of steps)
+    for d in (1, -1):
+        for t, tr in enumerate(out):
+            if not tr:
+                continue
+            b = tr[-1] if d == 1 else tr[0]
+            if b[3] - b[1] < grid or b[2] - b[4] < grid:
+                continue
+            if d == 1:
+                room = min([e for e in ends if e > b[0]] + [nf]) - 1 - b[0]
+            else:
+                room = b[0] - max([e for e in ends if e <= b[0]] + [0])
+            if min(room, steps) >= 1:
+                chains.append((t, d, b, min(room, steps)))
+    found = [[] for _ in chains]                            # per chain: the (oy, ox, cost, cost0) of its steps up to the stop
+
+    def row(c, k0, n, at=None):
+        """the 11 integers of the steps k0 ... k0 + n - 1 of chain c; ``at`` maps frame numbers to a slab's (consecutive
+        frames stay consecutive: the slab is sorted)"""
+        _, d, b, _ = chains[c]
+        fa, fs = b[0], b[0] + d * (k0 + 1)
+        if at is not None:
+            fa, fs = at[fa], at[fs]
+        return (fa, *b[1:], fs, d, n, sum(s[0] for s in found[c]), sum(s[1] for s in found[c]), stop)
+
+    def take(ids, got):
+        """the rows of one launch: chain ids[i] = (c, k0, n) continues with got[i, :n] up to its first refusal row"""
+        for (c, k0, n), rows in zip(ids, got):
+            for r in rows[:n].tolist():
+                if tuple(r) == _lib.TRACK_CHAIN_NONE:
+                    break
+                found[c].append(tuple(r))
+    if chains and fr.is_cuda:
+        ids = [(c, 0, ch[3]) for c, ch in enumerate(chains)]
+        take(ids, _lib.track_chain(fr, [row(*i) for i in ids], grid=grid, radius=radius).cpu().numpy())
+    elif chains:
+        # groups of (chain, first step, steps) segments: a chain takes as many steps as still fit into the group's frames
+        groups, used = [[]], set()
+        for c in sorted(range(len(chains)), key=lambda c: (min(chains[c][2][0], chains[c][2][0] + chains[c][1]), c)):
+            _, d, b, total = chains[c]
+            k0 = 0
+            while k0 < total:
+                n, need = 0, {b[0]}
+                while k0 + n < total and len(used | need | {b[0] + d * (k0 + n + 1)}) <= max_frames:
+                    need.add(b[0] + d * (k0 + n + 1))
+                    n += 1
+                if n:
+                    groups[-1].append((c, k0, n))
+                    used |= need
+                    k0 += n
+                if k0 < total:
+                    groups.append([])
+                    used = set()
+        for ids in groups:
+            ids = [(c, k0, n) for c, k0, n in ids if len(found[c]) == k0]          # a chain that stopped is not continued
+            if not ids:
+                continue
+            used = sorted({f for c, k0, n in ids for f in [chains[c][2][0]] + [chains[c][2][0] + chains[c][1] * (k + 1)
+                                                                               for k in range(k0, k0 + n)]})
+            at = {f: k for k, f in enumerate(used)}
+            slab = fr.index_select(0, torch.as_tensor(used)).to(dev or device)
+            take(ids, _lib.track_chain(slab, [row(*i, at) for i in ids], grid=grid, radius=radius).cpu().numpy())
+    # the collision rule, in the chains' order: forward in track order, then backward in track order
+    at_frame = {}
+    for t, tr in enumerate(out):
+        for b in tr:
+            at_frame.setdefault(b[0], []).append((t, b[1:]))
+    rows = []
+    for (t, d, b, _), steps_found in zip(chains, found):
+        box, added = b, []
+        for oy, ox, cost, cost0 in steps_found:
+            box = (box[0] + d, box[1] + oy, box[2] + ox, box[3] + oy, box[4] + ox)
+            if any(o != t and _box_iou(box[1:], ob) >= iou for o, ob in at_frame.get(box[0], ())):
+                break
+            at_frame.setdefault(box[0], []).append((t, box[1:]))
+            added.append(box)
+            rows.append((t, box[0], d, oy, ox, cost, cost0))
+        out[t] = out[t] + added if d == 1 else added[::-1] + out[t]
+    return out, np.asarray(rows, dtype=np.int32).reshape(-1, 7)
 
 
 def _check_cuts(what, threshold, regions):
@@ -782,7 +926,7 @@ def _scan_persons(fr, tracks, rows, offsets, logits, nets, max_batch, dev, link_
 def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3, window=15, stride=1, max_batch=128,
                 eps=None, follow=False, follow_grid=64, follow_radius=16, cuts=None, cut_threshold=0.4, cut_regions=4,
                 transitions=None, transition_args=None, quality=None, quality_args=None, persons=None,
-                person_args=None):
+                person_args=None, extend=None, extend_args=None):
     """When is a video fake, and whose face: every face of every frame is scored, linked into per-person tracks, and voted
     over sliding windows of each track.  ``frames``: uint8 (F,H,W,3) RGB, numpy or a tensor on either device.  ``boxes``:
     rows (frame, top, right, bottom, left); by default the detector — ``locate``, else ``face_locations(..., keep_all=True)``
@@ -821,8 +965,8 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
     [1, F - 1], anything else is a ValueError.  They go to ``track_boxes``, so no track, and therefore no window, no
     segment and no ``follow`` job, straddles a cut.  The result gains ``cuts``, and ``cut_scores`` (float64 (F - 1,)) when
     they were computed here: the default threshold is a starting value, not a tuned one.  With ``detect_every`` > 1 a face
-    goes unscored between its last detection before a cut and its first detection after it: tracks are not extended past
-    a detection.  ``cuts`` finds hard cuts only, and a one-frame flash gives two adjacent cuts; linear fades and dissolves
+    goes unscored between its last detection before a cut and its first detection after it unless ``extend`` carries the
+    tracks there.  ``cuts`` finds hard cuts only, and a one-frame flash gives two adjacent cuts; linear fades and dissolves
     are what ``transitions`` is for.
     ``transitions`` (``None`` by default: nothing changes): the fades and dissolves of edited footage.  A dissolve from one
     talking head to another leaves a box where a box was, so IoU joins the two people, and the frames inside it show a
@@ -873,10 +1017,33 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
     for this pass: the upload is not shared with the crops'.  The default ``link_max`` (9 082) is a starting value from
     synthetic material — the largest distance between two shots of one pattern there is 5 804, the smallest between two
     patterns 12 361 (``link_tracks``) — not a tuned one: no accuracy on real faces is claimed, and ``distance`` is returned so
-    that the caller can choose."""
+    that the caller can choose.
+    ``extend`` (``None`` by default: nothing changes): a track starts at its first detection and ends at its last, so with
+    ``detect_every`` = k up to k - 1 frames at each end of every shot are never scored, and a detector drop-out longer than
+    k (a head turned to profile) ends a track for good.  ``True``: after ``track_boxes`` and ``follow``, and before the
+    ``quality`` gate and ``persons`` so that both see the added rows, ``extend_tracks(frames, tracks, ends, iou=iou,
+    max_frames=max_batch, dev=the model's device, **extend_args)`` carries every track backward from its first and forward
+    from its last box by block matching (``_lib.track_chain``), with the ``ends`` that went to ``track_boxes``: no extension
+    enters a transition or crosses a found cut.  ``extend_args``: a dict with keys among ``grid``, ``radius``, ``steps`` and
+    ``cost_max``; None: ``EXTEND_DEFAULTS``; anything else is a ValueError, raised before anything runs.  ``tracks``,
+    ``boxes`` and everything after them hold the extended tracks, ``eps`` counts the crops after extension, and the result
+    gains ``extend``, int32 (n, 7) rows (track, frame, dir, oy, ox, cost, cost0), one per added box; the track column
+    counts the tracks before the ``quality`` gate.  Without ``cuts`` only the cost gate stops a chain at a hard cut.
+    Exposure drift raises the cost, so under it chains stop early: that is the safe side.  Where the detector did look at
+    an extended frame, it is a frame on which it found nothing there.  The default ``cost_max`` is a starting value from
+    synthetic material (``extend_tracks``), not a tuned one."""
     fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
     if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
         raise _lib.GenConViTHipError("scan_frames: frames must be uint8 of shape (F,H,W,3)")
+    if extend is not None and extend is not True:
+        raise ValueError(f"scan_frames: extend {extend!r} must be None or True")
+    eargs = dict(EXTEND_DEFAULTS)
+    if extend:
+        if extend_args is not None:
+            if not (isinstance(extend_args, dict) and set(extend_args) <= set(eargs)):
+                raise ValueError(f"scan_frames: extend_args must be a dict with keys among {sorted(eargs)}")
+            eargs.update(extend_args)
+        _check_extend("scan_frames", **eargs)
     if quality is not None and not isinstance(quality, bool):
         raise ValueError(f"scan_frames: quality {quality!r} must be None or True")
     qargs = dict(QUALITY_DEFAULTS)
@@ -951,6 +1118,8 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
                                       max_frames=max(max_batch, 3), dev=p.device)
     else:
         tracks = track_boxes(boxes, iou=iou, max_gap=detect_every, cuts=ends)
+    if extend:
+        tracks, extended = extend_tracks(fr, tracks, ends, iou=iou, max_frames=max(max_batch, 2), dev=p.device, **eargs)
     measures = None
     if quality:
         before = [b for tr in tracks for b in tr]
@@ -967,6 +1136,8 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
            "verdict": (None, None), "segments": []}
     if follow:
         res["follow"] = moved
+    if extend:
+        res["extend"] = extended
     if cuts is not None:
         res["cuts"] = cuts
         if cut_scores is not None:

@@ -257,10 +257,49 @@ int gcv_cam_overlay(const void* frames_u8_nhwc, int nframes, int H, int W, const
  * binding does): frame indices in range, boxes inside the frame, every h, w >= G, wa, wb >= 0 and 1 <= wa + wb <= 1024, which
  * keeps the cost below 2^31 (64 * 64 * 255 * 1024).  A row that breaks any of this reads nothing and gives (0, 0, 0, 0).
  * One launch, one workgroup per job; the call allocates, copies and synchronises nothing.
- * Not done here: sub-cell refinement, a change of box size inside a gap beyond the interpolation, extending a track past
- * its last detection. */
+ * Not done here: sub-cell refinement, a change of box size inside a gap beyond the interpolation.  Extending a track past
+ * its first and last detection is gcv_track_chain's. */
 int gcv_track_match(const void* frames_u8_nhwc, int nframes, int H, int W, const int* jobs17, int n, int grid, int radius,
                     int* out4, gcv_stream s);
+
+/* Carry a face past its first or last detection: n chains in one launch, each a walk over consecutive frames in which
+ * every step searches around the box the step before found.  gcv_track_match cannot do this — each of its jobs needs a
+ * prior box that is known before the launch.
+ *   frames  (nframes,H,W,3) uint8 RGB on the device, as for gcv_track_match
+ *   jobs11  int32 device array of n rows:
+ *             fa, top, right, bottom, left   the template: a detected box in frame fa; its h = bottom - top and
+ *                                            w = right - left are the size of every box of the chain
+ *             fs, dir, steps                 the frames searched are fs, fs + dir, ..., fs + dir (steps - 1); dir is +1 or
+ *                                            -1; 1 <= steps <= max_steps
+ *             py, px                         the pixel offset of the prior box of the first step from the template box: 0, 0
+ *                                            for a chain that starts at the detection; the sum of the (oy, ox) rows of an
+ *                                            earlier launch for a chain that continues it
+ *             stop                           a cost bound, 0 ... 2^31 - 1
+ *   max_steps  1 ... 1024: the rows of out4 per job
+ *   grid, radius  as for gcv_track_match
+ *   out4    (n,max_steps,4) int32: (oy, ox, cost, cost0) per step; (oy, ox) is relative to that step's prior box — the
+ *           caller adds the steps up
+ * Arithmetic: gcv_track_match's luma, cell edges, cell values and validity, and its minimum over
+ * (cost, dy dy + dx dx, dy, dx).  With A[u][v] the cells of the template box in frame fa, step k = 0 ... steps - 1 is:
+ *   prior box         step 0: the template box shifted by (py, px); step k: the prior of step k - 1 shifted by its (oy, ox)
+ *   search window     V[u][v], u, v in [-R, G + R): frame fs + dir k around that prior, with the template's h and w
+ *   cost(dy, dx)      sum over u, v of |A[u][v] - V[u + dy][v + dx]|, over the valid candidates of that prior
+ *   result            out[k] = (e_h(dy), e_w(dx), cost(dy, dx), cost(0, 0)) of the smallest (cost, dy dy + dx dx, dy, dx)
+ *   stop              if that smallest cost exceeds stop (cost > stop), step k and every later step of the job write
+ *                     (0, 0, -1, -1) and the job ends there; so do the rows steps ... max_steps - 1
+ * The template is not updated along the chain, so position errors do not accumulate in it; a face that changes pose or
+ * exposure makes the cost rise.  Each step equals gcv_track_match on the row (frame, prior box, template, 1, template, 0)
+ * — both anchors the template, weighted 1 and 0 —, which is how tests/extendutil.py restates it.
+ * Refused before anything is launched (gcv_last_error() says why): grid not 16, 32 or 64; radius outside 0 ... 32;
+ * max_steps outside 1 ... 1024; nframes, H or W not positive (or H W > 2^30).  n == 0 launches nothing.  The rows are the
+ * caller's to check (the Python binding does): fa and every searched frame in range, the template box and the first prior
+ * box inside the frame, h, w >= G, dir = +-1, 1 <= steps <= max_steps, stop >= 0.  A row that breaks any of this reads
+ * nothing and writes (0, 0, -1, -1) throughout.
+ * One launch, one workgroup per chain; the template's cells stay in LDS for the whole chain.  A launch of a few dozen
+ * chains is latency-bound: steps x the latency of one step.  The call allocates, copies and synchronises nothing.
+ * Not done here: a change of box size along a chain, sub-cell refinement, template update. */
+int gcv_track_chain(const void* frames_u8_nhwc, int nframes, int H, int W, const int* jobs11, int n, int max_steps, int grid,
+                    int radius, int* out4, gcv_stream s);
 
 /* Shot cuts: per-region luma histograms of every frame (gcv_frame_hist) and their L1 distance between consecutive frames
  * (gcv_hist_diff).  A whole-video scan links face boxes into tracks by position; after a hard cut the face of another
