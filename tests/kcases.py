@@ -1,8 +1,9 @@
 """One builder per kernel family whose output feeds the verdict: the CPU inputs of a case exactly as the GPU test uploads
 them, the float64 reference, the comparator, an honest float32 model, and the family's planted defects.  The GPU tests
-(tests/test_kernels_gpu.py, tests/test_mlp_bias_init_gpu.py) and the CPU audit (tests/test_kernel_sensitivity_cpu.py) share
-them, so what the audit proves about the comparator and the inputs holds for what the GPU tests assert.  Nothing here
-needs a GPU.
+(tests/test_kernels_gpu.py, tests/test_mlp_bias_init_gpu.py, the softmax cases of tests/test_numerics_gpu.py) and the CPU
+audit (tests/test_kernel_sensitivity_cpu.py) share them, so what the audit proves about the comparator and the inputs
+holds for what the GPU tests assert.  The Swin-T kernels (row A6) are here too, though the verdict does not pass through
+them.  Nothing here needs a GPU.
 
 A builder returns a Case:
   inputs            name -> CPU tensor (fp32 holding values of the storage dtype where the kernel reads that dtype)
@@ -42,6 +43,14 @@ Defects that do not apply to a family (every other entry of the catalogue applie
   reparam          no activation; a slab, the bias, the exponent, eps' row and the two orders z could be left in
   head tail        no b1, slab or activation without the split-K reduce in front
   resize + MSE     no vector term: coordinates, clamps, lerp weights, channel and axis order, and the two MSE reductions
+  window attention no bias vector, gamma, activation or shortcut; its table, index, scale, mask, roll, window and key-order
+                   defects are its own (swin_attn).  Mask and roll defects need a shift, the H-for-W and nWy-for-nWx ones
+                   H != W, the next head's column a second head, the window before a second window, the image before a second
+                   image; table rows 0 and 168 need a window that the mask does not split
+  patch merging    no contraction, no bias in front of the LayerNorm; rows strided by H need H != W
+  token mean       no vector term; the token left out needs L > 1, the image before n > 1, the unwritten last channel a
+                   partly filled 256-column trip (C % 256 != 0)
+  layernorm_rows   no contraction; the padded-width statistics and the padded lanes in the variance need C % 64 != 0
 A family with several outputs (reparam, resize + MSE) is a MultiCase: one comparator per output, a defect counts as rejected
 when any of them rejects it.
 Where a defect names "one" element, it is the vector's last element, the pair (2c, 2c + 1) at c = n // 4, the centre tap of
@@ -68,7 +77,8 @@ NAMES = {F16: "f16", BF16: "bf16", F32: "f32"}
 # thousand times below the smallest planted defect.  "gemm_bias_gelu" carries GeluH16's polynomial, the MLP families that
 # and the hidden values which land on the other side of a rounding step (the LN-patchify epilogue scales both by
 # lw / std of a row, about 4 here).  The small kernels of the verdict path (stem to resize) round an fp32 result once: all
-# at the floor but the bf16 stem, whose matrix-pipe LayerNorm reaches 4.3e-7.
+# at the floor but the bf16 stem, whose matrix-pipe LayerNorm reaches 4.3e-7.  Of the Swin-T kernels the three LayerNorm / mean
+# families are at the floor too; the window attention carries the probabilities that its matrix-pipe kernel rounds to T.
 FP32_ACC = 16 * 2.0 ** -24             # 9.54e-07
 E = {
     ("mlp", BF16): 2.4e-3,             # 8.31e-04
@@ -103,6 +113,14 @@ E = {
     ("reparam", F16): FP32_ACC,        # 6.13e-08
     ("resize", BF16): FP32_ACC,        # 0 (recon; msepart and mse are fp32 with a relative bound, MSE_REL)
     ("resize", F16): FP32_ACC,         # 0
+    ("swin_attn", BF16): 4.9e-3,       # 1.63e-03 (the MFMA kernel rounds exp(s - max) to T in front of P.V; the off-distribution
+    ("swin_attn", F16): 6.6e-4,        # 2.21e-04  softmax cases of tests/test_numerics_gpu.py stay below: 6.0e-04 / 7.0e-05)
+    ("patch_merge_ln", BF16): FP32_ACC,  # 1.70e-07
+    ("patch_merge_ln", F16): FP32_ACC,   # 1.38e-07
+    ("mean_tokens", BF16): FP32_ACC,   # 0
+    ("mean_tokens", F16): FP32_ACC,    # 0
+    ("layernorm_rows", BF16): FP32_ACC,  # 6.31e-08
+    ("layernorm_rows", F16): FP32_ACC,   # 5.97e-08
 }
 SPLITK_BOUND = {F32: 2e-5, BF16: 1e-4, F16: 1e-4}      # fp32 partial sums in every storage dtype: the flat bound as before
 
@@ -1115,3 +1133,325 @@ def resize_mse(B, dtype):
         case.parts[name] = Case("resize", dtype, inp, None, None, None, 1.0, what=f"{what} {name}",
                                 flat=MSE_REL_BEFORE * want[name].abs().max().item(), bound=MSE_REL[name] * want[name].abs())
     return case
+
+
+# ----------------------------------------------------------------------------- Swin-T kernels
+SWIN_SENTINEL = 7.0      # what the GPU tests fill every output buffer with; a defect that leaves an element unwritten leaves this
+
+
+def swin_rel_index():
+    """row of the (169, nH) table for each (query, key) of a 7 x 7 window: (ty - jy + 6) 13 + (tx - jx + 6); (49, 49)"""
+    t = torch.arange(49)
+    dy, dx = t[:, None] // 7 - t[None, :] // 7, t[:, None] % 7 - t[None, :] % 7
+    return (dy + 6) * 13 + (dx + 6)
+
+
+def _swin_axis_regions(n, shift):
+    """region id along one axis of the rolled map, from timm's three slices (0, -7), (-7, -shift), (-shift, end)"""
+    lab = torch.zeros(n, dtype=torch.long)
+    for cnt, s in enumerate((slice(0, -7), slice(-7, -shift), slice(-shift, None))):
+        lab[s] = cnt
+    return lab
+
+
+def _swin_axis_regions_by_compare(n, size, edge):
+    """the same by the kernels' comparisons, with the size the thresholds are taken from and the second edge as parameters
+    (the defects): 0 below size - 7, 1 below edge, else 2"""
+    c = torch.arange(n)
+    return (c >= size - 7).long() + (c >= edge).long() * (c >= size - 7).long()
+
+
+def _swin_windows(t, B, H, W):
+    """(B, H, W, ch) -> (B nWy nWx, 49, ch), windows row-major"""
+    return t.reshape(B, H // 7, 7, W // 7, 7, -1).permute(0, 1, 3, 2, 4, 5).reshape(B * (H // 7) * (W // 7), 49, -1)
+
+
+def _swin_unwindow(t, B, H, W):
+    return t.reshape(B, H // 7, W // 7, 7, 7, -1).permute(0, 1, 3, 2, 4, 5).reshape(B, H, W, -1)
+
+
+def swin_attn_mask(H, W, shift, ly=None, lx=None, value=-100.0):
+    """(nW, 49, 49): `value` between tokens of different regions of the rolled map, else 0"""
+    ly = _swin_axis_regions(H, shift) if ly is None else ly
+    lx = _swin_axis_regions(W, shift) if lx is None else lx
+    mw = _swin_windows((ly[:, None] * 3 + lx[None, :]).reshape(1, H, W, 1), 1, H, W).reshape(-1, 49)
+    differ = mw[:, :, None] != mw[:, None, :]
+    return torch.where(differ, torch.full((), value, dtype=torch.float64), torch.zeros((), dtype=torch.float64))
+
+
+_SWIN_UPPER = (torch.arange(49) & 4) != 0       # keys the MFMA kernel keeps on its upper lane half: kj = .. + 4 lh
+_SWIN_PV_SWAP = torch.tensor([j + 4 if 4 <= j % 16 < 8 else (j - 4 if 8 <= j % 16 < 12 else j) for j in range(49)])
+
+
+def _swin_variant_inputs(inp, variant, B, H, W, C, nH, shift):
+    """the off-distribution inputs of tests/test_numerics_*: built in the rolled frame, where a token's place in its window
+    is fixed, and rolled back"""
+    qkv = inp["qkv"].clone()
+    if variant == "uniform":                    # every unmasked logit 0: a row is the plain mean of its region's V rows
+        qkv[..., :C] = 0
+        return {"qkv": qkv, "table": torch.zeros_like(inp["table"])}
+    j = (torch.arange(H)[:, None] % 7) * 7 + torch.arange(W)[None, :] % 7          # place in the window, rolled frame
+    if variant == "wide":
+        # channel 0 of each head: key j holds a ramp 32 .. -22 over a seeded order of the keys whose top key is on the upper
+        # lane half and whose bottom key on the lower; query j holds +17 (even j) or -17.  Logits 0.177 x 17 x (32 .. -22) = 96
+        # .. -66 for the even queries (exp(96) overflows fp32) and 66 .. -96 for the odd: a span of 162 with the largest
+        # magnitude kept near the 89 an overflow needs.  The other 31 channels of q are zero: each of 31 additions to a partial
+        # sum of magnitude 96 rounds at its spacing of 7.6e-6, two keys of a row that the mask brings within 1 of each other
+        # turn a logit error d into 0.25 d |v1 - v2|, and with random channels the honest float32 model alone came to 3.0e-5 of
+        # fp32 storage's 4e-5.  With one product per logit it stays below 1e-5; the contraction is the benign cases' subject
+        order = torch.randperm(49, generator=torch.Generator().manual_seed(5)).tolist()
+        top = next(k for k in order if k & 4)
+        order.remove(top)
+        bottom = next(k for k in reversed(order) if not k & 4)
+        order.remove(bottom)
+        order = [top] + order + [bottom]
+        ramp = torch.empty(49)
+        ramp[torch.tensor(order)] = 32.0 - 54.0 * torch.arange(49) / 48.0
+        q0, k0 = torch.where(j % 2 == 0, 17.0, -17.0), ramp[j]
+        qkv[..., :C] = 0
+    else:                                       # "mask100": the last key of every window leads the others by 0.177 x 16 x 42.5 = 120
+        q0, k0 = torch.full((H, W), 16.0), torch.where(j == 48, 42.5, 0.0)
+    q0, k0 = (torch.roll(t, shifts=(shift, shift), dims=(0, 1)) for t in (q0, k0))
+    for h in range(nH):
+        qkv[..., h * 32] = q0
+        qkv[..., C + h * 32] = k0
+    return {"qkv": qkv, "table": inp["table"]}
+
+
+def swin_attn(B, H, W, C, nH, shift, dtype, qk_scale=1.5, variant="benign"):
+    """W-MSA / SW-MSA of timm 0.6.5 on a (B, H, W, 3C) qkv tensor, head_dim 32, for any H x W that 7 divides
+    (gcv_k_swin_window_attn): roll by -shift, 7 x 7 windows, softmax(q k^T 32^-0.5 + table[index] + mask) v, windows back,
+    roll by +shift.  q, k and v are U(-1.5, 1.5) (q and k times qk_scale / 1.5).  The table is +-[0.5, 1], rows 0 and 168
+    +[0.5, 1]: each of the two is reached by one (query, key) pair of a window, whose probability p a zeroed entry t moves by
+    p (1 - e^-t) where t > 0 and by e^t times less where t < 0.  At one window and one head that single pair has to show: in bf16
+    +-[0.25, 0.5] left row 168 at 1.3 x the bound there, this at 4.3 x.  Where the shift mask splits every window along an axis
+    (shift != 0 and a single window row or column) the two corner pairs are masked in every window, and zeroing them moves
+    nothing: those two defects are left out there.
+    The model rounds the unnormalised probabilities exp(s - max) to a 16-bit storage dtype in front of P.V and divides by
+    the fp32 sum of the unrounded ones, as swin_window_attn_mfma_kernel does.  `variant`: the inputs of the softmax cases
+    of tests/test_numerics_* ("uniform", "wide", "mask100") with their own defects; case.logits() are the float64 logits
+    with bias and mask (mask=False: without), (B nW, nH, 49, 49)."""
+    nWy, nWx = H // 7, W // 7
+    nW = nWy * nWx
+    qkv = rnd((B, H, W, 3 * C), 1, 1.5)
+    qkv[..., :2 * C] *= qk_scale / 1.5
+    table = signed((169, nH), 2, 0.5, 1.0)
+    table[[0, 168]] = table[[0, 168]].abs()
+    inp = {"qkv": q(qkv, dtype), "table": table}
+    if variant != "benign":
+        inp = _swin_variant_inputs(inp, variant, B, H, W, C, nH, shift)
+        inp["qkv"] = q(inp["qkv"], dtype)
+    index = swin_rel_index()
+    if shift:
+        for n in (H, W):
+            assert torch.equal(_swin_axis_regions(n, shift), _swin_axis_regions_by_compare(n, n, n - shift))
+
+    def logits(i, f=torch.float64, index=index, use_scale=True, mask=None):
+        x = i["qkv"].to(f)
+        if shift:
+            x = torch.roll(x, shifts=(-shift, -shift), dims=(1, 2))
+        qq, kk, vv = _swin_windows(x, B, H, W).reshape(B * nW, 49, 3, nH, 32).permute(2, 0, 3, 1, 4).unbind(0)
+        s = (qq * 32 ** -0.5 if use_scale else qq) @ kk.transpose(-2, -1)
+        s = s + i["table"].to(f)[index.reshape(-1)].reshape(49, 49, nH).permute(2, 0, 1)
+        if shift and mask is not False:
+            m = (swin_attn_mask(H, W, shift) if mask is None else mask).to(f)
+            s = (s.reshape(B, nW, nH, 49, 49) + m[None, :, None]).reshape(B * nW, nH, 49, 49)
+        return s, vv
+
+    def attend(s, vv, f, p_dtype=None, pad_keys=False, lower_half_sum=False, pv_swap=False, half_max=False, no_max=False):
+        if no_max:
+            mx = torch.zeros_like(s[..., :1])
+        elif half_max:
+            up = _SWIN_UPPER.expand_as(s)
+            ninf = torch.full_like(s, -math.inf)
+            mx = torch.where(up, torch.where(up, s, ninf).amax(-1, keepdim=True), torch.where(up, ninf, s).amax(-1, keepdim=True))
+        else:
+            mx = s.amax(-1, keepdim=True)
+            if pad_keys:
+                mx = mx.clamp(min=0)
+        p = torch.exp(s - mx)
+        den = (p[..., ~_SWIN_UPPER] if lower_half_sum else p).sum(-1, keepdim=True)
+        if pad_keys:
+            den = den + 15.0 * torch.exp(-mx)
+        if p_dtype is not None:
+            p = p.to(p_dtype).to(f)
+        pv = p @ (vv[..., _SWIN_PV_SWAP, :] if pv_swap else vv)
+        return pv / den if f == torch.float64 else pv * (1.0 / den)
+
+    def place(o, unroll=True, last_window_prev=False, last_image_prev=False, covered=None):
+        o = o.transpose(1, 2).reshape(B * nW, 49, C)
+        if last_window_prev:
+            o = o.clone()
+            o[-1] = o[-2]
+        if covered is not None:
+            o = o.clone().reshape(B, nW, 49, C)
+            o[:, [w for w in range(nW) if w not in covered]] = SWIN_SENTINEL
+        o = _swin_unwindow(o, B, H, W)
+        if shift and unroll:
+            o = torch.roll(o, shifts=(shift, shift), dims=(1, 2))
+        if last_image_prev:
+            o = o.clone()
+            o[B - 1] = o[B - 2]
+        return o.contiguous()
+
+    def ref(i, lkw=None, akw=None, pkw=None):
+        s, vv = logits(i, **(lkw or {}))
+        return place(attend(s, vv, torch.float64, **(akw or {})), **(pkw or {}))
+
+    def model(i):
+        s, vv = logits(i, torch.float32)
+        return _out(place(attend(s, vv, torch.float32, p_dtype=None if dtype == F32 else dtype)), dtype)
+
+    def no_max_fp32(i):
+        s, vv = logits(i, torch.float32)                    # exp(136) is finite in float64: the defect shows in the kernel's fp32
+        return place(attend(s, vv, torch.float32, no_max=True)).double()
+
+    def table_row_zeroed(r):
+        def f(i):
+            t = i["table"].clone()
+            t[r] = 0
+            return ref(_with(i, table=t))
+        return f
+
+    t49 = torch.arange(49)
+    dy, dx = t49[:, None] // 7 - t49[None, :] // 7, t49[:, None] % 7 - t49[None, :] % 7
+    if variant == "uniform":
+        defects = {"padded_keys_in_the_softmax_sum": lambda i: ref(i, akw={"pad_keys": True})}
+    elif variant == "wide":
+        defects = {"max_taken_per_lane_half": lambda i: ref(i, akw={"half_max": True}), "max_not_subtracted": no_max_fp32}
+    elif variant == "mask100":
+        defects = {"mask_is_minus_inf": lambda i: ref(i, lkw={"mask": swin_attn_mask(H, W, shift, value=-math.inf)})}
+    else:
+        corners_seen = not shift or (nWy > 1 and nWx > 1)
+        defects = {f"table_row_{r}_zeroed": table_row_zeroed(r) for r in (0, 168, 84) if r == 84 or corners_seen}
+        if nH > 1:
+            defects["table_column_of_next_head"] = lambda i: ref(_with(i, table=torch.roll(i["table"], -1, dims=1)))
+        defects["rel_index_transposed"] = lambda i: ref(i, lkw={"index": (dx + 6) * 13 + (dy + 6)})
+        defects["rel_index_negated"] = lambda i: ref(i, lkw={"index": (6 - dy) * 13 + (6 - dx)})
+        defects["scale_omitted"] = lambda i: ref(i, lkw={"use_scale": False})
+        if shift:
+            defects["shift_mask_omitted"] = lambda i: ref(i, lkw={"mask": False})
+            if H != W:
+                lx_h = _swin_axis_regions_by_compare(W, H, H - shift)
+                defects["mask_regions_with_H_on_both_axes"] = lambda i: ref(i, lkw={"mask": swin_attn_mask(H, W, shift, lx=lx_h)})
+            ly_1 = _swin_axis_regions_by_compare(H, H, H - shift - 1)
+            defects["region_edge_off_by_one"] = lambda i: ref(i, lkw={"mask": swin_attn_mask(H, W, shift, ly=ly_1)})
+            defects["reverse_roll_omitted"] = lambda i: ref(i, pkw={"unroll": False})
+        if H != W:
+            # wy = win / nWy, wx = win - wy nWy: some windows are computed twice (the kernels wrap coordinates into the map),
+            # the others never: those keep what the buffer held
+            covered = {((w // nWy) % nWy) * nWx + (w - (w // nWy) * nWy) % nWx for w in range(nW)}
+            assert len(covered) < nW
+            defects["window_index_decomposed_with_nWy"] = lambda i: ref(i, pkw={"covered": covered})
+        defects["padded_keys_in_the_softmax_sum"] = lambda i: ref(i, akw={"pad_keys": True})
+        defects["normaliser_over_one_lane_half"] = lambda i: ref(i, akw={"lower_half_sum": True})
+        defects["pv_keys_4_7_and_8_11_exchanged"] = lambda i: ref(i, akw={"pv_swap": True})
+        if B * nW > 1:
+            defects["last_window_from_window_before"] = lambda i: ref(i, pkw={"last_window_prev": True})
+        if B > 1:
+            defects["last_image_from_image_before"] = lambda i: ref(i, pkw={"last_image_prev": True})
+    case = Case("swin_attn", dtype, inp, ref, model, defects, 2.0,
+                what=f"swin_attn B={B} {H}x{W} C={C} nH={nH} shift={shift}" + ("" if variant == "benign" else f" {variant}"))
+    case.logits = lambda **kw: logits(inp, **kw)[0]
+    return case
+
+
+def patch_merge_ln(C, H, W, n, dtype):
+    """Swin PatchMerging's front half (gcv_k_patch_merge_ln): LayerNorm(4C, eps 1e-5) over timm's concat
+    [x(0::2, 0::2), x(1::2, 0::2), x(0::2, 1::2), x(1::2, 1::2)]; x (n, H, W, C) -> (n, H / 2, W / 2, 4C)"""
+    inp = {"x": q(rnd((n, H, W, C), 1, 2.0), dtype), "lw": signed((4 * C,), 4, 0.5, 1.5), "lb": signed((4 * C,), 5, 0.1, 0.3)}
+
+    def gather(x, patchify_order=False, stride_h=False):
+        if stride_h:                      # pixel (b, y, xx) read at ((b H + y) H + xx) C of the buffer
+            b, y, xx = torch.meshgrid(torch.arange(n), torch.arange(H), torch.arange(W), indexing="ij")
+            x = x.reshape(n * H * W, C)[((b * H + y) * H + xx) % (n * H * W)]
+        parts = [x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 1::2]]
+        if patchify_order:
+            parts = [parts[0], parts[2], parts[1], parts[3]]
+        return torch.cat(parts, -1)
+
+    def ref(i, first_quadrant_stats=False, last_from_prev=False, **kw):
+        d = _d(i)
+        r = gather(d["x"], **kw)
+        if first_quadrant_stats:
+            mean = r[..., :C].mean(-1, keepdim=True)
+            var = ((r[..., :C] - mean) ** 2).mean(-1, keepdim=True)
+            y = (r - mean) / torch.sqrt(var + 1e-5) * d["lw"] + d["lb"]
+        else:
+            y = numutil.ln_ref(r, d["lw"], d["lb"], 1e-5)
+        return _last_from_prev(y) if last_from_prev else y.contiguous()
+
+    def model(i):
+        return _out(F.layer_norm(gather(i["x"]), (4 * C,), i["lw"], i["lb"], 1e-5), dtype)
+
+    defects = {}
+    _vec_defects(defects, inp, ref, ("lw", "lb"))
+    defects["quadrants_dy_dx_swapped"] = lambda i: ref(i, patchify_order=True)
+    if H != W:
+        defects["rows_strided_by_H"] = lambda i: ref(i, stride_h=True)
+    defects["statistics_over_the_first_quadrant"] = lambda i: ref(i, first_quadrant_stats=True)
+    if n * (H // 2) * (W // 2) > 1:
+        defects["last_row_from_row_before"] = lambda i: ref(i, last_from_prev=True)
+    return Case("patch_merge_ln", dtype, inp, ref, model, defects, 3.0, what=f"patch_merge_ln C={C} {H}x{W} n={n}")
+
+
+def mean_tokens(n, L, C, dtype):
+    """mean over the L tokens of each image (gcv_k_mean_tokens): x (n, L, C) -> (n, C)"""
+    inp = {"x": q(rnd((n, L, C), 1, 2.0), dtype)}
+
+    def ref(i, drop_last=False, div_plus_1=False, last_from_prev=False, last_channel_unwritten=False):
+        x = i["x"].double()
+        m = (x[:, :L - 1] if drop_last else x).sum(1) / ((L + 1) if div_plus_1 else L)
+        if last_from_prev:
+            m = m.clone()
+            m[n - 1] = m[n - 2]
+        if last_channel_unwritten:
+            m = m.clone()
+            m[:, C - 1] = SWIN_SENTINEL
+        return m
+
+    def model(i):
+        return _out(i["x"].mean(1), dtype)
+
+    defects = {"mean_divided_by_L_plus_1": lambda i: ref(i, div_plus_1=True)}
+    if L > 1:
+        defects["last_token_left_out_of_the_mean"] = lambda i: ref(i, drop_last=True)
+    if n > 1:
+        defects["last_image_from_image_before"] = lambda i: ref(i, last_from_prev=True)
+    if C % 256:
+        defects["last_channel_of_a_partly_filled_trip_unwritten"] = lambda i: ref(i, last_channel_unwritten=True)
+    return Case("mean_tokens", dtype, inp, ref, model, defects, 1.0, what=f"mean_tokens n={n} L={L} C={C}")
+
+
+def layernorm_rows(rows, C, dtype):
+    """LayerNorm(C, eps 1e-5) of each row (gcv_k_layernorm_rows), any C <= 1536.  Each row carries an offset of +-[0.5, 1]:
+    lanes past C that were counted in the variance as (0 - mean)^2 show only on a row whose mean is not near zero."""
+    inp = {"x": q(rnd((rows, C), 1, 2.0) + signed((rows, 1), 6, 0.5, 1.0), dtype), "lw": signed((C,), 4, 0.5, 1.5),
+           "lb": signed((C,), 5, 0.1, 0.3)}
+    Cp = 64 * -(-C // 64)
+
+    def ref(i, last_from_prev=False, padded_width=False, padded_lanes_in_variance=False):
+        d = _d(i)
+        x = d["x"]
+        n = Cp if padded_width else C
+        mean = x.sum(-1, keepdim=True) / n
+        var = ((x - mean) ** 2).sum(-1, keepdim=True)
+        if padded_lanes_in_variance:
+            var = var + (Cp - C) * mean ** 2
+        y = (x - mean) / torch.sqrt(var / n + 1e-5) * d["lw"] + d["lb"]
+        if last_from_prev:
+            y = y.clone()
+            y[rows - 1] = y[rows - 2]
+        return y
+
+    def model(i):
+        return _out(F.layer_norm(i["x"], (C,), i["lw"], i["lb"], 1e-5), dtype)
+
+    defects = {}
+    _vec_defects(defects, inp, ref, ("lw", "lb"))
+    if rows > 1:
+        defects["last_row_from_row_before"] = lambda i: ref(i, last_from_prev=True)
+    if C % 64:
+        defects["statistics_divided_by_the_padded_width"] = lambda i: ref(i, padded_width=True)
+        defects["padded_lanes_counted_in_the_variance"] = lambda i: ref(i, padded_lanes_in_variance=True)
+    return Case("layernorm_rows", dtype, inp, ref, model, defects, 3.0, what=f"layernorm_rows rows={rows} C={C}")

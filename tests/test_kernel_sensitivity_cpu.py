@@ -100,6 +100,26 @@ CASES = [
     ("head-splitk-relu-37x500x8", kcases.head_tail_splitk, (37, 500, 8, 1), ALL),
     ("head-splitk-gelu-37x500x8", kcases.head_tail_splitk, (37, 500, 8, 2), ALL),
     ("resize-mse-2", kcases.resize_mse, (2,), ALL),
+    # Swin-T (row A6): window attention (B, H, W, C, nH, shift).  16-bit storage runs swin_window_attn_mfma_kernel on aligned
+    # buffers and swin_window_attn_kernel<T> on a misaligned qkv or out: same case, same comparator
+    ("swin-attn-one-window", kcases.swin_attn, (1, 7, 7, 32, 1, 0), ALL),
+    ("swin-attn-14x21-shifted", kcases.swin_attn, (2, 14, 21, 96, 3, 3), ALL),
+    ("swin-attn-21x14", kcases.swin_attn, (2, 21, 14, 96, 3, 0), ALL),
+    ("swin-attn-14x7-shifted", kcases.swin_attn, (2, 14, 7, 64, 2, 3), ALL),
+    ("swin-attn-24-heads", kcases.swin_attn, (1, 7, 7, 768, 24, 0), ALL),
+    ("swin-attn-28x28-shifted", kcases.swin_attn, (2, 28, 28, 192, 6, 3), ALL),
+    ("patch-merge-one-row", kcases.patch_merge_ln, (96, 2, 2, 1), ALL),
+    ("patch-merge-6x10", kcases.patch_merge_ln, (96, 6, 10, 3), ALL),
+    ("patch-merge-384", kcases.patch_merge_ln, (384, 4, 2, 2), ALL),
+    ("patch-merge-192x28x28", kcases.patch_merge_ln, (192, 28, 28, 2), ALL),
+    ("mean-tokens-3x49x768", kcases.mean_tokens, (3, 49, 768), ALL),
+    ("mean-tokens-one-token", kcases.mean_tokens, (2, 1, 96), ALL),
+    ("mean-tokens-3x5x300", kcases.mean_tokens, (3, 5, 300), ALL),
+    ("ln-rows-1x768", kcases.layernorm_rows, (1, 768), ALL),
+    ("ln-rows-5x96", kcases.layernorm_rows, (5, 96), ALL),
+    ("ln-rows-4x100", kcases.layernorm_rows, (4, 100), ALL),
+    ("ln-rows-3x1536", kcases.layernorm_rows, (3, 1536), ALL),
+    ("ln-rows-37x384", kcases.layernorm_rows, (37, 384), ALL),
 ]
 
 
@@ -147,3 +167,25 @@ def test_comparator_accepts_honest_results_and_rejects_every_planted_defect(buil
         if ratio < 2.0:
             missed.append(f"{name} (err/bound {ratio:.2f})")
     assert not missed, f"(c) {case.what}: not rejected by a factor 2: " + ", ".join(missed)
+
+
+def test_swin_reference_is_the_oracles_on_a_square_map():
+    """kcases.swin_attn is written for any H x W; on a square map its index, its mask and its result are those of
+    oracle/cpu_ref.py's restatement of timm (the formula the GPU test used before)"""
+    from oracle.cpu_ref import _swin_attn_mask, _swin_rel_index
+    assert torch.equal(kcases.swin_rel_index(), _swin_rel_index(7))
+    B, H, C, nH, shift, N = 2, 14, 96, 3, 3, 49
+    assert torch.equal(kcases.swin_attn_mask(H, H, shift).float(), _swin_attn_mask(H, H, 7, shift))
+    case = kcases.swin_attn(B, H, H, C, nH, shift, torch.float32)
+    qkv, table = case.inputs["qkv"].double(), case.inputs["table"].double()
+    y = torch.roll(qkv, shifts=(-shift, -shift), dims=(1, 2))
+    yw = y.view(B, H // 7, 7, H // 7, 7, 3 * C).permute(0, 1, 3, 2, 4, 5).reshape(-1, N, 3, nH, C // nH)
+    qq, kk, vv = yw.permute(2, 0, 3, 1, 4).unbind(0)
+    attn = (qq * (C // nH) ** -0.5) @ kk.transpose(-2, -1)
+    attn = attn + table[_swin_rel_index(7).view(-1)].view(N, N, nH).permute(2, 0, 1).unsqueeze(0)
+    m = _swin_attn_mask(H, H, 7, shift).double()
+    attn = (attn.view(B, m.shape[0], nH, N, N) + m.unsqueeze(1).unsqueeze(0)).view(-1, nH, N, N)
+    o = (attn.softmax(-1) @ vv).transpose(1, 2).reshape(-1, N, C)
+    o = o.view(B, H // 7, H // 7, 7, 7, C).permute(0, 1, 3, 2, 4, 5).reshape(B, H, H, C)
+    o = torch.roll(o, shifts=(shift, shift), dims=(1, 2))
+    assert (case.want() - o).abs().max().item() <= 1e-14

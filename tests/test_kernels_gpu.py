@@ -5,7 +5,8 @@ The families that feed the verdict (fused MLPs, the GEMM epilogues, conv-as-GEMM
 frame and the two logits: stem, LN-patchify, pool + LN, first conv, last convT, reparam, head tail, resize + MSE) take inputs,
 float64 reference and per-element comparator from tests/kcases.py; tests/test_kernel_sensitivity_cpu.py shows, without a GPU,
 which planted defects that comparator rejects.  Where a case is meant for one kernel of a launcher, the test asserts the
-launcher's own rule on the pointers, strides and shape it passes.  The Swin kernels keep the fp32 reference and flat bound."""
+launcher's own rule on the pointers, strides and shape it passes.  The Swin-T kernels (window attention, patch merging, token
+mean, layernorm_rows) are on the same builders."""
 import ctypes
 import math
 
@@ -418,18 +419,35 @@ def test_avgpool_layernorm_row_mapping(dt, C, nimg, seg_n, row_stride, row0):
 
 
 
+def _ln_rows_case(dtype, rows, C):
+    """gcv_k_layernorm_rows against kcases.layernorm_rows, the result in the middle of a sentinel-filled buffer: two rows of
+    guard in front and behind.  Where C is no multiple of 64 the buffer is laid out with 64 ceil(C / 64) columns per row; the
+    kernel writes dense rows, so all it may touch is the first rows x C elements behind the front guard."""
+    case = kcases.layernorm_rows(rows, C, dtype)
+    i = case.inputs
+    Cp = 64 * -(-C // 64)
+    buf = torch.full(((rows + 4) * Cp,), SENT, dtype=dtype, device=dev())
+    out = buf[2 * Cp:2 * Cp + rows * C]
+    kutil.call("gcv_k_layernorm_rows", _lib.dtype_code(dtype), ptr(D(i["x"], dtype)), ptr(D(i["lw"])), ptr(D(i["lb"])),
+               ptr(out), rows, C, 1e-5)
+    assert (buf[:2 * Cp].float() == SENT).all(), "written in front of the first row"
+    assert (buf[2 * Cp + rows * C:].float() == SENT).all(), "written behind the last row"
+    case.assert_close(out.reshape(rows, C))
+
+
 @pytest.mark.parametrize("dt", ALL)
 @pytest.mark.parametrize("C", [96, 384, 1536])
 def test_layernorm_rows(dt, C):
-    dtype = DTYPES[dt]
-    rows = 37
-    x = q(rnd((rows, C), 1, 2.0), dtype)
-    lw, lb = rnd((C,), 4, 0.5) + 1.0, rnd((C,), 5, 0.1)
-    want = F.layer_norm(x, (C,), lw, lb, 1e-5)
-    out = torch.zeros((rows, C), dtype=dtype, device=dev())
-    kutil.call("gcv_k_layernorm_rows", _lib.dtype_code(dtype), ptr(D(x, dtype)), ptr(D(lw)),
-               ptr(D(lb)), ptr(out), rows, C, 1e-5)
-    assert_close(out, want, tol(dtype, 3.0), "layernorm_rows")
+    _ln_rows_case(DTYPES[dt], 37, C)
+
+
+@pytest.mark.parametrize("dt", ALL)
+@pytest.mark.parametrize("rows,C", [(1, 768),       # one row: one live wave of the workgroup
+                                    (5, 96),        # a second workgroup with one live wave; half of the second register's lanes
+                                    (4, 100),       # C no multiple of 64: the c < C guards of a partly filled register
+                                    (3, 1536)])     # all 24 registers
+def test_layernorm_rows_one_row_ragged_width_and_full_width(dt, rows, C):
+    _ln_rows_case(DTYPES[dt], rows, C)
 
 
 # ----------------------------------------------------------------------------- AE / VAE small kernels
@@ -674,57 +692,116 @@ def test_errors_are_raised_not_swallowed():
 
 
 # ----------------------------------------------------------------------------- Swin-T pieces (row A6)
+def swin_attn_case(dtype, B, H, W, C, nH, shift, kernel, qkv_off=0, out_off=0, variant="benign"):
+    """gcv_k_swin_window_attn against kcases.swin_attn.  The result lies in the middle of a sentinel-filled buffer, one row
+    of W tokens of guard in front and behind; the whole buffer is sentinel before the launch, so a token that is never
+    written shows too.  `qkv_off` / `out_off`: the tensor starts that many elements into its allocation.  `kernel` ("mfma" /
+    "valu") is asserted by launch_swin_window_attn's own rule (csrc/kernels_impl.h): swin_window_attn_mfma_kernel for 16-bit
+    storage when `(qkv & 15) == 0 && (out & 7) == 0 && C % 8 == 0`, else swin_window_attn_kernel<T>.  Also used by
+    tests/test_numerics_gpu.py."""
+    case = kcases.swin_attn(B, H, W, C, nH, shift, dtype, variant=variant)
+    i = case.inputs
+    n_in, n_out, guard = B * H * W * 3 * C, B * H * W * C, W * C
+    qbuf = torch.zeros((n_in + 8,), dtype=dtype, device=dev())
+    qkv = qbuf[qkv_off:qkv_off + n_in]
+    qkv.copy_(i["qkv"].reshape(-1).to(dev(), dtype))
+    obuf = torch.full((n_out + 2 * guard + 8,), SENT, dtype=dtype, device=dev())
+    out = obuf[guard + out_off:guard + out_off + n_out]
+    mfma = dtype != torch.float32 and qkv.data_ptr() % 16 == 0 and out.data_ptr() % 8 == 0 and C % 8 == 0
+    assert mfma == (kernel == "mfma"), f"this launch does not reach the {kernel} kernel"
+    kutil.call("gcv_k_swin_window_attn", _lib.dtype_code(dtype), ptr(qkv), ptr(D(i["table"])), ptr(out), B, H, W, C, nH, shift)
+    assert (obuf[:guard + out_off].float() == SENT).all(), "written in front of the first token"
+    assert (obuf[guard + out_off + n_out:].float() == SENT).all(), "written behind the last token"
+    got = out.reshape(B, H, W, C)
+    assert torch.isfinite(got.float()).all(), "non-finite attention output"
+    case.assert_close(got)
+    return case
+
+
+def _attn_kernel(dtype):
+    return "valu" if dtype == torch.float32 else "mfma"
+
+
 @pytest.mark.parametrize("dt", ALL)
 @pytest.mark.parametrize("H,C,nH,shift", [(14, 96, 3, 0), (14, 96, 3, 3), (28, 192, 6, 3), (7, 768, 24, 0)])
 def test_swin_window_attention(dt, H, C, nH, shift):
-    """W-MSA / SW-MSA (timm 0.6.5 WindowAttention + cyclic shift + mask) on a (B,H,W,3C) qkv tensor."""
-    from oracle.cpu_ref import _swin_attn_mask, _swin_rel_index
+    """W-MSA / SW-MSA (timm 0.6.5 WindowAttention + cyclic shift + mask) on a (B,H,W,3C) qkv tensor: the network's square maps"""
     dtype = DTYPES[dt]
-    B, ws, N = 2, 7, 49
-    qkv = q(rnd((B, H, H, 3 * C), 1, 1.5), dtype)
-    table = rnd((169, nH), 2, 0.5)
-    y = qkv
-    if shift:
-        y = torch.roll(y, shifts=(-shift, -shift), dims=(1, 2))
-    yw = y.view(B, H // ws, ws, H // ws, ws, 3 * C).permute(0, 1, 3, 2, 4, 5).reshape(-1, N, 3, nH, C // nH)
-    qq, kk, vv = yw.permute(2, 0, 3, 1, 4).unbind(0)
-    attn = (qq * (C // nH) ** -0.5) @ kk.transpose(-2, -1)
-    attn = attn + table[_swin_rel_index(ws).view(-1)].view(N, N, nH).permute(2, 0, 1).unsqueeze(0)
-    if shift:
-        m = _swin_attn_mask(H, H, ws, shift)
-        attn = (attn.view(B, m.shape[0], nH, N, N) + m.unsqueeze(1).unsqueeze(0)).view(-1, nH, N, N)
-    o = (attn.softmax(-1) @ vv).transpose(1, 2).reshape(-1, N, C)
-    o = o.view(B, H // ws, H // ws, ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(B, H, H, C)
-    if shift:
-        o = torch.roll(o, shifts=(shift, shift), dims=(1, 2))
-    out = torch.zeros((B, H, H, C), dtype=dtype, device=dev())
-    kutil.call("gcv_k_swin_window_attn", _lib.dtype_code(dtype), ptr(D(qkv, dtype)), ptr(D(table)), ptr(out), B, H, H, C,
-               nH, shift)
-    assert_close(out, o, tol(dtype, 2.0), "window attention")
+    swin_attn_case(dtype, 2, H, H, C, nH, shift, _attn_kernel(dtype))
+
+
+@pytest.mark.parametrize("dt", ALL)
+@pytest.mark.parametrize("B,H,W,C,nH,shift", [
+    (1, 7, 7, 32, 1, 0),        # one window, one head
+    (2, 14, 21, 96, 3, 3),      # off-square, nWy != nWx, all nine mask regions
+    (2, 21, 14, 96, 3, 0),      # the other orientation, unshifted
+    (2, 14, 7, 64, 2, 3),       # shift 3 at W = 7 (the launcher only requires H > 7): x region 0 is empty
+    (1, 7, 7, 768, 24, 0),      # the table's head stride at the largest nH
+])
+def test_swin_window_attention_off_square_maps(dt, B, H, W, C, nH, shift):
+    """fp32 storage on swin_window_attn_kernel, 16-bit on swin_window_attn_mfma_kernel"""
+    dtype = DTYPES[dt]
+    swin_attn_case(dtype, B, H, W, C, nH, shift, _attn_kernel(dtype))
+
+
+@pytest.mark.parametrize("dt", H16)
+@pytest.mark.parametrize("qkv_off,out_off", [(1, 0),       # qkv 2-byte aligned: (qkv & 15) != 0
+                                             (0, 2)])      # out 4 bytes into its allocation: (out & 7) != 0
+def test_swin_window_attention_valu_kernel_in_16bit_storage(dt, qkv_off, out_off):
+    """swin_window_attn_kernel<half_t> / <bf16_t>: the launcher takes it for 16-bit storage only when
+    `(qkv & 15) == 0 && (out & 7) == 0 && C % 8 == 0` fails, which a fresh allocation never does"""
+    swin_attn_case(DTYPES[dt], 2, 14, 21, 96, 3, 3, "valu", qkv_off=qkv_off, out_off=out_off)
+
+
+def _patch_merge_case(dtype, C, H, W, n):
+    """gcv_k_patch_merge_ln against kcases.patch_merge_ln; two rows of sentinel in front of and behind the result"""
+    case = kcases.patch_merge_ln(C, H, W, n, dtype)
+    i = case.inputs
+    rows = n * (H // 2) * (W // 2)
+    buf = torch.full((rows + 4, 4 * C), SENT, dtype=dtype, device=dev())
+    kutil.call("gcv_k_patch_merge_ln", _lib.dtype_code(dtype), ptr(D(i["x"], dtype)), ptr(D(i["lw"])), ptr(D(i["lb"])),
+               ptr(buf[2:]), n, H, W, C, 1e-5)
+    assert (buf[:2].float() == SENT).all() and (buf[rows + 2:].float() == SENT).all(), "written outside the merged rows"
+    case.assert_close(buf[2:rows + 2].reshape(n, H // 2, W // 2, 4 * C))
 
 
 @pytest.mark.parametrize("dt", ALL)
 @pytest.mark.parametrize("C,H", [(96, 56), (192, 28), (384, 14)])
 def test_swin_patch_merging_layernorm(dt, C, H):
-    dtype = DTYPES[dt]
-    n = 2
-    x = q(rnd((n, H, H, C), 1, 2.0), dtype)
-    lw, lb = rnd((4 * C,), 4, 0.5) + 1.0, rnd((4 * C,), 5, 0.1)
-    y = torch.cat([x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 1::2]], -1)
-    want = F.layer_norm(y, (4 * C,), lw, lb, 1e-5)
-    out = torch.zeros((n, H // 2, H // 2, 4 * C), dtype=dtype, device=dev())
-    kutil.call("gcv_k_patch_merge_ln", _lib.dtype_code(dtype), ptr(D(x, dtype)), ptr(D(lw)), ptr(D(lb)), ptr(out), n, H,
-               H, C, 1e-5)
-    assert_close(out, want, tol(dtype, 3.0), "patch merging")
+    _patch_merge_case(DTYPES[dt], C, H, H, 2)
+
+
+@pytest.mark.parametrize("dt", ALL)
+@pytest.mark.parametrize("C,H,W,n", [(96, 2, 2, 1),        # one row
+                                     (96, 6, 10, 3),       # off-square; 45 rows: the last workgroup has one live wave
+                                     (384, 4, 2, 2)])      # 4C = 1536: all 24 registers
+def test_swin_patch_merging_layernorm_one_row_off_square_and_widest(dt, C, H, W, n):
+    _patch_merge_case(DTYPES[dt], C, H, W, n)
+
+
+def _mean_tokens_case(dtype, n, L, C):
+    """gcv_k_mean_tokens against kcases.mean_tokens.  The buffer has 256 ceil(C / 256) columns per image and two images of
+    guard in front and behind; the kernel writes dense rows: the first n x C elements behind the front guard"""
+    case = kcases.mean_tokens(n, L, C, dtype)
+    Cp = 256 * -(-C // 256)
+    buf = torch.full(((n + 4) * Cp,), SENT, dtype=dtype, device=dev())
+    out = buf[2 * Cp:2 * Cp + n * C]
+    kutil.call("gcv_k_mean_tokens", _lib.dtype_code(dtype), ptr(D(case.inputs["x"], dtype)), ptr(out), n, L, C)
+    assert (buf[:2 * Cp].float() == SENT).all(), "written in front of the first image"
+    assert (buf[2 * Cp + n * C:].float() == SENT).all(), "written behind the last image"
+    case.assert_close(out.reshape(n, C))
 
 
 @pytest.mark.parametrize("dt", ALL)
 def test_mean_over_tokens(dt):
-    dtype = DTYPES[dt]
-    x = q(rnd((3, 49, 768), 1, 2.0), dtype)
-    out = torch.zeros((3, 768), dtype=dtype, device=dev())
-    kutil.call("gcv_k_mean_tokens", _lib.dtype_code(dtype), ptr(D(x, dtype)), ptr(out), 3, 49, 768)
-    assert_close(out, x.mean(1), tol(dtype, 1.0), "mean tokens")
+    _mean_tokens_case(DTYPES[dt], 3, 49, 768)
+
+
+@pytest.mark.parametrize("dt", ALL)
+@pytest.mark.parametrize("n,L,C", [(2, 1, 96),        # one token; less than one trip of the 256-stride loop
+                                   (3, 5, 300)])      # a second trip with 44 live threads
+def test_mean_over_tokens_one_token_and_ragged_width(dt, n, L, C):
+    _mean_tokens_case(DTYPES[dt], n, L, C)
 
 
 # ----------------------------------------------------------------------------- fused ConvNeXt MLP

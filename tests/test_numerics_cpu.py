@@ -3,7 +3,7 @@ restatement of the device formula with one planted defect, and on the unmodified
 import pytest
 import torch
 
-from tests import numutil as nu
+from tests import kcases, numutil as nu
 
 torch.set_grad_enabled(False)
 
@@ -91,3 +91,44 @@ def test_layernorm_constant_bound_rejects_a_mean_of_16bit_precision():
         e16 = (bad.double() - b.double()).abs().max().item()
         print(f"constant rows {dtype}: bound {bound:.3e}  centred {e2:.3e}  2^-12 mean {e16:.3e}")
         assert e2 <= bound and not e16 <= bound
+
+
+# ----------------------------------------------------------------------------- softmax of the Swin window attention
+_ATTN = (2, 14, 21, 96, 3, 3)
+_UPPER = (torch.arange(49) & 4) != 0       # keys on the MFMA kernel's upper lane half
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16], ids=["f32", "f16", "bf16"])
+@pytest.mark.parametrize("variant", ["uniform", "wide", "mask100"])
+def test_softmax_cases_are_what_they_claim_and_reject_their_defects(variant, dtype):
+    """The off-distribution softmax cases of tests/test_numerics_gpu.py (kcases.swin_attn's variants): the inputs have the
+    property each case is named for, the honest float32 model passes the family's comparator, and every defect planted in
+    the float64 restatement (the missing maximum in float32, where it overflows) is rejected by a factor 2."""
+    case = kcases.swin_attn(*_ATTN, dtype, variant=variant)
+    s = case.logits()
+    if variant == "uniform":
+        assert ((s == 0) | (s == -100)).all() and (s == -100).any()
+    elif variant == "wide":
+        span = s.amax(-1) - s.amin(-1)
+        upper = _UPPER[s.argmax(-1)].double().mean().item()
+        print(f"wide: logit span {span.min().item():.1f} .. {span.max().item():.1f}, largest logit {s.max().item():.1f}, "
+              f"row maximum on the upper lane half in {upper:.2f} of the rows")
+        assert span.min().item() >= 150 and 0.3 <= upper <= 0.7
+        assert s.max().item() > 89, "exp of the largest logit must overflow fp32 for the missing maximum to show"
+    else:
+        plain = case.logits(mask=False)
+        others = torch.arange(49) != 48
+        lead = plain[..., 48] - plain[..., others].amax(-1)
+        masked = (s[..., 48] < plain[..., 48] - 99)
+        kept = s[..., 48] - s[..., others].amax(-1)
+        print(f"mask100: key 48 leads by {lead.min().item():.1f} .. {lead.max().item():.1f} before the mask, by at least "
+              f"{kept.min().item():.1f} after it; masked in {masked.double().mean().item():.2f} of the rows")
+        assert 110 <= lead.min().item() and lead.max().item() <= 130 and kept.min().item() >= 10 and masked.any()
+    want = case.want()
+    m = case.measure(case.model(case.inputs), want)
+    print(f"{case.what}: honest fp32 model err/bound {m['ratio']:.2f}, excess {m['excess']:.3e}")
+    assert m["ratio"] <= 1.0
+    for name, planted in case.defects.items():
+        m = case.measure(case.to_storage(planted(case.inputs)), want)
+        print(f"  {name:36s} max err {m['err']:.3e}  err/bound {m['ratio']:.1f}")
+        assert m["ratio"] >= 2.0, f"{case.what}: {name} passes (err/bound {m['ratio']:.2f})"

@@ -1,6 +1,7 @@
 """Numerics off the benign input distribution (every other kernel test draws U(-1, 1) * scale): the GELU of every site that
 evaluates one, swept over every finite value of the storage dtype through identity weights, and the LayerNorm of every
-kernel that computes one, on rows with a large common offset, a tiny or large scale, and no variance at all.  References are
+kernel that computes one, on rows with a large common offset, a tiny or large scale, and no variance at all, and the softmax
+of the Swin window attention on uniform rows, on rows whose logits span 270, and where a masked key still wins.  References are
 float64; the bounds (tests/numutil.py) are rounding terms plus a measured allowance, and tests/test_numerics_cpu.py shows
 without a GPU that each of them rejects a defective restatement of the device formula.  Every case prints what it measured."""
 import ctypes
@@ -416,3 +417,27 @@ def test_layernorm_conditioning_patch_merge_ln(dt):
         return o[:n], rows, lw, lb, 1e-5
 
     _run_families(dt, "patch_merge_ln", run, x_fed=True)
+
+
+# ============================================================================= C. Softmax of the Swin window attention
+_ATTN = (2, 14, 21, 96, 3, 3)
+# fp32 storage runs swin_window_attn_kernel; 16-bit storage swin_window_attn_mfma_kernel, and swin_window_attn_kernel<T> when
+# qkv starts one element into its allocation (tests/test_kernels_gpu.py, swin_attn_case)
+_ATTN_SITES = [("f32", "valu"), ("bf16", "mfma"), ("bf16", "valu"), ("f16", "mfma"), ("f16", "valu")]
+
+
+@pytest.mark.parametrize("dt,kernel", _ATTN_SITES)
+@pytest.mark.parametrize("variant", ["uniform", "wide", "mask100"])
+def test_softmax_off_distribution_swin_window_attn(variant, dt, kernel):
+    """gcv_k_swin_window_attn at (B, H, W, C, nH, shift) = (2, 14, 21, 96, 3, 3) on the inputs of kcases.swin_attn's variants,
+    with the family's comparator against float64, sentinels around the result, and a finite result required:
+      uniform   q = 0 and a zero table: every row is the plain mean of its region's V rows; a padded key counted in the
+                sum shows at its largest
+      wide      logits from -136 to 136 in every row, the maximum on the upper lane half of the MFMA kernel (key index bit 2)
+                for the even queries and on the lower for the odd: a maximum taken per half, or none subtracted (inf / nan)
+      mask100   the last key of each window leads the others by 120: masked by -100 it still carries the row, where a kernel
+                that masks with -inf returns the softmax of the in-region keys
+    tests/test_numerics_cpu.py checks those properties of the inputs and that the comparator rejects each defect."""
+    from tests.test_kernels_gpu import swin_attn_case
+    dtype = DTYPES[dt]
+    swin_attn_case(dtype, *_ATTN, kernel, qkv_off=1 if (kernel == "valu" and dt != "f32") else 0, variant=variant)
