@@ -12,6 +12,8 @@
 #include <sstream>
 #include <vector>
 
+#include "cam.h"
+#include "cam_bwd.h"
 #include "cnx_mlp.h"
 #include "gemm.h"
 #include "kernels.h"
@@ -718,6 +720,70 @@ int gcv_k_patch_merge_ln(int dtype, const void* x, const float* w, const float* 
 
 int gcv_k_mean_tokens(int dtype, const void* x, void* out, int nimg, int L, int C, gcv_stream s) {
   DISPATCH_DT(dtype, launch_mean_tokens<T>((const T*)x, (T*)out, nimg, L, C, (hipStream_t)s));
+}
+
+// Grad-CAM backward kernels (cam.h, cam_bwd.h): the launchers' argument structs are filled here from flat arguments
+int gcv_k_head_bwd(int dtype, const float* partial, int S, const float* b1, const float* fc2_w, const float* logits,
+                   const int* target, const void* fc_w, const void* bb_pre, float* dfeat, int B, int act, gcv_stream s) {
+  const HeadBwdArgs a{partial, S, b1, fc2_w, logits, target, fc_w, bb_pre, dfeat, B, act};
+  DISPATCH_DT(dtype, launch_head_bwd<T>(a, (hipStream_t)s));
+}
+
+int gcv_k_bb_bwd(int dtype, const float* dfeat, const void* w, float* dpool, int rows, int C, gcv_stream s) {
+  DISPATCH_DT(dtype, launch_bb_bwd<T>(dfeat, w, dpool, rows, C, (hipStream_t)s));
+}
+
+int gcv_k_cam(int dtype, int C, int npass, const void* A0, const void* A1, int side0, int side1, int off0, int off1,
+              int cam_ld, int up_pass, const float* lnw, const float* dpool, float* cam, float* cam224, float eps, int B,
+              gcv_stream s) {
+  CamArgs a{};
+  a.A[0] = A0; a.A[1] = A1; a.side[0] = side0; a.side[1] = side1; a.hw[0] = side0 * side0; a.hw[1] = side1 * side1;
+  a.cam_off[0] = off0; a.cam_off[1] = off1; a.npass = npass; a.cam_ld = cam_ld; a.up_pass = up_pass; a.lnw = lnw;
+  a.dpool = dpool; a.cam = cam; a.cam224 = cam224; a.eps = eps; a.B = B;
+  DISPATCH_DT(dtype, launch_cam<T>(a, C, (hipStream_t)s));
+}
+
+int gcv_k_pool_ln_bwd(int dtype, int C, int npass, const void* A0, const void* A1, int hw0, int hw1, int tok0_0,
+                      int tok0_1, const float* lnw, const float* dpool, float* dA, float eps, int B, gcv_stream s) {
+  PoolLnBwdArgs a{};
+  a.A[0] = A0; a.A[1] = A1; a.hw[0] = hw0; a.hw[1] = hw1; a.tok0[0] = tok0_0; a.tok0[1] = tok0_1; a.npass = npass;
+  a.B = B; a.lnw = lnw; a.dpool = dpool; a.dA = dA; a.eps = eps;
+  DISPATCH_DT(dtype, launch_pool_ln_bwd<T>(a, C, (hipStream_t)s));
+}
+
+int gcv_k_scale_rows(int dtype, const float* g, const float* gamma, void* out, float* inv, int M, int C, gcv_stream s) {
+  DISPATCH_DT(dtype, launch_scale_rows<T>(g, gamma, (T*)out, inv, M, C, (hipStream_t)s));
+}
+
+int gcv_k_gelu_bwd(int dtype, const float* dh, const float* inv_in, void* pre, float* inv_out, int M, int C4,
+                   gcv_stream s) {
+  DISPATCH_DT(dtype, launch_gelu_bwd<T>(dh, inv_in, (T*)pre, inv_out, M, C4, (hipStream_t)s));
+}
+
+int gcv_k_dw_ln_bwd(int dtype, const void* x, const float* dw_w, const float* dw_b, const float* ln_w, const float* dxln,
+                    const float* inv, float* ddw, int nimg, int side, int C, float eps, gcv_stream s) {
+  const DwLnBwdArgs a{x, dw_w, dw_b, ln_w, dxln, inv, ddw, nimg, side, eps};
+  DISPATCH_DT(dtype, launch_dw_ln_bwd<T>(a, C, (hipStream_t)s));
+}
+
+int gcv_k_dw_dgrad_res(const float* ddw, const float* dw_w, float* g, int nimg, int side, int C, gcv_stream s) {
+  return launch_dw_dgrad_res(ddw, dw_w, g, nimg, side, C, (hipStream_t)s);
+}
+
+int gcv_k_down_ln_bwd(int dtype, const void* x, const float* ln_w, const float* dP, const float* inv, float* dA2,
+                      int nimg, int side2, int C2, float eps, gcv_stream s) {
+  const DownLnBwdArgs a{x, ln_w, dP, inv, dA2, nimg, side2, eps};
+  DISPATCH_DT(dtype, launch_down_ln_bwd<T>(a, C2, (hipStream_t)s));
+}
+
+int gcv_k_cam2(int dtype, int C2, int npass, const void* A0, const void* A1, const float* dA0, const float* dA1,
+               int side0, int side1, int off0, int off1, int cam_ld, int up_pass, float* cam, float* cam224, float* alpha,
+               int B, gcv_stream s) {
+  Cam2Args a{};
+  a.A[0] = A0; a.A[1] = A1; a.dA2[0] = dA0; a.dA2[1] = dA1; a.side[0] = side0; a.side[1] = side1; a.cam_off[0] = off0;
+  a.cam_off[1] = off1; a.npass = npass; a.cam_ld = cam_ld; a.up_pass = up_pass; a.B = B; a.cam = cam; a.cam224 = cam224;
+  a.alpha = alpha;
+  DISPATCH_DT(dtype, launch_cam2<T>(a, C2, (hipStream_t)s));
 }
 
 int gcv_preprocess(int dtype, const void* frames_u8_nhwc, void* out_nchw, int n, int H, int W, gcv_stream s) {

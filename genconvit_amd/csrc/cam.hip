@@ -187,6 +187,7 @@ __global__ void __launch_bounds__(256) cam_kernel(CamArgs p) {
 
 template <typename T> int launch_head_bwd(const HeadBwdArgs& a, hipStream_t s) {
   GCV_REQUIRE(a.B > 0 && a.S >= 1, "head_bwd: empty");
+  GCV_REQUIRE(a.partial && a.b1 && a.fc2_w && (a.target || a.logits) && a.fc_w && a.bb_pre && a.dfeat, "head_bwd: null operand");
   const dim3 grid(cdiv(a.B, kRB), cdiv(2000, 64));
   if (a.act == ACT_GELU) hipLaunchKernelGGL((head_bwd_kernel<T, ACT_GELU>), grid, dim3(256), 0, s, a);
   else if (a.act == ACT_RELU) hipLaunchKernelGGL((head_bwd_kernel<T, ACT_RELU>), grid, dim3(256), 0, s, a);
@@ -197,6 +198,7 @@ template <typename T> int launch_head_bwd(const HeadBwdArgs& a, hipStream_t s) {
 
 template <typename T> int launch_bb_bwd(const float* dfeat, const void* W, float* dpool, int rows, int C, hipStream_t s) {
   GCV_REQUIRE(rows > 0 && (C == 768 || C == 1536), "bb_bwd: empty, or C not 768 / 1536");
+  GCV_REQUIRE(dfeat && W && dpool, "bb_bwd: null operand");
   if (C == 768)
     hipLaunchKernelGGL((bb_bwd_kernel<T, 768>), dim3(cdiv(rows, kRB), 768 / 64), dim3(256), 0, s, dfeat, (const T*)W, dpool, rows);
   else
@@ -209,6 +211,7 @@ template <typename T> int launch_cam(const CamArgs& a, int C, hipStream_t s) {
   GCV_REQUIRE(a.B > 0 && a.npass >= 1 && a.npass <= 2 && (C == 768 || C == 1536), "cam: empty, or C not 768 / 1536");
   for (int q = 0; q < a.npass; ++q)
     GCV_REQUIRE(a.A[q] && a.side[q] >= 1 && a.side[q] * a.side[q] == a.hw[q] && a.hw[q] <= 49, "cam: stage-3 map of at most 7 x 7");
+  GCV_REQUIRE(a.lnw && a.dpool && a.cam, "cam: null operand");
   if (C == 768) hipLaunchKernelGGL((cam_kernel<T, 768>), dim3(a.B, a.npass), dim3(256), 0, s, a);
   else hipLaunchKernelGGL((cam_kernel<T, 1536>), dim3(a.B, a.npass), dim3(256), 0, s, a);
   GCV_CHECK_HIP(hipGetLastError());

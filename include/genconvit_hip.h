@@ -602,6 +602,30 @@ int gcv_k_patch_merge_ln(int dtype, const void* x, const float* w, const float* 
                          int C, float eps, gcv_stream s);
 int gcv_k_mean_tokens(int dtype, const void* x, void* out, int nimg, int L, int C, gcv_stream s);
 
+/* Grad-CAM backward kernels, one launch each (csrc/cam.h, csrc/cam_bwd.h; the chains are gcv_*_explain and gcv_*_explain_at).
+ * Gradients are fp32 in every storage dtype; x, A, fc_w, bb_pre, w, and the `out` of scale_rows / `pre` of gelu_bwd are in the
+ * storage dtype.  target, gamma and cam224 may be null.  Pass p's map of image b lands at cam + b * cam_ld + off_p; a launch with
+ * npass = 1 ignores the second pass's arguments. */
+int gcv_k_head_bwd(int dtype, const float* partial, int S, const float* b1, const float* fc2_w, const float* logits,
+                   const int* target, const void* fc_w, const void* bb_pre, float* dfeat, int B, int act, gcv_stream s);
+int gcv_k_bb_bwd(int dtype, const float* dfeat, const void* w, float* dpool, int rows, int C, gcv_stream s);
+int gcv_k_cam(int dtype, int C, int npass, const void* A0, const void* A1, int side0, int side1, int off0, int off1,
+              int cam_ld, int up_pass, const float* lnw, const float* dpool, float* cam, float* cam224, float eps, int B,
+              gcv_stream s);
+int gcv_k_pool_ln_bwd(int dtype, int C, int npass, const void* A0, const void* A1, int hw0, int hw1, int tok0_0,
+                      int tok0_1, const float* lnw, const float* dpool, float* dA, float eps, int B, gcv_stream s);
+int gcv_k_scale_rows(int dtype, const float* g, const float* gamma, void* out, float* inv, int M, int C, gcv_stream s);
+int gcv_k_gelu_bwd(int dtype, const float* dh, const float* inv_in, void* pre, float* inv_out, int M, int C4,
+                   gcv_stream s);
+int gcv_k_dw_ln_bwd(int dtype, const void* x, const float* dw_w, const float* dw_b, const float* ln_w, const float* dxln,
+                    const float* inv, float* ddw, int nimg, int side, int C, float eps, gcv_stream s);
+int gcv_k_dw_dgrad_res(const float* ddw, const float* dw_w, float* g, int nimg, int side, int C, gcv_stream s);
+int gcv_k_down_ln_bwd(int dtype, const void* x, const float* ln_w, const float* dP, const float* inv, float* dA2,
+                      int nimg, int side2, int C2, float eps, gcv_stream s);
+int gcv_k_cam2(int dtype, int C2, int npass, const void* A0, const void* A1, const float* dA0, const float* dA1,
+               int side0, int side1, int off0, int off1, int cam_ld, int up_pass, float* cam, float* cam224, float* alpha,
+               int B, gcv_stream s);
+
 /* Fused ConvNeXt MLP for C = 96 / 192, 16-bit storage:
  * out = resid + gamma * (W2 . GELU(W1 . x + b1) + b2) with the 4C hidden activation kept on chip
  * (timm ConvNeXtBlock: mlp.fc1 -> GELU -> mlp.fc2 -> * gamma -> + shortcut).  w2_f32: (C,4C) fp32 device. */

@@ -3,7 +3,8 @@ them, the float64 reference, the comparator, an honest float32 model, and the fa
 (tests/test_kernels_gpu.py, tests/test_mlp_bias_init_gpu.py, the softmax cases of tests/test_numerics_gpu.py) and the CPU
 audit (tests/test_kernel_sensitivity_cpu.py) share them, so what the audit proves about the comparator and the inputs
 holds for what the GPU tests assert.  The Swin-T kernels (row A6) are here too, though the verdict does not pass through
-them.  Nothing here needs a GPU.
+them.  The ten Grad-CAM backward kernels have their builders in tests/camcases.py, on the Case / MultiCase of this module and
+with their e in E below (their GPU tests: tests/test_cam_kernels_gpu.py).  Nothing here needs a GPU.
 
 A builder returns a Case:
   inputs            name -> CPU tensor (fp32 holding values of the storage dtype where the kernel reads that dtype)
@@ -25,7 +26,8 @@ its factor.  The shortcut of the residual families is |res| <= 0.25 so that the 
 branch's smallest term.
 
 Defects that do not apply to a family (every other entry of the catalogue applies):
-  split-K          no bias, gamma, activation or shortcut: contraction and row defects only (plus a K index at a split edge)
+  split-K          no bias, gamma, activation or shortcut: contraction and row defects only (plus a K index at a split edge,
+                   where there is one: the backward contractions' launch is one split of the whole K)
   GEMM bias/act    no gamma, no shortcut, no branch to scale; ReLU-for-LeakyReLU only where the activation is LeakyReLU;
                    activation-omitted only where there is one
   POOL4 / CONVT    no gamma, no shortcut; CONVT has no pool, POOL4's activation is ReLU
@@ -121,6 +123,39 @@ E = {
     ("mean_tokens", F16): FP32_ACC,    # 0
     ("layernorm_rows", BF16): FP32_ACC,  # 6.31e-08
     ("layernorm_rows", F16): FP32_ACC,   # 5.97e-08
+    # the Grad-CAM backward kernels (tests/camcases.py): fp32 outputs against e s, s the scale of the element or row.  Measured:
+    # largest |got - want64| / s over the family's cases, for the T outputs of scale_rows / gelu_bwd the excess over half a step.
+    # All at the floor but dw_ln_bwd: its case of a constant depthwise bias 0.25 and a token variance of eps' size holds
+    # deviations of 1e-3 on 0.25, where one fp32 rounding of the raw conv output is 3e-5 of the deviation; the other dw_ln_bwd
+    # cases stay at 2.2e-07.
+    ("head_bwd", F32): FP32_ACC,        # 5.87e-08
+    ("head_bwd", BF16): FP32_ACC,       # 6.47e-08
+    ("head_bwd", F16): FP32_ACC,        # 7.55e-08
+    ("bb_bwd", F32): FP32_ACC,          # 7.05e-08
+    ("bb_bwd", BF16): FP32_ACC,         # 7.55e-08
+    ("bb_bwd", F16): FP32_ACC,          # 6.37e-08
+    ("pool_ln_bwd", F32): FP32_ACC,     # 1.96e-07
+    ("pool_ln_bwd", BF16): FP32_ACC,    # 1.65e-07
+    ("pool_ln_bwd", F16): FP32_ACC,     # 1.77e-07
+    ("cam", F32): FP32_ACC,             # 1.70e-08
+    ("cam", BF16): FP32_ACC,            # 1.74e-08
+    ("cam", F16): FP32_ACC,             # 1.87e-08
+    ("scale_rows", F32): FP32_ACC,      # below 0: never past half a step
+    ("scale_rows", BF16): FP32_ACC,     # below 0: never past half a step
+    ("scale_rows", F16): FP32_ACC,      # below 0: never past half a step
+    ("gelu_bwd", F32): FP32_ACC,        # 3.52e-08
+    ("gelu_bwd", BF16): FP32_ACC,       # 9.87e-11
+    ("gelu_bwd", F16): FP32_ACC,        # 4.45e-09
+    ("dw_ln_bwd", F32): 5.6e-06,        # 1.86e-06
+    ("dw_ln_bwd", BF16): 6.0e-06,       # 1.99e-06
+    ("dw_ln_bwd", F16): 5.0e-06,        # 1.63e-06
+    ("dw_dgrad_res", F32): FP32_ACC,    # 2.89e-07
+    ("down_ln_bwd", F32): FP32_ACC,     # 1.98e-07
+    ("down_ln_bwd", BF16): FP32_ACC,    # 2.19e-07
+    ("down_ln_bwd", F16): FP32_ACC,     # 2.31e-07
+    ("cam2", F32): FP32_ACC,            # 1.22e-07
+    ("cam2", BF16): FP32_ACC,           # 1.22e-07
+    ("cam2", F16): FP32_ACC,            # 1.22e-07
 }
 SPLITK_BOUND = {F32: 2e-5, BF16: 1e-4, F16: 1e-4}      # fp32 partial sums in every storage dtype: the flat bound as before
 
@@ -309,7 +344,7 @@ def gemm(epi, M, N, K, dtype, act=0, k_per_split=0):
         return f
 
     ks = k_indices(K)
-    if epi == "splitk":
+    if epi == "splitk" and k_per_split < K:              # one split of the whole K has no split edge
         ks["k_split_edge"] = k_per_split
     defects = {name: zero_k(k) for name, k in ks.items()}
     for vec in ("bias", "gamma"):

@@ -1,5 +1,6 @@
 """Do the per-kernel GPU tests notice a kernel that is subtly wrong?  Answered without a GPU, on the builders the GPU tests
-use (tests/kcases.py): per family, storage dtype and the family's smallest case per dispatch class,
+use (tests/kcases.py, and tests/camcases.py for the Grad-CAM backward kernels): per family, storage dtype and the family's
+smallest case per dispatch class,
   (a) the float64 reference rounded to the storage dtype passes the comparator,
   (b) an honest float32 model passes it (float32 torch matmul / conv; the 16-bit GELU through numutil.gelu_h16_ref),
   (c) every defect of the family's catalogue is rejected, with some element at least 2 x over its bound.
@@ -10,7 +11,7 @@ kcases.E, and err / bound of every defect."""
 import pytest
 import torch
 
-from tests import kcases
+from tests import camcases, kcases
 from tests.kutil import DTYPES
 
 torch.set_grad_enabled(False)
@@ -120,7 +121,14 @@ CASES = [
     ("ln-rows-4x100", kcases.layernorm_rows, (4, 100), ALL),
     ("ln-rows-3x1536", kcases.layernorm_rows, (3, 1536), ALL),
     ("ln-rows-37x384", kcases.layernorm_rows, (37, 384), ALL),
+    # the backward contractions' launch shape: one split of the whole K (no split edge to drop an index at)
+    ("splitk-one-split-13x3072x768", lambda M, N, K, kps, dt: kcases.gemm("splitk", M, N, K, dt, k_per_split=kps),
+     (13, 3072, 768, 768), ALL),
+    ("splitk-one-split-13x768x3072", lambda M, N, K, kps, dt: kcases.gemm("splitk", M, N, K, dt, k_per_split=kps),
+     (13, 768, 3072, 3072), ALL),
 ]
+# the Grad-CAM backward kernels: the cases of tests/test_cam_kernels_gpu.py, every one of them (tests/camcases.py)
+CASES += camcases.CASES
 
 
 def _tokens(segs):
@@ -167,6 +175,19 @@ def test_comparator_accepts_honest_results_and_rejects_every_planted_defect(buil
         if ratio < 2.0:
             missed.append(f"{name} (err/bound {ratio:.2f})")
     assert not missed, f"(c) {case.what}: not rejected by a factor 2: " + ", ".join(missed)
+
+
+@pytest.mark.parametrize("name", [name for name, *_ in camcases.CASES])
+def test_cam_closed_forms_equal_the_autograd_reference(name):
+    """The float32 models and the defects of tests/camcases.py are closed forms; the reference is autograd.  Run in float64 the
+    closed form equals the reference to 1e-12 of each output's largest magnitude (gaps hold the sentinel in both)."""
+    case = camcases.build(name, torch.float32)
+    got, want = case.closed64(), case.want()
+    assert set(got) == set(want)
+    for out, w in want.items():
+        rel = ((got[out].double() - w).abs().max() / w.abs().max().clamp(min=1e-300)).item()
+        print(f"{case.what} {out}: closed form against autograd {rel:.2e}")
+        assert rel <= 1e-12, f"{case.what} {out}: {rel:.2e}"
 
 
 def test_swin_reference_is_the_oracles_on_a_square_map():

@@ -6,7 +6,8 @@ frame and the two logits: stem, LN-patchify, pool + LN, first conv, last convT, 
 float64 reference and per-element comparator from tests/kcases.py; tests/test_kernel_sensitivity_cpu.py shows, without a GPU,
 which planted defects that comparator rejects.  Where a case is meant for one kernel of a launcher, the test asserts the
 launcher's own rule on the pointers, strides and shape it passes.  The Swin-T kernels (window attention, patch merging, token
-mean, layernorm_rows) are on the same builders."""
+mean, layernorm_rows) are on the same builders.  The Grad-CAM backward kernels are on builders of the same kind in
+tests/camcases.py; their per-kernel tests are tests/test_cam_kernels_gpu.py."""
 import ctypes
 import math
 
