@@ -562,19 +562,26 @@ class Comm:
             pass
 
 
+def _check_frames(frames_u8, expects, least=0, on_device=True):
+    """``frames_u8`` as a contiguous uint8 (F,H,W,3) tensor, F >= ``least``, on a device unless ``on_device`` is False (the
+    caller then looks at the device itself), and (F, H, W); anything else is an error that says ``expects``."""
+    import torch
+    if not (torch.is_tensor(frames_u8) and (frames_u8.is_cuda or not on_device) and frames_u8.dtype == torch.uint8
+            and frames_u8.dim() == 4 and frames_u8.shape[3] == 3 and frames_u8.shape[0] >= least):
+        raise GenConViTHipError(expects)
+    return frames_u8.contiguous(), tuple(int(v) for v in frames_u8.shape[:3])
+
+
 def preprocess(frames_u8, dtype=None):
     """Device-side ``preprocess_frame`` (model/pred_func.py:95-108): uint8 (N,H,W,3) device tensor ->
     normalised (N,3,H,W) tensor of ``dtype`` (fp32 by default, like the reference)."""
     import torch
-    lib = load()
     dtype = dtype or torch.float32
-    if not (frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3):
-        raise GenConViTHipError("preprocess expects a uint8 device tensor of shape (N,H,W,3)")
-    frames_u8 = frames_u8.contiguous()
-    n, h, w, _ = frames_u8.shape
+    frames_u8, (n, h, w) = _check_frames(frames_u8, "preprocess expects a uint8 device tensor of shape (N,H,W,3)")
+    code = dtype_code(dtype)
     out = torch.empty((n, 3, h, w), dtype=dtype, device=frames_u8.device)
-    check(lib.gcv_preprocess(dtype_code(dtype), frames_u8.data_ptr(), out.data_ptr(), n, h, w,
-                             current_stream_ptr(frames_u8.device)), "gcv_preprocess")
+    check(load().gcv_preprocess(code, frames_u8.data_ptr(), out.data_ptr(), n, h, w, current_stream_ptr(frames_u8.device)),
+          "gcv_preprocess")
     return out
 
 
@@ -584,12 +591,9 @@ def face_crop_resize(frames_u8, boxes, size=224):
     ``boxes``: (n,5) integers (frame index, top, right, bottom, left).  Returns (n,size,size,3) uint8 on the device.
     Boxes outside their frame are an error here (the kernel itself would write zeros for them)."""
     import torch
-    lib = load()
-    if not (frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3):
-        raise GenConViTHipError("face_crop_resize expects a uint8 device tensor of shape (F,H,W,3)")
-    frames_u8 = frames_u8.contiguous()
-    nf, h, w, _ = frames_u8.shape
+    frames_u8, (nf, h, w) = _check_frames(frames_u8, "face_crop_resize expects a uint8 device tensor of shape (F,H,W,3)")
     b = _check_boxes("face_crop_resize", boxes, nf, h, w)
+    lib = load()
     out = torch.empty((b.shape[0], size, size, 3), dtype=torch.uint8, device=frames_u8.device)
     if b.shape[0] == 0:
         return out
@@ -605,14 +609,11 @@ def face_crop_preprocess(frames_u8, boxes, size=224, dtype=None):
     ``dtype`` (fp32 by default) with no uint8 image in between.  Boxes as for ``face_crop_resize``: one outside its frame
     is an error, none give an empty tensor."""
     import torch
-    lib = load()
     dtype = dtype or torch.float32
-    if not (frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3):
-        raise GenConViTHipError("face_crop_preprocess expects a uint8 device tensor of shape (F,H,W,3)")
-    frames_u8 = frames_u8.contiguous()
-    nf, h, w, _ = frames_u8.shape
+    frames_u8, (nf, h, w) = _check_frames(frames_u8, "face_crop_preprocess expects a uint8 device tensor of shape (F,H,W,3)")
     b = _check_boxes("face_crop_preprocess", boxes, nf, h, w)
     code = dtype_code(dtype)
+    lib = load()
     out = torch.empty((b.shape[0], 3, size, size), dtype=dtype, device=frames_u8.device)
     if b.shape[0] == 0:
         return out
@@ -658,6 +659,16 @@ def _check_track_jobs(what, jobs, nf, h, w, grid):
     return j
 
 
+def _check_grid_radius(what, grid, radius):
+    """(grid, radius) as integers; a grid outside ``TRACK_GRIDS`` and a radius outside 0 ... ``TRACK_RADIUS_MAX`` are errors."""
+    grid, radius = int(grid), int(radius)
+    if grid not in TRACK_GRIDS:
+        raise GenConViTHipError(f"{what}: grid {grid}; accepted values are 16, 32 and 64")
+    if not 0 <= radius <= TRACK_RADIUS_MAX:
+        raise GenConViTHipError(f"{what}: radius {radius} outside 0 ... {TRACK_RADIUS_MAX}")
+    return grid, radius
+
+
 def track_match(frames_u8, jobs, grid=64, radius=16):
     """Where is the face in a frame the detector skipped (``gcv_track_match``, include/genconvit_hip.h: the arithmetic is
     stated there): integer block matching on a ``grid`` x ``grid`` lattice of mean-luma cells, searched ``radius`` cells
@@ -667,18 +678,10 @@ def track_match(frames_u8, jobs, grid=64, radius=16):
     device: (oy, ox, best cost, cost at zero displacement) with (oy, ox) the pixel offset to add to the prior box.  A
     ``grid`` other than 16, 32, 64, a ``radius`` outside 0 ... 32 and a bad row are errors; none give an empty tensor."""
     import torch
-    lib = load()
-    if not (torch.is_tensor(frames_u8) and frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4
-            and frames_u8.shape[3] == 3):
-        raise GenConViTHipError("track_match expects a uint8 device tensor of shape (F,H,W,3)")
-    grid, radius = int(grid), int(radius)
-    if grid not in TRACK_GRIDS:
-        raise GenConViTHipError(f"track_match: grid {grid}; accepted values are 16, 32 and 64")
-    if not 0 <= radius <= TRACK_RADIUS_MAX:
-        raise GenConViTHipError(f"track_match: radius {radius} outside 0 ... {TRACK_RADIUS_MAX}")
-    frames_u8 = frames_u8.contiguous()
-    nf, h, w, _ = frames_u8.shape
+    frames_u8, (nf, h, w) = _check_frames(frames_u8, "track_match expects a uint8 device tensor of shape (F,H,W,3)")
+    grid, radius = _check_grid_radius("track_match", grid, radius)
     j = _check_track_jobs("track_match", jobs, nf, h, w, grid)
+    lib = load()
     n = j.shape[0]
     out = torch.empty((n, 4), dtype=torch.int32, device=frames_u8.device)
     if n == 0:
@@ -722,18 +725,10 @@ def track_chain(frames_u8, jobs, grid=64, radius=8):
     relative to that step's prior, and (0, 0, -1, -1) from the step that exceeded ``stop``, and from ``steps``, on.  A ``grid``
     other than 16, 32, 64, a ``radius`` outside 0 ... 32 and a bad row are errors; no rows give an empty (0, 0, 4) tensor."""
     import torch
-    lib = load()
-    if not (torch.is_tensor(frames_u8) and frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4
-            and frames_u8.shape[3] == 3):
-        raise GenConViTHipError("track_chain expects a uint8 device tensor of shape (F,H,W,3)")
-    grid, radius = int(grid), int(radius)
-    if grid not in TRACK_GRIDS:
-        raise GenConViTHipError(f"track_chain: grid {grid}; accepted values are 16, 32 and 64")
-    if not 0 <= radius <= TRACK_RADIUS_MAX:
-        raise GenConViTHipError(f"track_chain: radius {radius} outside 0 ... {TRACK_RADIUS_MAX}")
-    frames_u8 = frames_u8.contiguous()
-    nf, h, w, _ = frames_u8.shape
+    frames_u8, (nf, h, w) = _check_frames(frames_u8, "track_chain expects a uint8 device tensor of shape (F,H,W,3)")
+    grid, radius = _check_grid_radius("track_chain", grid, radius)
     j = _check_chain_jobs("track_chain", jobs, nf, h, w, grid)
+    lib = load()
     n = j.shape[0]
     if n == 0:
         return torch.empty((0, 0, 4), dtype=torch.int32, device=frames_u8.device)
@@ -755,16 +750,12 @@ def face_quality(frames_u8, boxes, grid=64):
     frame and a box lower or narrower than ``grid`` are errors here, before anything is launched (the zeros row is the C
     entry's guard); none give an empty tensor."""
     import torch
-    lib = load()
     grid = int(grid)
     if grid not in TRACK_GRIDS:
         raise GenConViTHipError(f"face_quality: grid {grid}; accepted values are 16, 32 and 64")
-    if not (torch.is_tensor(frames_u8) and frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4
-            and frames_u8.shape[3] == 3):
-        raise GenConViTHipError("face_quality expects a uint8 device tensor of shape (F,H,W,3)")
-    frames_u8 = frames_u8.contiguous()
-    nf, h, w, _ = frames_u8.shape
+    frames_u8, (nf, h, w) = _check_frames(frames_u8, "face_quality expects a uint8 device tensor of shape (F,H,W,3)")
     b = _check_quality_boxes("face_quality", boxes, nf, h, w, grid)
+    lib = load()
     n = b.shape[0]
     out = torch.empty((n, 8), dtype=torch.int64, device=frames_u8.device)
     if n == 0:
@@ -796,13 +787,9 @@ def face_signature(frames_u8, boxes):
     left).  Returns (n,384) uint8 on the device.  A box outside its frame and a box lower or narrower than 16 pixels are
     errors here, before anything is launched (the zeros row is the C entry's guard); none give an empty tensor."""
     import torch
-    lib = load()
-    if not (torch.is_tensor(frames_u8) and frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4
-            and frames_u8.shape[3] == 3):
-        raise GenConViTHipError("face_signature expects a uint8 device tensor of shape (F,H,W,3)")
-    frames_u8 = frames_u8.contiguous()
-    nf, h, w, _ = frames_u8.shape
+    frames_u8, (nf, h, w) = _check_frames(frames_u8, "face_signature expects a uint8 device tensor of shape (F,H,W,3)")
     b = _check_quality_boxes("face_signature", boxes, nf, h, w, SIG_GRID)
+    lib = load()
     n = b.shape[0]
     out = torch.empty((n, SIG_BYTES), dtype=torch.uint8, device=frames_u8.device)
     if n == 0:
@@ -844,10 +831,10 @@ def sig_link(sig, owner, tracks):
     outside [-1, T), a host tensor and a wrong shape are errors here, before anything is launched; no row or T = 0
     launches nothing."""
     import torch
-    lib = load()
     o, tracks = _check_sig_link("sig_link", sig, owner, tracks)
     if not sig.is_cuda:
         raise GenConViTHipError("sig_link expects the signatures as a device tensor")
+    lib = load()
     n = sig.shape[0]
     if n == 0 or tracks == 0:
         return torch.full((tracks, tracks), SIG_NONE, dtype=torch.int64, device=sig.device)
@@ -864,6 +851,17 @@ def sig_link(sig, owner, tracks):
 CUT_REGIONS, CUT_BINS = (1, 2, 4, 8), 64
 
 
+def _out_buffer(what, out, shape, device):
+    """``out`` if it is a contiguous int32 tensor of ``shape`` on ``device``, a new one for None, else an error."""
+    import torch
+    if out is None:
+        return torch.empty(shape, dtype=torch.int32, device=device)
+    if not (torch.is_tensor(out) and out.dtype == torch.int32 and out.device == device and tuple(out.shape) == shape
+            and out.is_contiguous()):
+        raise GenConViTHipError(f"{what}: out must be a contiguous int32 tensor of shape {shape} on {device}")
+    return out
+
+
 def frame_hist(frames_u8, regions=4, out=None):
     """Luma histograms of the ``regions`` x ``regions`` parts of every frame (``gcv_frame_hist``, include/genconvit_hip.h: the
     arithmetic is stated there).  ``frames_u8``: (F,H,W,3) uint8 device tensor (RGB), F >= 1; a slice such as ``frames[1:]``
@@ -872,28 +870,26 @@ def frame_hist(frames_u8, regions=4, out=None):
     shape on the same device instead of a new one (the rows of one group of frames in a whole video's buffer).  ``regions``
     other than 1, 2, 4, 8, a frame lower or narrower than ``regions``, more than 2^30 pixels a frame, a host tensor and a
     wrong shape or dtype are errors."""
-    import torch
-    if not (torch.is_tensor(frames_u8) and frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4
-            and frames_u8.shape[3] == 3 and frames_u8.shape[0] >= 1):
-        raise GenConViTHipError("frame_hist expects a uint8 device tensor of shape (F,H,W,3), F >= 1")
+    frames_u8, (nf, h, w) = _check_frames(frames_u8, "frame_hist expects a uint8 device tensor of shape (F,H,W,3), F >= 1", 1)
     if isinstance(regions, bool) or not isinstance(regions, int) or regions not in CUT_REGIONS:
         raise GenConViTHipError(f"frame_hist: regions {regions}; accepted values are 1, 2, 4 and 8")
-    frames_u8 = frames_u8.contiguous()
-    nf, h, w, _ = frames_u8.shape
     if h < regions or w < regions or h * w > 1 << 30:
         raise GenConViTHipError(f"frame_hist: frames of {h}x{w} pixels; each side must be at least regions = {regions} and "
                                 f"a frame hold at most 2^30 pixels")
-    shape = (nf, regions * regions, CUT_BINS)
-    if out is None:
-        hist = torch.empty(shape, dtype=torch.int32, device=frames_u8.device)
-    elif (torch.is_tensor(out) and out.dtype == torch.int32 and out.device == frames_u8.device and tuple(out.shape) == shape
-          and out.is_contiguous()):
-        hist = out
-    else:
-        raise GenConViTHipError(f"frame_hist: out must be a contiguous int32 tensor of shape {shape} on {frames_u8.device}")
+    hist = _out_buffer("frame_hist", out, (nf, regions * regions, CUT_BINS), frames_u8.device)
     check(load().gcv_frame_hist(frames_u8.data_ptr(), nf, h, w, regions, hist.data_ptr(), current_stream_ptr(frames_u8.device)),
           "gcv_frame_hist")
     return hist
+
+
+def _check_hist(what, hist):
+    """``hist`` as a contiguous int32 (F, R^2, 64) device tensor, F >= 1, and (F, R^2, the R its shape implies)."""
+    import torch
+    squares = [r * r for r in CUT_REGIONS]
+    if not (torch.is_tensor(hist) and hist.is_cuda and hist.dtype == torch.int32 and hist.dim() == 3
+            and hist.shape[0] >= 1 and hist.shape[2] == CUT_BINS and hist.shape[1] in squares):
+        raise GenConViTHipError(f"{what} expects an int32 device tensor of shape (F, R^2, 64), F >= 1, R in 1, 2, 4, 8")
+    return hist.contiguous(), int(hist.shape[0]), int(hist.shape[1]), CUT_REGIONS[squares.index(hist.shape[1])]
 
 
 def hist_diff(hist):
@@ -902,15 +898,11 @@ def hist_diff(hist):
     is launched).  A distance is at most twice the region's pixel count; the one value that does not fit int32, 2^31 (a
     whole frame of 2^30 pixels at R = 1 with disjoint histograms), reads -2^31: view the tensor's numpy array as uint32."""
     import torch
-    if not (torch.is_tensor(hist) and hist.is_cuda and hist.dtype == torch.int32 and hist.dim() == 3
-            and hist.shape[0] >= 1 and hist.shape[2] == CUT_BINS and hist.shape[1] in [r * r for r in CUT_REGIONS]):
-        raise GenConViTHipError("hist_diff expects an int32 device tensor of shape (F, R^2, 64), F >= 1, R in 1, 2, 4, 8")
-    hist = hist.contiguous()
-    nf, rr, _ = hist.shape
+    hist, nf, rr, regions = _check_hist("hist_diff", hist)
     dist = torch.empty((nf - 1, rr), dtype=torch.int32, device=hist.device)
     if nf > 1:
-        check(load().gcv_hist_diff(hist.data_ptr(), nf, CUT_REGIONS[[r * r for r in CUT_REGIONS].index(rr)], dist.data_ptr(),
-                                current_stream_ptr(hist.device)), "gcv_hist_diff")
+        check(load().gcv_hist_diff(hist.data_ptr(), nf, regions, dist.data_ptr(), current_stream_ptr(hist.device)),
+              "gcv_hist_diff")
     return dist
 
 
@@ -918,17 +910,13 @@ def hist_diff_lag(hist, lag):
     """``hist_diff`` between frames p and p + ``lag`` (``gcv_hist_diff_lag``): (max(F - lag, 0), R^2) int32 on the device,
     nothing launched when it is empty.  ``lag``: an integer >= 1; ``lag`` = 1 is ``hist_diff``."""
     import torch
-    if not (torch.is_tensor(hist) and hist.is_cuda and hist.dtype == torch.int32 and hist.dim() == 3
-            and hist.shape[0] >= 1 and hist.shape[2] == CUT_BINS and hist.shape[1] in [r * r for r in CUT_REGIONS]):
-        raise GenConViTHipError("hist_diff_lag expects an int32 device tensor of shape (F, R^2, 64), F >= 1, R in 1, 2, 4, 8")
+    hist, nf, rr, regions = _check_hist("hist_diff_lag", hist)
     if isinstance(lag, bool) or not isinstance(lag, int) or lag < 1:
         raise GenConViTHipError(f"hist_diff_lag: lag {lag} must be an integer >= 1")
-    hist = hist.contiguous()
-    nf, rr, _ = hist.shape
     dist = torch.empty((max(nf - lag, 0), rr), dtype=torch.int32, device=hist.device)
     if nf > lag:
-        check(load().gcv_hist_diff_lag(hist.data_ptr(), nf, CUT_REGIONS[[r * r for r in CUT_REGIONS].index(rr)], lag,
-                                    dist.data_ptr(), current_stream_ptr(hist.device)), "gcv_hist_diff_lag")
+        check(load().gcv_hist_diff_lag(hist.data_ptr(), nf, regions, lag, dist.data_ptr(), current_stream_ptr(hist.device)),
+              "gcv_hist_diff_lag")
     return dist
 
 
@@ -943,25 +931,13 @@ def frame_cells(frames_u8, grid=16, out=None):
     of one group of frames in a whole video's buffer).  ``grid`` other than 8, 16, 32, a frame lower or narrower than
     ``grid``, more than 2^25 pixels a frame (the bound that keeps ``blend_fit``'s 64-bit sums exact), a host tensor and a
     wrong shape or dtype are errors."""
-    import torch
-    if not (torch.is_tensor(frames_u8) and frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4
-            and frames_u8.shape[3] == 3 and frames_u8.shape[0] >= 1):
-        raise GenConViTHipError("frame_cells expects a uint8 device tensor of shape (F,H,W,3), F >= 1")
+    frames_u8, (nf, h, w) = _check_frames(frames_u8, "frame_cells expects a uint8 device tensor of shape (F,H,W,3), F >= 1", 1)
     if isinstance(grid, bool) or not isinstance(grid, int) or grid not in CELL_GRIDS:
         raise GenConViTHipError(f"frame_cells: grid {grid}; accepted values are 8, 16 and 32")
-    frames_u8 = frames_u8.contiguous()
-    nf, h, w, _ = frames_u8.shape
     if h < grid or w < grid or h * w > CELL_MAX_PIXELS:
         raise GenConViTHipError(f"frame_cells: frames of {h}x{w} pixels; each side must be at least grid = {grid} and a "
                                 f"frame hold at most 2^25 pixels")
-    shape = (nf, grid * grid)
-    if out is None:
-        cells = torch.empty(shape, dtype=torch.int32, device=frames_u8.device)
-    elif (torch.is_tensor(out) and out.dtype == torch.int32 and out.device == frames_u8.device and tuple(out.shape) == shape
-          and out.is_contiguous()):
-        cells = out
-    else:
-        raise GenConViTHipError(f"frame_cells: out must be a contiguous int32 tensor of shape {shape} on {frames_u8.device}")
+    cells = _out_buffer("frame_cells", out, (nf, grid * grid), frames_u8.device)
     check(load().gcv_frame_cells(frames_u8.data_ptr(), nf, h, w, grid, cells.data_ptr(), current_stream_ptr(frames_u8.device)),
           "gcv_frame_cells")
     return cells
@@ -1013,11 +989,9 @@ def cam_overlay(frames_u8, boxes, maps, alpha=0.5, weighted=True, lut=None, out=
     ``weighted``; ``lut``: (256,3) uint8 colours (default ``jet_lut``); ``out``: a contiguous tensor like the frames to
     write into (``out=frames_u8`` draws in place).  Returns the (F,H,W,3) uint8 frames with the overlays drawn."""
     import torch
-    lib = load()
-    if not (torch.is_tensor(frames_u8) and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3):
-        raise GenConViTHipError("cam_overlay: frames must be a uint8 device tensor of shape (F,H,W,3)")
+    src, (nf, h, w) = _check_frames(frames_u8, "cam_overlay: frames must be a uint8 device tensor of shape (F,H,W,3)",
+                                    on_device=False)
     dev = frames_u8.device
-    nf, h, w, _ = frames_u8.shape
     b = _check_boxes("cam_overlay", boxes, nf, h, w)
     n = b.shape[0]
     if not (torch.is_tensor(maps) and maps.is_floating_point() and maps.device == dev and maps.dim() == 3):
@@ -1040,9 +1014,10 @@ def cam_overlay(frames_u8, boxes, maps, alpha=0.5, weighted=True, lut=None, out=
     elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.shape == frames_u8.shape and out.device == dev
               and out.is_contiguous()):
         raise GenConViTHipError(f"cam_overlay: out must be a contiguous uint8 tensor of shape {tuple(frames_u8.shape)} on {dev}")
+    lib = load()
     if nf * h * w == 0:
         return out
-    src, maps, lut, bd = frames_u8.contiguous(), maps.float().contiguous(), lut.contiguous(), b.to(dev)
+    maps, lut, bd = maps.float().contiguous(), lut.contiguous(), b.to(dev)
     check(lib.gcv_cam_overlay(src.data_ptr(), nf, h, w, bd.data_ptr() if n else None, n, maps.data_ptr() if n else None,
                               mh, mw, lut.data_ptr(), float(alpha), 1 if weighted else 0, out.data_ptr(),
                               current_stream_ptr(dev)), "gcv_cam_overlay")
@@ -1069,7 +1044,6 @@ def vote_windows(logits, batch, nets, ranges):
     overlap, nest, repeat and come in any order (lo < 0, hi > batch or lo > hi is an error).  Returns ``(frame_p, mean2)``:
     (batch,2) fp32 mean over nets of sigmoid per frame, and (n,2) fp32 mean of it over each range (0.5 for an empty one)."""
     import torch
-    lib = load()
     batch, nets = int(batch), int(nets)
     if not (torch.is_tensor(logits) and logits.is_cuda):
         raise GenConViTHipError("vote_windows expects the logits as a device tensor")
@@ -1086,8 +1060,8 @@ def vote_windows(logits, batch, nets, ranges):
     frame_p = torch.empty((batch, 2), dtype=torch.float32, device=logits.device)
     mean2 = torch.empty((n, 2), dtype=torch.float32, device=logits.device)
     rd = r.contiguous().to(logits.device)
-    check(lib.gcv_vote_windows(logits.data_ptr(), batch, nets, rd.data_ptr() if n else None, n, frame_p.data_ptr(),
-                               mean2.data_ptr() if n else None, current_stream_ptr(logits.device)), "gcv_vote_windows")
+    check(load().gcv_vote_windows(logits.data_ptr(), batch, nets, rd.data_ptr() if n else None, n, frame_p.data_ptr(),
+                                  mean2.data_ptr() if n else None, current_stream_ptr(logits.device)), "gcv_vote_windows")
     return frame_p, mean2
 
 

@@ -11,6 +11,7 @@ dependencies (dlib, face_recognition, decord) are imported lazily inside the vid
 functions so the model path imports on a box without them; cv2 is not needed any more (the crop +
 INTER_AREA resize of ``face_rec`` runs on the device, row N4).
 """
+import collections
 import os
 
 import numpy as np
@@ -184,9 +185,7 @@ def explain_frames(frames, model, boxes=None, locate=None, eps=None, target=None
     on the device; ``boxes``: the list used.  No face: ``((None, None), the frames on the device, [])``, nothing is run."""
     if which not in ("ed", "vae", "mean"):
         raise ValueError(f"unknown map {which!r}: accepted values are 'ed', 'vae' and 'mean'")
-    fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
-    if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
-        raise _lib.GenConViTHipError("explain_frames: frames must be uint8 of shape (F,H,W,3)")
+    fr = _as_frames("explain_frames", frames)
     if boxes is None:
         boxes = (locate or face_locations)(frames)
     boxes = list(boxes)[:len(fr)]
@@ -223,6 +222,28 @@ def window_ranges(length, window, stride):
     if starts[-1] != length - window:
         starts.append(length - window)
     return [(s, s + window) for s in starts]
+
+
+def _as_frames(what, frames):
+    """``frames`` (numpy or a tensor on either device) as a tensor; anything but uint8 (F,H,W,3) is an error."""
+    fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
+    if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
+        raise _lib.GenConViTHipError(f"{what}: frames must be uint8 of shape (F,H,W,3)")
+    return fr
+
+
+def _upload(fr, used, dev):
+    """What one group of a stage needs of ``fr``: the frames ``used`` (frame numbers, sorted) as a slab on ``dev``, and the map
+    from frame number to slab row.  Which rows make a group is each stage's own business."""
+    return fr.index_select(0, torch.as_tensor(used, device=fr.device)).to(dev), {f: k for k, f in enumerate(used)}
+
+
+def _is_whole(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _is_number(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and bool(np.isfinite(v))
 
 
 def _box_iou(a, b):
@@ -313,9 +334,7 @@ def follow_tracks(frames, tracks, anchors, grid=64, radius=16, max_frames=128, d
     _check_follow("follow_tracks", grid, radius)
     if max_frames < 3:
         raise ValueError(f"follow_tracks: max_frames {max_frames} must be at least 3 (a job reads three frames)")
-    fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
-    if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
-        raise _lib.GenConViTHipError("follow_tracks: frames must be uint8 of shape (F,H,W,3)")
+    fr = _as_frames("follow_tracks", frames)
     big = lambda b: b[3] - b[1] >= grid and b[2] - b[4] >= grid
     jobs = []                                               # (track, index in the track, the 17 integers)
     for t, (tr, flags) in enumerate(zip(tracks, anchors)):
@@ -348,9 +367,7 @@ def follow_tracks(frames, tracks, anchors, grid=64, radius=16, max_frames=128, d
             groups[-1].append(n)
             used |= need
         for ids in groups:
-            used = sorted({jobs[n][2][c] for n in ids for c in (0, 5, 11)})
-            at = {f: k for k, f in enumerate(used)}
-            slab = fr.index_select(0, torch.as_tensor(used)).to(dev or device)
+            slab, at = _upload(fr, sorted({jobs[n][2][c] for n in ids for c in (0, 5, 11)}), dev or device)
             rows = [tuple(at[v] if c in (0, 5, 11) else v for c, v in enumerate(jobs[n][2])) for n in ids]
             res[ids] = _lib.track_match(slab, rows, grid=grid, radius=radius).cpu().numpy()
     for n, (t, i, row) in enumerate(jobs):
@@ -366,13 +383,11 @@ EXTEND_DEFAULTS = dict(grid=64, radius=8, steps=16, cost_max=18.7)
 
 def _check_extend(what, grid=EXTEND_DEFAULTS["grid"], radius=EXTEND_DEFAULTS["radius"], steps=EXTEND_DEFAULTS["steps"],
                   cost_max=EXTEND_DEFAULTS["cost_max"]):
-    whole = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
-    if not (whole(grid) and grid in _lib.TRACK_GRIDS and whole(radius) and 0 <= radius <= _lib.TRACK_RADIUS_MAX):
+    if not (_is_whole(grid) and grid in _lib.TRACK_GRIDS and _is_whole(radius) and 0 <= radius <= _lib.TRACK_RADIUS_MAX):
         raise ValueError(f"{what}: grid {grid} must be 16, 32 or 64 and radius {radius} lie in 0 ... {_lib.TRACK_RADIUS_MAX}")
-    if not (whole(steps) and 1 <= steps <= _lib.TRACK_CHAIN_STEPS_MAX):
+    if not (_is_whole(steps) and 1 <= steps <= _lib.TRACK_CHAIN_STEPS_MAX):
         raise ValueError(f"{what}: steps {steps} must be an integer in 1 ... {_lib.TRACK_CHAIN_STEPS_MAX}")
-    if not (isinstance(cost_max, (int, float, np.integer, np.floating)) and not isinstance(cost_max, bool) and
-            0 <= cost_max <= 255):
+    if not (_is_number(cost_max) and 0 <= cost_max <= 255):
         raise ValueError(f"{what}: cost_max {cost_max} must be a number in 0 ... 255 (grey levels per cell)")
 
 
@@ -416,9 +431,7 @@ def extend_tracks(frames, tracks, ends=None, grid=EXTEND_DEFAULTS["grid"], radiu
     if max_frames < 2:
         raise ValueError(f"extend_tracks: max_frames {max_frames} must be at least 2 (a chain reads its template's frame and a "
                          f"frame to search)")
-    fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
-    if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
-        raise _lib.GenConViTHipError("extend_tracks: frames must be uint8 of shape (F,H,W,3)")
+    fr = _as_frames("extend_tracks", frames)
     nf = int(fr.shape[0])
     ends = sorted({int(e) for e in ends}) if ends is not None else []
     out = [[tuple(int(v) for v in b) for b in tr] for tr in tracks]
@@ -483,8 +496,7 @@ def extend_tracks(frames, tracks, ends=None, grid=EXTEND_DEFAULTS["grid"], radiu
                 continue
             used = sorted({f for c, k0, n in ids for f in [chains[c][2][0]] + [chains[c][2][0] + chains[c][1] * (k + 1)
                                                                                for k in range(k0, k0 + n)]})
-            at = {f: k for k, f in enumerate(used)}
-            slab = fr.index_select(0, torch.as_tensor(used)).to(dev or device)
+            slab, at = _upload(fr, used, dev or device)
             take(ids, _lib.track_chain(slab, [row(*i, at) for i in ids], grid=grid, radius=radius).cpu().numpy())
     # the collision rule, in the chains' order: forward in track order, then backward in track order
     at_frame = {}
@@ -537,9 +549,7 @@ def shot_cuts(frames, threshold=0.4, regions=4, max_frames=128, dev=None):
     _check_cuts("shot_cuts", threshold, regions)
     if max_frames < 1:
         raise ValueError(f"shot_cuts: max_frames {max_frames} must be at least 1")
-    fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
-    if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
-        raise _lib.GenConViTHipError("shot_cuts: frames must be uint8 of shape (F,H,W,3)")
+    fr = _as_frames("shot_cuts", frames)
     nf, h, w = (int(v) for v in fr.shape[:3])
     if nf <= 1:
         return [], np.empty((0,), dtype=np.float64)
@@ -586,17 +596,15 @@ TRANSITION_DEFAULTS = dict(lags=(4, 8), grid=16, h_min=0.25, rho_max=0.05, a_lo=
 
 
 def _check_transitions(what, regions, lags, grid, h_min, rho_max, a_lo, a_hi, slack):
-    integer = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
-    if not integer(regions) or regions not in _lib.CUT_REGIONS:
+    if not _is_whole(regions) or regions not in _lib.CUT_REGIONS:
         raise ValueError(f"{what}: regions {regions} must be 1, 2, 4 or 8")
-    if not integer(grid) or grid not in _lib.CELL_GRIDS:
+    if not _is_whole(grid) or grid not in _lib.CELL_GRIDS:
         raise ValueError(f"{what}: grid {grid} must be 8, 16 or 32")
-    if not (isinstance(lags, (list, tuple)) and len(lags) > 0 and all(integer(v) and 3 <= v <= _lib.FIT_LAGS[1] for v in lags)
+    if not (isinstance(lags, (list, tuple)) and len(lags) > 0 and all(_is_whole(v) and 3 <= v <= _lib.FIT_LAGS[1] for v in lags)
             and len(set(lags)) == len(lags)):
         raise ValueError(f"{what}: lags {lags} must be distinct integers in 3 ... {_lib.FIT_LAGS[1]} (a span needs two frames "
                          f"between its ends)")
-    number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v)
-    if not (all(number(v) for v in (h_min, rho_max, a_lo, a_hi, slack)) and 0.0 <= h_min <= 1.0 and rho_max >= 0.0
+    if not (all(_is_number(v) for v in (h_min, rho_max, a_lo, a_hi, slack)) and 0.0 <= h_min <= 1.0 and rho_max >= 0.0
             and 0.0 <= a_lo < a_hi <= 1.0 and slack >= 0.0):
         raise ValueError(f"{what}: h_min {h_min} must lie in [0, 1], rho_max {rho_max} and slack {slack} be at least 0 and "
                          f"0 <= a_lo {a_lo} < a_hi {a_hi} <= 1")
@@ -667,9 +675,7 @@ def shot_transitions(frames, lags=(4, 8), grid=16, regions=4, h_min=0.25, rho_ma
     _check_transitions("shot_transitions", regions, lags, grid, h_min, rho_max, a_lo, a_hi, slack)
     if max_frames < 1:
         raise ValueError(f"shot_transitions: max_frames {max_frames} must be at least 1")
-    fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
-    if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
-        raise _lib.GenConViTHipError("shot_transitions: frames must be uint8 of shape (F,H,W,3)")
+    fr = _as_frames("shot_transitions", frames)
     nf, h, w = (int(v) for v in fr.shape[:3])
     hist, cells = _frame_stats(fr, regions, grid, max_frames, dev) if nf > min(lags) else (None, None)
     return _transitions_of(hist, cells, nf, h, w, regions, lags, h_min, rho_max, a_lo, a_hi, slack)
@@ -679,19 +685,18 @@ QUALITY_DEFAULTS = dict(grid=64, sharp_rel=0.5, sharp_min=0.0, clip_max=0.5)
 
 
 def _check_quality(what, grid=64, sharp_rel=0.5, sharp_min=0.0, clip_max=0.5):
-    if isinstance(grid, bool) or not isinstance(grid, (int, np.integer)) or grid not in _lib.TRACK_GRIDS:
+    if not _is_whole(grid) or grid not in _lib.TRACK_GRIDS:
         raise ValueError(f"{what}: grid {grid} must be 16, 32 or 64")
-    number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v)
-    if not (all(number(v) for v in (sharp_rel, sharp_min, clip_max)) and 0.0 <= sharp_rel <= 1.0 and sharp_min >= 0.0
+    if not (all(_is_number(v) for v in (sharp_rel, sharp_min, clip_max)) and 0.0 <= sharp_rel <= 1.0 and sharp_min >= 0.0
             and 0.0 < clip_max <= 1.0):
         raise ValueError(f"{what}: sharp_rel {sharp_rel} must lie in [0, 1], sharp_min {sharp_min} be at least 0 and clip_max "
                          f"{clip_max} lie in (0, 1]")
 
 
-def _box_groups(rows, ids, max_frames):
+def _box_groups(fr, rows, ids, max_frames, dev):
     """The boxes ``ids`` of ``rows`` in frame order, cut into runs that lie on at most ``max_frames`` distinct frames; per run
-    (its ids, its frames in rising order, its rows with the frame counted within those frames): what one upload of host
-    frames serves."""
+    (its ids, those frames of the host frames ``fr`` as a slab on ``dev``, its rows with the frame counted within the slab):
+    what one upload serves."""
     groups, used = [], set()
     for i in sorted(ids, key=lambda i: (rows[i][0], i)):
         if not groups or len(used | {rows[i][0]}) > max_frames:
@@ -700,9 +705,8 @@ def _box_groups(rows, ids, max_frames):
         groups[-1].append(i)
         used.add(rows[i][0])
     for group in groups:
-        used = sorted({rows[i][0] for i in group})
-        at = {f: k for k, f in enumerate(used)}
-        yield group, used, [(at[rows[i][0]], *rows[i][1:]) for i in group]
+        slab, at = _upload(fr, sorted({rows[i][0] for i in group}), dev)
+        yield group, slab, [(at[rows[i][0]], *rows[i][1:]) for i in group]
 
 
 def face_quality(frames, boxes, grid=64, max_frames=128, dev=None):
@@ -734,9 +738,7 @@ def face_quality(frames, boxes, grid=64, max_frames=128, dev=None):
     _check_quality("face_quality", grid=grid)
     if max_frames < 1:
         raise ValueError(f"face_quality: max_frames {max_frames} must be at least 1")
-    fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
-    if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
-        raise _lib.GenConViTHipError("face_quality: frames must be uint8 of shape (F,H,W,3)")
+    fr = _as_frames("face_quality", frames)
     grid = int(grid)
     rows = [tuple(int(v) for v in b) for b in boxes]
     _lib._check_boxes("face_quality", rows, *fr.shape[:3])
@@ -746,8 +748,7 @@ def face_quality(frames, boxes, grid=64, max_frames=128, dev=None):
     if big and fr.is_cuda:
         raw[big] = _lib.face_quality(fr, [rows[i] for i in big], grid=grid).cpu().numpy()
     elif big:
-        for ids, used, local in _box_groups(rows, big, max_frames):
-            slab = fr.index_select(0, torch.as_tensor(used)).to(dev or device)
+        for ids, slab, local in _box_groups(fr, rows, big, max_frames, dev or device):
             raw[ids] = _lib.face_quality(slab, local, grid=grid).cpu().numpy()
     measured = np.zeros(n, dtype=bool)
     measured[big] = True
@@ -797,10 +798,9 @@ PERSON_DEFAULTS = dict(link_max=9082, per_track=64)
 
 
 def _check_persons(what, link_max=PERSON_DEFAULTS["link_max"], per_track=PERSON_DEFAULTS["per_track"]):
-    number = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v)
-    if not (number(link_max) and link_max >= 0):
+    if not (_is_number(link_max) and link_max >= 0):
         raise ValueError(f"{what}: link_max {link_max} must be a number of at least 0")
-    if isinstance(per_track, bool) or not isinstance(per_track, (int, np.integer)) or per_track < 1:
+    if not _is_whole(per_track) or per_track < 1:
         raise ValueError(f"{what}: per_track {per_track} must be an integer of at least 1")
 
 
@@ -820,9 +820,7 @@ def face_signatures(frames, boxes, max_frames=128, dev=None):
     not."""
     if max_frames < 1:
         raise ValueError(f"face_signatures: max_frames {max_frames} must be at least 1")
-    fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
-    if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
-        raise _lib.GenConViTHipError("face_signatures: frames must be uint8 of shape (F,H,W,3)")
+    fr = _as_frames("face_signatures", frames)
     rows = [tuple(int(v) for v in b) for b in boxes]
     _lib._check_boxes("face_signatures", rows, *fr.shape[:3])
     n, g = len(rows), _lib.SIG_GRID
@@ -837,8 +835,8 @@ def face_signatures(frames, boxes, max_frames=128, dev=None):
         parts, order = [_lib.face_signature(fr, [rows[i] for i in big])], list(big)
     else:
         parts, order = [], []
-        for ids, used, local in _box_groups(rows, big, max_frames):
-            parts.append(_lib.face_signature(fr.index_select(0, torch.as_tensor(used)).to(to), local))
+        for ids, slab, local in _box_groups(fr, rows, big, max_frames, to):
+            parts.append(_lib.face_signature(slab, local))
             order += ids
     got = torch.cat(parts)
     if order == list(range(n)):
@@ -921,6 +919,162 @@ def _scan_persons(fr, tracks, rows, offsets, logits, nets, max_batch, dev, link_
     means = mean2.cpu()
     return {"tracks": linked, "of_track": of_track, "verdicts": [_verdict(means[k]) for k in range(len(linked))],
             "means": mean2, "distance": distance, "rows": sampled, "measured": sigs["measured"]}
+
+
+_ScanOptions = collections.namedtuple("_ScanOptions", "follow cuts transitions targs extend eargs quality qargs persons pargs")
+
+
+def _option_args(option, value, name, given, defaults, check, *lead, false_is_off=True):
+    """One on/off option of ``scan_frames`` and its ``*_args``: ``defaults`` with the dict ``given`` laid over and checked
+    (``check("scan_frames", *lead, **args)``) when the option is on, the defaults alone when it is off.  ``value`` must be
+    None or True; False means off too, unless ``false_is_off`` is False."""
+    if value is not None and value is not True and not (false_is_off and value is False):
+        raise ValueError(f"scan_frames: {option} {value!r} must be None or True")
+    args = dict(defaults)
+    if value:
+        if given is not None:
+            if not (isinstance(given, dict) and set(given) <= set(args)):
+                raise ValueError(f"scan_frames: {name} must be a dict with keys among {sorted(args)}")
+            args.update(given)
+        check("scan_frames", *lead, **args)
+    return args
+
+
+def _scan_options(nf, detect_every, window, stride, max_batch, follow, follow_grid, follow_radius, cuts, cut_threshold,
+                  cut_regions, transitions, transition_args, quality, quality_args, persons, person_args, extend, extend_args):
+    """The options stage of ``scan_frames``: every check that needs nothing but the arguments and the number of frames
+    ``nf``, before the detector, ``track_boxes`` or any binding is reached.  Returns what the later stages read: which
+    options are on, ``cuts`` and ``transitions`` as None, True or their sorted lists, and each ``*_args`` merged with its
+    defaults."""
+    eargs = _option_args("extend", extend, "extend_args", extend_args, EXTEND_DEFAULTS, _check_extend, false_is_off=False)
+    qargs = _option_args("quality", quality, "quality_args", quality_args, QUALITY_DEFAULTS, _check_quality)
+    pargs = _option_args("persons", persons, "person_args", person_args, PERSON_DEFAULTS, _check_persons)
+    targs = _option_args("transitions", transitions is True or None, "transition_args", transition_args, TRANSITION_DEFAULTS,
+                         _check_transitions, cut_regions)
+    if transitions is not True and transitions is not None:
+        given = list(transitions) if isinstance(transitions, (list, tuple)) else None
+        if given is None or not all(isinstance(t, (list, tuple)) and len(t) == 2 and _is_whole(t[0]) and _is_whole(t[1]) and
+                                    0 <= t[0] <= t[1] < nf for t in given):
+            raise ValueError(f"scan_frames: transitions must be True or a list of (first, last) integer pairs with "
+                             f"0 <= first <= last <= {nf - 1}")
+        transitions = sorted({(int(t[0]), int(t[1])) for t in given})
+    if cuts is True:
+        _check_cuts("scan_frames", cut_threshold, cut_regions)
+    elif cuts is not None:
+        given = list(cuts) if isinstance(cuts, (list, tuple, np.ndarray)) else None
+        if given is None or not all(_is_whole(c) and 1 <= c < nf for c in given):
+            raise ValueError(f"scan_frames: cuts must be True or a list of integers in [1, {nf - 1}]")
+        cuts = sorted({int(c) for c in given})
+    if detect_every < 1 or max_batch < 1:
+        raise ValueError(f"scan_frames: detect_every {detect_every} and max_batch {max_batch} must both be at least 1")
+    window_ranges(1, window, stride)                        # bad window / stride: raise before anything runs
+    if follow:
+        _check_follow("scan_frames", follow_grid, follow_radius)
+    return _ScanOptions(bool(follow), cuts, transitions, targs, bool(extend), eargs, bool(quality), qargs, bool(persons), pargs)
+
+
+def _scan_shots(fr, opt, cut_threshold, cut_regions, max_batch, dev):
+    """The shots stage of ``scan_frames``: the cuts and transitions that were asked for and not given, from one shared
+    ``_frame_stats`` upload when both are computed.  Returns ``(cuts, cut_scores, transitions, transition_info, ends)``:
+    the scores and the info are None where nothing was computed, and ``ends`` are the frames at which a new shot starts
+    for ``track_boxes`` and ``extend_tracks`` — the cuts and the borders of the transitions."""
+    cuts, transitions = opt.cuts, opt.transitions
+    nf, h, w = (int(v) for v in fr.shape[:3])
+    cut_scores = transition_info = None
+    if transitions is True:
+        targs = dict(opt.targs)
+        lags, grid = targs.pop("lags"), targs.pop("grid")
+        hist, cells = (_frame_stats(fr, cut_regions, grid, max_batch, dev)                        # one upload feeds both
+                       if nf > (1 if cuts is True else min(lags)) else (None, None))
+        transitions, transition_info = _transitions_of(hist, cells, nf, h, w, cut_regions, lags, **targs)
+        if cuts is True:
+            cuts, cut_scores = _cuts_of(hist, h, w, cut_regions, cut_threshold) if nf > 1 else ([], np.empty((0,), np.float64))
+    elif cuts is True:
+        cuts, cut_scores = shot_cuts(fr, cut_threshold, cut_regions, max_frames=max_batch, dev=dev)
+    ends = cuts
+    if transitions is not None:
+        ends = sorted(set(cuts or []) | {c for first, last in transitions for c in (first, last + 1) if 1 <= c < nf})
+    return cuts, cut_scores, transitions, transition_info, ends
+
+
+def _scan_tracks(fr, boxes, transitions, ends, opt, detect_every, iou, follow_grid, follow_radius, max_batch, dev):
+    """The tracks stage of ``scan_frames``: the boxes outside the transitions linked into tracks, then followed, extended
+    and gated by quality as ``opt`` says.  Returns ``(tracks, follow, extend, quality)``, the last three as the result
+    holds them, None for a step that is off."""
+    moved = extended = measures = None
+    if transitions is not None:
+        boxes = [b for b in boxes if not any(first <= b[0] <= last for first, last in transitions)]
+    if opt.follow:
+        tracks, anchors = track_boxes(boxes, iou=iou, max_gap=detect_every, return_anchors=True, cuts=ends)
+        tracks, moved = follow_tracks(fr, tracks, anchors, grid=follow_grid, radius=follow_radius,
+                                      max_frames=max(max_batch, 3), dev=dev)
+    else:
+        tracks = track_boxes(boxes, iou=iou, max_gap=detect_every, cuts=ends)
+    if opt.extend:
+        tracks, extended = extend_tracks(fr, tracks, ends, iou=iou, max_frames=max(max_batch, 2), dev=dev, **opt.eargs)
+    if opt.quality:
+        qargs = dict(opt.qargs)
+        before = [b for tr in tracks for b in tr]
+        measures = face_quality(fr, before, grid=qargs.pop("grid"), max_frames=max_batch, dev=dev)
+        kept = quality_keep(measures, np.cumsum([0] + [len(tr) for tr in tracks]), **qargs)
+        left = iter(kept.tolist())
+        tracks = [[b for b in tr if next(left)] for tr in tracks]
+        measures.update(kept=kept, boxes=before, track_map=[t for t, tr in enumerate(tracks) if tr])
+        tracks = [tr for tr in tracks if tr]
+    return tracks, moved, extended, measures
+
+
+def _scan_logits(fr, model, rows, eps, max_batch):
+    """The crops stage of ``scan_frames``: the crop ``rows`` in frame order in groups of at most ``max_batch``, each one upload
+    of the frames it lies on, one ``_lib.face_crop_preprocess`` and one model call.  Returns ``(logits, nets)``: the groups'
+    [net 0 | net 1] logits put into [net 0 all crops; net 1 all crops] in the order of ``rows``."""
+    p = next(model.parameters())
+    n = len(rows)
+    nets = 2 if getattr(model, "net", "genconvit") not in ("ed", "vae") else 1
+    order = sorted(range(n), key=lambda i: (rows[i][0], i))             # frame order
+    parts, src = [], [0] * (nets * n)
+    for g in range(0, n, max_batch):
+        ids = order[g:g + max_batch]
+        slab, at = _upload(fr, sorted({rows[i][0] for i in ids}), p.device)     # the frames this group's crops lie on, no others
+        x = _lib.face_crop_preprocess(slab, [(at[rows[i][0]], *rows[i][1:]) for i in ids], dtype=p.dtype)
+        if eps is not None:
+            logits = model(x, eps=eps[torch.as_tensor(ids, device=eps.device)].to(p.device))
+        else:
+            logits = model(x)
+        if getattr(model, "reference_logits_dtype", False):
+            logits = logits.to(p.dtype)
+        parts.append(logits.reshape(-1, 2))
+        for k in range(nets):                                           # this group's rows are [net 0 | net 1]
+            for j, i in enumerate(ids):
+                src[k * n + i] = nets * g + k * len(ids) + j
+    return torch.cat(parts).index_select(0, torch.as_tensor(src, device=p.device)), nets
+
+
+def _scan_votes(tracks, offsets, logits, nets, window, stride):
+    """The votes stage of ``scan_frames``: ONE ``_lib.vote_windows`` call over every window of every track, every whole track
+    and everything.  Returns the result's ``frame_scores``, ``window_means``, ``windows``, ``track_verdicts``, ``verdict`` and
+    ``segments``."""
+    n = offsets[-1]
+    ranges, wins = [], []
+    for t, tr in enumerate(tracks):
+        for lo, hi in window_ranges(len(tr), window, stride):
+            ranges.append((offsets[t] + lo, offsets[t] + hi))
+            wins.append((t, tr[lo][0], tr[hi - 1][0]))
+    ranges += [(offsets[t], offsets[t + 1]) for t in range(len(tracks))] + [(0, n)]
+    frame_p, mean2 = _lib.vote_windows(logits, n, nets, ranges)
+    means = mean2.cpu()
+    nw = len(wins)
+    windows = [(*w, *_verdict(means[k])) for k, w in enumerate(wins)]
+    segments, run = [], None
+    for t, first, last, y, y_val in windows + [(None, 0, 0, 1, 0.0)]:
+        if run is not None and (y != 0 or t != run[0]):
+            segments.append(tuple(run))
+            run = None
+        if y == 0:
+            run = [t, first, last, y_val] if run is None else [t, run[1], last, max(run[3], y_val)]
+    return {"frame_scores": frame_p, "window_means": mean2[:nw], "windows": windows,
+            "track_verdicts": [_verdict(means[nw + t]) for t in range(len(tracks))],
+            "verdict": _verdict(means[nw + len(tracks)]), "segments": segments}
 
 
 def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3, window=15, stride=1, max_batch=128,
@@ -1032,64 +1186,10 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
     Exposure drift raises the cost, so under it chains stop early: that is the safe side.  Where the detector did look at
     an extended frame, it is a frame on which it found nothing there.  The default ``cost_max`` is a starting value from
     synthetic material (``extend_tracks``), not a tuned one."""
-    fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
-    if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
-        raise _lib.GenConViTHipError("scan_frames: frames must be uint8 of shape (F,H,W,3)")
-    if extend is not None and extend is not True:
-        raise ValueError(f"scan_frames: extend {extend!r} must be None or True")
-    eargs = dict(EXTEND_DEFAULTS)
-    if extend:
-        if extend_args is not None:
-            if not (isinstance(extend_args, dict) and set(extend_args) <= set(eargs)):
-                raise ValueError(f"scan_frames: extend_args must be a dict with keys among {sorted(eargs)}")
-            eargs.update(extend_args)
-        _check_extend("scan_frames", **eargs)
-    if quality is not None and not isinstance(quality, bool):
-        raise ValueError(f"scan_frames: quality {quality!r} must be None or True")
-    qargs = dict(QUALITY_DEFAULTS)
-    if quality:
-        if quality_args is not None:
-            if not (isinstance(quality_args, dict) and set(quality_args) <= set(qargs)):
-                raise ValueError(f"scan_frames: quality_args must be a dict with keys among {sorted(qargs)}")
-            qargs.update(quality_args)
-        _check_quality("scan_frames", **qargs)
-    if persons is not None and not isinstance(persons, bool):
-        raise ValueError(f"scan_frames: persons {persons!r} must be None or True")
-    pargs = dict(PERSON_DEFAULTS)
-    if persons:
-        if person_args is not None:
-            if not (isinstance(person_args, dict) and set(person_args) <= set(pargs)):
-                raise ValueError(f"scan_frames: person_args must be a dict with keys among {sorted(pargs)}")
-            pargs.update(person_args)
-        _check_persons("scan_frames", **pargs)
-    targs = dict(TRANSITION_DEFAULTS)
-    if transitions is True:
-        if transition_args is not None:
-            if not (isinstance(transition_args, dict) and set(transition_args) <= set(targs)):
-                raise ValueError(f"scan_frames: transition_args must be a dict with keys among {sorted(targs)}")
-            targs.update(transition_args)
-        _check_transitions("scan_frames", cut_regions, **targs)
-    elif transitions is not None:
-        given = list(transitions) if isinstance(transitions, (list, tuple)) else None
-        whole = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
-        if given is None or not all(isinstance(t, (list, tuple)) and len(t) == 2 and whole(t[0]) and whole(t[1]) and
-                                    0 <= t[0] <= t[1] < fr.shape[0] for t in given):
-            raise ValueError(f"scan_frames: transitions must be True or a list of (first, last) integer pairs with "
-                             f"0 <= first <= last <= {fr.shape[0] - 1}")
-        transitions = sorted({(int(t[0]), int(t[1])) for t in given})
-    if cuts is True:
-        _check_cuts("scan_frames", cut_threshold, cut_regions)
-    elif cuts is not None:
-        given = list(cuts) if isinstance(cuts, (list, tuple, np.ndarray)) else None
-        if given is None or not all(isinstance(c, (int, np.integer)) and not isinstance(c, bool) and
-                                    1 <= c < fr.shape[0] for c in given):
-            raise ValueError(f"scan_frames: cuts must be True or a list of integers in [1, {fr.shape[0] - 1}]")
-        cuts = sorted({int(c) for c in given})
-    if detect_every < 1 or max_batch < 1:
-        raise ValueError(f"scan_frames: detect_every {detect_every} and max_batch {max_batch} must both be at least 1")
-    window_ranges(1, window, stride)                        # bad window / stride: raise before anything runs
-    if follow:
-        _check_follow("scan_frames", follow_grid, follow_radius)
+    fr = _as_frames("scan_frames", frames)
+    opt = _scan_options(int(fr.shape[0]), detect_every, window, stride, max_batch, follow, follow_grid, follow_radius, cuts,
+                        cut_threshold, cut_regions, transitions, transition_args, quality, quality_args, persons, person_args,
+                        extend, extend_args)
     if boxes is None:
         seen = (fr.cpu().numpy() if torch.is_tensor(frames) else np.asarray(frames))[::detect_every]
         found = locate(seen) if locate is not None else face_locations(seen, keep_all=True)
@@ -1097,110 +1197,33 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
     boxes = [tuple(int(v) for v in b) for b in boxes]
     _lib._check_boxes("scan_frames", boxes, *fr.shape[:3])
     p = next(model.parameters())
-    cut_scores = transition_info = None
-    if transitions is True:
-        nf, h, w = (int(v) for v in fr.shape[:3])
-        lags, grid = targs.pop("lags"), targs.pop("grid")
-        hist, cells = (_frame_stats(fr, cut_regions, grid, max_batch, p.device)                    # one upload feeds both
-                       if nf > (1 if cuts is True else min(lags)) else (None, None))
-        transitions, transition_info = _transitions_of(hist, cells, nf, h, w, cut_regions, lags, **targs)
-        if cuts is True:
-            cuts, cut_scores = _cuts_of(hist, h, w, cut_regions, cut_threshold) if nf > 1 else ([], np.empty((0,), np.float64))
-    elif cuts is True:
-        cuts, cut_scores = shot_cuts(fr, cut_threshold, cut_regions, max_frames=max_batch, dev=p.device)
-    ends = cuts
-    if transitions is not None:
-        boxes = [b for b in boxes if not any(first <= b[0] <= last for first, last in transitions)]
-        ends = sorted(set(cuts or []) | {c for first, last in transitions for c in (first, last + 1) if 1 <= c < fr.shape[0]})
-    if follow:
-        tracks, anchors = track_boxes(boxes, iou=iou, max_gap=detect_every, return_anchors=True, cuts=ends)
-        tracks, moved = follow_tracks(fr, tracks, anchors, grid=follow_grid, radius=follow_radius,
-                                      max_frames=max(max_batch, 3), dev=p.device)
-    else:
-        tracks = track_boxes(boxes, iou=iou, max_gap=detect_every, cuts=ends)
-    if extend:
-        tracks, extended = extend_tracks(fr, tracks, ends, iou=iou, max_frames=max(max_batch, 2), dev=p.device, **eargs)
-    measures = None
-    if quality:
-        before = [b for tr in tracks for b in tr]
-        measures = face_quality(fr, before, grid=qargs.pop("grid"), max_frames=max_batch, dev=p.device)
-        kept = quality_keep(measures, np.cumsum([0] + [len(tr) for tr in tracks]), **qargs)
-        left = iter(kept.tolist())
-        tracks = [[b for b in tr if next(left)] for tr in tracks]
-        measures.update(kept=kept, boxes=before, track_map=[t for t, tr in enumerate(tracks) if tr])
-        tracks = [tr for tr in tracks if tr]
+    cuts, cut_scores, transitions, transition_info, ends = _scan_shots(fr, opt, cut_threshold, cut_regions, max_batch, p.device)
+    tracks, moved, extended, measures = _scan_tracks(fr, boxes, transitions, ends, opt, detect_every, iou, follow_grid,
+                                                     follow_radius, max_batch, p.device)
     rows = [b for tr in tracks for b in tr]
     offsets = [0] + [int(v) for v in np.cumsum([len(tr) for tr in tracks])]
     n = len(rows)
     res = {"tracks": tracks, "boxes": rows, "track_offsets": offsets, "windows": [], "track_verdicts": [],
            "verdict": (None, None), "segments": []}
-    if follow:
-        res["follow"] = moved
-    if extend:
-        res["extend"] = extended
-    if cuts is not None:
-        res["cuts"] = cuts
-        if cut_scores is not None:
-            res["cut_scores"] = cut_scores
-    if transitions is not None:
-        res["transitions"] = transitions
-        if transition_info is not None:
-            res["transition_info"] = transition_info
-    if measures is not None:
-        res["quality"] = measures
+    gained = {"follow": moved, "extend": extended, "cuts": cuts, "cut_scores": cut_scores, "transitions": transitions,
+              "transition_info": transition_info, "quality": measures}
+    res.update({k: v for k, v in gained.items() if v is not None})     # the scores and the info only where computed here
     if n == 0:
         res["frame_scores"] = torch.empty((0, 2), dtype=torch.float32, device=p.device)
         res["window_means"] = torch.empty((0, 2), dtype=torch.float32, device=p.device)
-        if persons:
+        if opt.persons:
             res["persons"] = {"tracks": [], "of_track": [], "verdicts": [], "distance": np.empty((0, 0), dtype=np.int64),
                               "means": torch.empty((0, 2), dtype=torch.float32, device=p.device), "rows": [],
                               "measured": np.zeros(0, dtype=bool)}
         return res
     if eps is not None and eps.shape[0] != n:
         raise ValueError(f"scan_frames: eps holds {eps.shape[0]} rows for {n} crops")
-    nets = 2 if getattr(model, "net", "genconvit") not in ("ed", "vae") else 1
-    order = sorted(range(n), key=lambda i: (rows[i][0], i))             # frame order
-    parts, src = [], [0] * (nets * n)
     with torch.no_grad():
-        for g in range(0, n, max_batch):
-            ids = order[g:g + max_batch]
-            used = sorted({rows[i][0] for i in ids})                    # the frames this group's crops lie on, no others
-            at = {f: k for k, f in enumerate(used)}
-            slab = fr.index_select(0, torch.as_tensor(used, device=fr.device)).to(p.device)
-            x = _lib.face_crop_preprocess(slab, [(at[rows[i][0]], *rows[i][1:]) for i in ids], dtype=p.dtype)
-            if eps is not None:
-                logits = model(x, eps=eps[torch.as_tensor(ids, device=eps.device)].to(p.device))
-            else:
-                logits = model(x)
-            if getattr(model, "reference_logits_dtype", False):
-                logits = logits.to(p.dtype)
-            parts.append(logits.reshape(-1, 2))
-            for k in range(nets):                                       # this group's rows are [net 0 | net 1]
-                for j, i in enumerate(ids):
-                    src[k * n + i] = nets * g + k * len(ids) + j
-        logits = torch.cat(parts).index_select(0, torch.as_tensor(src, device=p.device))
-        ranges, wins = [], []
-        for t, tr in enumerate(tracks):
-            for lo, hi in window_ranges(len(tr), window, stride):
-                ranges.append((offsets[t] + lo, offsets[t] + hi))
-                wins.append((t, tr[lo][0], tr[hi - 1][0]))
-        ranges += [(offsets[t], offsets[t + 1]) for t in range(len(tracks))] + [(0, n)]
-        frame_p, mean2 = _lib.vote_windows(logits, n, nets, ranges)
-        if persons:
-            res["persons"] = _scan_persons(fr, tracks, rows, offsets, logits, nets, max_batch, p.device, **pargs)
-    means = mean2.cpu()
-    nw = len(wins)
-    res["frame_scores"], res["window_means"] = frame_p, mean2[:nw]
-    res["windows"] = [(*w, *_verdict(means[k])) for k, w in enumerate(wins)]
-    res["track_verdicts"] = [_verdict(means[nw + t]) for t in range(len(tracks))]
-    res["verdict"] = _verdict(means[nw + len(tracks)])
-    run = None
-    for t, first, last, y, y_val in res["windows"] + [(None, 0, 0, 1, 0.0)]:
-        if run is not None and (y != 0 or t != run[0]):
-            res["segments"].append(tuple(run))
-            run = None
-        if y == 0:
-            run = [t, first, last, y_val] if run is None else [t, run[1], last, max(run[3], y_val)]
+        logits, nets = _scan_logits(fr, model, rows, eps, max_batch)
+        voted = _scan_votes(tracks, offsets, logits, nets, window, stride)
+        if opt.persons:
+            res["persons"] = _scan_persons(fr, tracks, rows, offsets, logits, nets, max_batch, p.device, **opt.pargs)
+    res.update(voted)
     return res
 
 
