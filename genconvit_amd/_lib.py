@@ -95,6 +95,7 @@ SIGNATURES = {
     "gcv_profile_enable": (c_int, [c_void_p, c_int]),
     "gcv_profile_report": (c_char_p, [c_void_p]),
     "gcv_k_gemm": (c_int, [c_int, c_int, c_int, ctypes.POINTER(GemmArgs), c_void_p]),
+    "gcv_gemm_plan": (c_int, [c_int, c_int, c_int, ctypes.POINTER(GemmArgs), c_void_p]),
     "gcv_k_stem_ln": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
     "gcv_k_stem_ln_c": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,

@@ -615,14 +615,31 @@ const char* gcv_profile_report(gcv_handle* h) {
     default: set_error("bad dtype"); return -2;                  \
   }
 
-int gcv_k_gemm(int dtype, int a_mode, int epi, const gcv_gemm_args* a, gcv_stream stream) {
-  GCV_REQUIRE(a, "null args");
+static GemmArgs gemm_args(const gcv_gemm_args* a) {
   GemmArgs g{};
   g.A = a->A; g.Wt = a->Wt; g.C = a->C; g.bias = a->bias; g.gamma = a->gamma; g.resid = a->resid;
   g.partial = a->partial; g.M = a->M; g.N = a->N; g.K = a->K; g.lda = a->lda; g.ldc = a->ldc; g.act = a->act;
   g.splitk = a->splitk; g.k_per_split = a->k_per_split; g.H = a->H; g.W = a->W; g.cin_log2 = a->cin_log2;
   g.cout_log2 = a->cout_log2;
+  return g;
+}
+
+int gcv_k_gemm(int dtype, int a_mode, int epi, const gcv_gemm_args* a, gcv_stream stream) {
+  GCV_REQUIRE(a, "null args");
+  const GemmArgs g = gemm_args(a);
   DISPATCH_DT(dtype, launch_gemm<T>(g, a_mode, epi, (hipStream_t)stream));
+}
+
+int gcv_gemm_plan(int dtype, int a_mode, int epi, const gcv_gemm_args* a, int* out10) {
+  GCV_REQUIRE(a && out10, "null args / out10");
+  const GemmArgs g = gemm_args(a);
+  GemmPlan p;
+  auto put = [&](int rc) {
+    const int v[10] = {(int)p.kind, p.bm, p.bn, p.wm, p.wn, p.bkb, p.grid_x, p.grid_y, p.threads, p.lds};
+    for (int i = 0; rc == 0 && i < 10; ++i) out10[i] = v[i];
+    return rc;
+  };
+  DISPATCH_DT(dtype, put(gemm_plan<T>(p, g, a_mode, epi)));
 }
 
 int gcv_k_stem_ln(int dtype, const void* x, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* wp,

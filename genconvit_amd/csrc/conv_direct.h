@@ -1,7 +1,7 @@
 // Direct 3x3 convolution for 16-bit storage at Cin = 16 / 32 and N = 32 / 64 (ED encoder layers 2-3: conv + ReLU + 2x2
-// max-pool; VAE encoder layers 2-3: conv stride 2 + LeakyReLU).  Reached from launch_gemm (gemm_impl.h) for the
-// A_IM2COL3_POOL / EPI_POOL4 and A_IM2COL3_S2 / EPI_BIAS_ACT launches that qualify (conv_direct_applicable); everything
-// else stays on gemm_kernel.
+// max-pool; VAE encoder layers 2-3: conv stride 2 + LeakyReLU).  One of the three kinds of kernel that gemm_select
+// (gemm_impl.h) picks from: the A_IM2COL3_POOL / EPI_POOL4 and A_IM2COL3_S2 / EPI_BIAS_ACT launches that meet its rules there
+// run here, everything else stays on gemm_kernel.
 //
 // Why: at these widths a wave of gemm_kernel issues 2-4 MFMAs per K tile and pays gathered loads with tap / bounds / address
 // arithmetic, an LDS store, an LDS read-back and a barrier for each of them.  Here both MFMA operands come straight from
@@ -216,52 +216,17 @@ __global__ void __launch_bounds__(256, 2) conv3_direct_kernel(const ConvDirectAr
 #endif
 constexpr bool conv_direct_on(bool pool, int cin) { return (GCV_CONV_DIRECT >> ((pool ? 0 : 2) + (cin == 32 ? 1 : 0))) & 1; }
 
-// workgroups of four waves; a wave takes at least two pixel blocks where there are that many (the second block's loads
-// run under the first block's MFMAs), and at most four workgroups per CU of a 256-CU chip are launched
+// at most four workgroups per CU of a 256-CU chip are launched (the grid is planned with the kernel: gemm_select, gemm_impl.h)
 constexpr int kConvDirectMaxWg = 1024;
-static inline int conv_direct_grid(int M, int N) {
-  const int items = cdiv(M, 32) * (N / 32);
-  return std::min(kConvDirectMaxWg, cdiv(items, 8));
-}
 
-template <typename T> static bool conv_direct_applicable(const GemmArgs& g, int a_mode, int epi) {
-  if (sizeof(T) != 2) return false;
-  const bool pool = a_mode == A_IM2COL3_POOL && epi == EPI_POOL4 && g.act == ACT_RELU;
-  const bool s2 = a_mode == A_IM2COL3_S2 && epi == EPI_BIAS_ACT && g.act == ACT_LEAKY;
-  if (!pool && !s2) return false;
-  const int cin = 1 << g.cin_log2;
-  if ((cin != 16 && cin != 32) || !conv_direct_on(pool, cin) || (g.N != 32 && g.N != 64) || !g.bias) return false;
-  // 32-bit byte offsets into the input, 32-bit row numbers with a block of slack
-  const int64_t in_bytes = (int64_t)g.M * (pool ? 1 : 4) * cin * 2;
-  if (in_bytes >= (int64_t(1) << 31) || g.M > (1 << 30)) return false;
-  // the stride-2 epilogue stores 16-byte pieces
-  if (s2 && ((reinterpret_cast<uintptr_t>(g.C) & 15u) != 0 || g.ldc % 8 != 0)) return false;
-  return true;
-}
-
-template <typename T, int CIN, int STRIDE> static int launch_conv_direct_cfg(const ConvDirectArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL((conv3_direct_kernel<T, CIN, STRIDE>), dim3(conv_direct_grid(a.M, a.N)), dim3(256), 0, s, a);
-  GCV_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-template <typename T> static int launch_conv_direct(const GemmArgs& g, int a_mode, hipStream_t s) {
-  if constexpr (sizeof(T) == 2) {
-    ConvDirectArgs a;
-    a.x = g.A; a.wt = g.Wt; a.out = g.C; a.bias = g.bias;
-    a.M = g.M; a.N = g.N; a.ldc = g.ldc; a.H = g.H; a.W = g.W;
-    a.nblk = cdiv(g.M, 32);
-    a.mg_w = udiv_mg_of((uint32_t)g.W >> 1);
-    a.mg_h = udiv_mg_of((uint32_t)g.H >> 1);
-    const bool pool = a_mode == A_IM2COL3_POOL;
-    const int cin = 1 << g.cin_log2;
-    if constexpr (conv_direct_on(true, 16)) if (pool && cin == 16) return launch_conv_direct_cfg<T, 16, 1>(a, s);
-    if constexpr (conv_direct_on(true, 32)) if (pool && cin == 32) return launch_conv_direct_cfg<T, 32, 1>(a, s);
-    if constexpr (conv_direct_on(false, 16)) if (!pool && cin == 16) return launch_conv_direct_cfg<T, 16, 2>(a, s);
-    if constexpr (conv_direct_on(false, 32)) if (!pool && cin == 32) return launch_conv_direct_cfg<T, 32, 2>(a, s);
-  }
-  set_error("launch_conv_direct: no kernel built for this launch");
-  return -3;
+static inline ConvDirectArgs conv_direct_args(const GemmArgs& g) {
+  ConvDirectArgs a;
+  a.x = g.A; a.wt = g.Wt; a.out = g.C; a.bias = g.bias;
+  a.M = g.M; a.N = g.N; a.ldc = g.ldc; a.H = g.H; a.W = g.W;
+  a.nblk = cdiv(g.M, 32);
+  a.mg_w = udiv_mg_of((uint32_t)g.W >> 1);
+  a.mg_h = udiv_mg_of((uint32_t)g.H >> 1);
+  return a;
 }
 
 }  // namespace gcv

@@ -659,8 +659,18 @@ __global__ void __launch_bounds__(256) gemm_kernel(const GemmArgs g) {
   }
 }
 
-// Host-side launcher: validates shapes, picks a tile config, launches on `stream`.
-// Returns 0 on success (error text via gcv::get_error()).
+// Host side (gemm_impl.h): gemm_select validates a launch and plans its kernel, tile and grid in one place.
+enum class GemmKind { Tile, Glds, Direct };   // in this order: the `kind` of gcv_gemm_plan
+struct GemmPlan {
+  GemmKind kind = GemmKind::Tile;
+  // Tile: BM, BN, WM, WN, BKB of gemm_kernel.  Glds: gemm_glds_kernel's 128 x 192 tile, 64 x 96 per wave, and its BKB.
+  // Direct: bm = CIN and bn = STRIDE of conv3_direct_kernel, the rest 0.
+  int bm = 0, bn = 0, wm = 0, wn = 0, bkb = 0;
+  int grid_x = 0, grid_y = 1, threads = 0, lds = 0;   // workgroups, threads per workgroup, dynamic LDS bytes
+};
+// the plan of a launch, or the launcher's error, without a HIP call
+template <typename T> int gemm_plan(GemmPlan& p, const GemmArgs& g, int a_mode, int epi);
+// launches from that plan on `stream`.  Returns 0 on success (error text via gcv::get_error()).
 template <typename T> int launch_gemm(const GemmArgs& g, int a_mode, int epi, hipStream_t stream);
 // name of the kernel family a (dtype, a_mode, epi) launch resolves to — for profiling tables
 const char* gemm_family_name(int a_mode, int epi);

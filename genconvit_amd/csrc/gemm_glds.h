@@ -240,8 +240,4 @@ __global__ void __launch_bounds__(256, 2) gemm_glds_kernel(const GemmArgs g) {
 #endif
 }
 
-template <typename T> int launch_gemm_glds(const GemmArgs& g, int epi, hipStream_t s);
-// true when (g, a_mode, epi) is a shape the LDS-DMA kernel covers
-template <typename T> bool gemm_glds_applicable(const GemmArgs& g, int a_mode, int epi);
-
 }  // namespace gcv

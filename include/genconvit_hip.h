@@ -551,6 +551,14 @@ typedef struct {
 
 /* C = epilogue(A * Wt^T): nn.Linear / Conv2d-as-GEMM / ConvTranspose2d(k=s=2) / split-K slab */
 int gcv_k_gemm(int dtype, int a_mode, int epi, const gcv_gemm_args* a, gcv_stream s);
+/* Test query: the kernel and grid that gcv_k_gemm picks for the launch *a.  The pointers in *a are tested for null and
+ * alignment only, never dereferenced.  out10 = {kind, five tile fields, grid.x, grid.y, threads per workgroup, dynamic LDS
+ * bytes}; or the launcher's error.  The tile fields by kind:
+ *   0 tile GEMM         BM, BN (workgroup tile), WM, WN (wave tile), BKB (bytes per LDS row: a K tile of BKB / sizeof(T))
+ *   1 LDS-DMA GEMM      128, 192, 64, 96, BKB (64 or 128)
+ *   2 direct 3x3 conv   CIN (16 / 32), STRIDE (1: conv + ReLU + 2x2 max-pool, 2: stride-2 conv + LeakyReLU), 0, 0, 0
+ * No HIP call: works without a GPU. */
+int gcv_gemm_plan(int dtype, int a_mode, int epi, const gcv_gemm_args* a, int* out10);
 int gcv_k_stem_ln(int dtype, const void* x, int64_t sb, int64_t sc, int64_t sy, int64_t sx, const float* wp,
                   const float* bias, const float* lnw, const float* lnb, void* out, int nimg, int Ho, int Wo,
                   float eps, gcv_stream s);

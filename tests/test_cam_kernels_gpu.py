@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from genconvit_amd import _lib
-from tests import camcases, kcases, kutil
+from tests import camcases, gemmcases, kcases, kutil
 from tests.camcases import SENT
 from tests.kutil import DTYPES, dev, gemm, ptr
 
@@ -215,10 +215,10 @@ def test_dw_dgrad_per_image_kernel_sums_in_the_generic_kernels_order(name):
 
 
 @pytest.mark.parametrize("dt", camcases.ALL)
-@pytest.mark.parametrize("N,K", [(3072, 768), (768, 3072)])
+@pytest.mark.parametrize("N,K", gemmcases.cases(gemmcases.CAM_CONTRACTION))
 def test_backward_contraction_gemm_with_one_split(dt, N, K):
     """The contractions between the backward kernels: launch_gemm with EPI_SPLITK, one split of the whole K, 13 rows"""
-    dtype, M = DTYPES[dt], 13
+    dtype, M = DTYPES[dt], gemmcases.CAM_ROWS
     case = kcases.gemm("splitk", M, N, K, dtype, k_per_split=K)
     i = case.inputs
     part = Guarded(M, N)

@@ -1,11 +1,11 @@
 """The direct 3x3 convolution kernel for 16-bit storage (csrc/conv_direct.h), reached through gcv_k_gemm exactly as the
-networks reach it: launch_gemm (csrc/gemm_impl.h) sends the A_IM2COL3_POOL / EPI_POOL4 launches with Cin = 16 / 32, N = 32 / 64
-and the A_IM2COL3_S2 / EPI_BIAS_ACT launches with Cin = 16, N = 32 / 64 there (conv_direct_applicable), and everything else
-to gemm_kernel: the stride-2 cases at Cin = 32 below pin that generic path, which measured faster for them.  Inputs, float64
+networks reach it: gemm_select (csrc/gemm_impl.h) sends the A_IM2COL3_POOL / EPI_POOL4 launches with Cin = 16 / 32, N = 32 / 64
+and the A_IM2COL3_S2 / EPI_BIAS_ACT launches with Cin = 16, N = 32 / 64 there, and everything else
+to gemm_kernel (tests/gemmcases.py has the cases and the kernel each reaches; tests/test_host_cpu.py asserts it): the stride-2 cases at Cin = 32 below pin that generic path, which measured faster for them.  Inputs, float64
 reference and comparator are tests/kcases.py's conv3x3_pool / conv3x3_s2, unchanged.
 
 A wave's work item is 32 consecutive rows m of the flattened launch x 32 output channels, and the launcher starts
-min(1024, ceil(items / 8)) workgroups of four waves (conv_direct_grid), so a wave makes two trips of its loop wherever there
+min(1024, ceil(items / 8)) workgroups of four waves (DirectShape, csrc/gemm_impl.h), so a wave makes two trips of its loop wherever there
 are eight items or more, the second block's loads issued beside the first block's MFMAs:
   pool (1, 2, 16, 32)    4 rows: one window, one partial block; five of the nine taps of every pixel fall outside the image
   pool (3, 6, 16, 32)    108 rows = 27 windows, 9 per image: blocks straddle image rows and images, the fourth block has 12
@@ -27,15 +27,15 @@ import pytest
 import torch
 
 from genconvit_amd import _lib
-from tests import kcases
+from tests import gemmcases, kcases
 from tests.kutil import DTYPES, dev, gemm
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
 
 SENTINEL = 7.0
-GUARD = 4               # rows in front of and behind the result
-PAD = 8                 # columns behind the result: ldc stays a multiple of 8 (the stride-2 epilogue stores 16-byte pieces)
+GUARD = gemmcases.DIRECT_GUARD      # rows in front of and behind the result
+PAD = gemmcases.DIRECT_PAD          # columns behind the result: ldc stays a multiple of 8 (the stride-2 epilogue stores 16-byte pieces)
 
 
 def _run(case, mode, n, H, cin, cout, dtype):
@@ -47,7 +47,7 @@ def _run(case, mode, n, H, cin, cout, dtype):
     rows, ldc = n * Ho * Ho, cout + PAD
     buf = torch.full((GUARD + rows + GUARD, ldc), SENTINEL, dtype=dtype, device=dev())
     out = buf[GUARD:GUARD + rows]
-    # what launch_gemm asks of a launch before it takes the direct kernel's 16-byte stores (conv_direct_applicable)
+    # what gemm_select asks of a launch before it takes the direct kernel's 16-byte stores
     assert out.data_ptr() % 16 == 0 and ldc % 8 == 0
     if mode == "pool":
         gemm(dtype, _lib.A_IM2COL3_POOL, _lib.EPI_POOL4, x_nhwc, wt, out, n * H * H, cout, 9 * cin, ldc=ldc,
@@ -63,15 +63,14 @@ def _run(case, mode, n, H, cin, cout, dtype):
 
 
 @pytest.mark.parametrize("dt", ["f16", "bf16"])
-@pytest.mark.parametrize("n,H,cin,cout", [(1, 2, 16, 32), (3, 6, 16, 32), (3, 6, 32, 64), (2, 16, 32, 64),
-                                          (2, 16, 16, 16)])
+@pytest.mark.parametrize("n,H,cin,cout", gemmcases.cases(gemmcases.DIRECT_POOL))
 def test_direct_conv3x3_relu_maxpool(dt, n, H, cin, cout):
     dtype = DTYPES[dt]
     _run(kcases.conv3x3_pool(n, H, cin, cout, dtype), "pool", n, H, cin, cout, dtype)
 
 
 @pytest.mark.parametrize("dt", ["f16", "bf16"])
-@pytest.mark.parametrize("n,H,cin,cout", [(1, 2, 32, 64), (5, 6, 16, 32), (5, 6, 32, 64), (2, 16, 16, 16)])
+@pytest.mark.parametrize("n,H,cin,cout", gemmcases.cases(gemmcases.DIRECT_S2))
 def test_direct_conv3x3_stride2_leaky(dt, n, H, cin, cout):
     dtype = DTYPES[dt]
     _run(kcases.conv3x3_s2(n, H, cin, cout, dtype), "s2", n, H, cin, cout, dtype)

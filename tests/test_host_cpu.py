@@ -165,6 +165,87 @@ def test_every_dw_kernel_has_a_gpu_parity_case():
         assert kinds == ({"roll", "pair"} if dt == "f32" else {"roll", "pair", "mfma"}), (dt, kinds)
 
 
+def test_gemm_plan_table():
+    """The GEMM family's launch, pinned: kernel (tile GEMM and its tile, LDS-DMA GEMM and its LDS row, direct conv), grid,
+    threads and dynamic LDS bytes of every launch_gemm call of the ED and VAE networks on both backbones (both VAE schedules),
+    their explain passes and Swin-T at B = 1 ... 256 (tests/gemmcases.py has the formulas), of every GPU GEMM test, of the
+    operand alignments that change the kernel and of every error.  tests/golden/gemm_plan.json was recorded from the
+    launchers as they were before the choice moved into gemm_select: in a copy of that source, outside the repository, the
+    three functions that launched (launch_cfg, launch_glds_bkb, launch_conv_direct_cfg) wrote their template parameters,
+    grid, block and LDS bytes into a thread-local and returned, and gcv_k_gemm was called on the CPU for every row."""
+    import json
+    from tests import gemmcases as gc
+    with open(os.path.join(REPO, "tests", "golden", "gemm_plan.json")) as f:
+        gold = json.load(f)
+    assert gold["columns"] == list(gc.Launch._fields) + ["f32", "f16_bf16"]
+    assert gold["plan"] == ["kernel", "grid_x", "grid_y", "threads", "lds"]
+    table = {gc.Launch(*r[:-2]): r[-2:] for r in gold["rows"]}
+    assert gc.table_launches() <= set(table), sorted(gc.table_launches() - set(table))[:5]
+    text = dict(gc.ERRORS)
+    for l, per_dt in table.items():
+        for dt, want in zip(("f32", "f16", "bf16"), per_dt + per_dt[1:]):
+            got = gc.plan(dt, l)
+            if isinstance(want, int):
+                assert got[0] == want, (dt, l, got)
+                assert l not in text or text[l] in got[1], (dt, l, got)
+            else:
+                assert got == tuple(gold["kernels"][want[0]]) + tuple(want[1:]), (dt, l, got, want)
+    for l, msg in gc.ERRORS:
+        assert all(isinstance(v, int) for v in table[l]), (l, msg)
+
+
+def _gemm_kernels_named(dt):
+    """the (kind, five tile fields, a_mode, epi) that gemm_select (csrc/gemm_impl.h) names for storage dtype dt, read from
+    its source: go(Route{}, Shape<...>{}) calls, the conv tiles once per route they are called with"""
+    from genconvit_amd import _lib
+    csrc = os.path.join(REPO, "genconvit_amd", "csrc")
+    src = open(os.path.join(csrc, "gemm_impl.h")).read()
+    body = src[src.index("int gemm_select("):src.index("int gemm_plan(")]
+    routes = {name: (getattr(_lib, a), getattr(_lib, e))
+              for a, e, name in re.findall(r"typedef Route<(A_\w+), (EPI_\w+)[^>]*> (\w+);", src)}
+    calls = re.findall(r"\bgo\((\w+)(?:\{\})?, (Tile|Glds|Direct)Shape<([^>]*)>\{\}\)", body)
+    assert len(calls) == body.count("Shape<") == 26, (len(calls), body.count("Shape<"))
+    conv_routes = re.findall(r"\btiles\((\w+)\{\}\)", body)
+    assert sorted(conv_routes) == ["ConvPool", "ConvS2"]
+    built = int(re.search(r"#define GCV_CONV_DIRECT (\d+)", open(os.path.join(csrc, "conv_direct.h")).read()).group(1))
+    named = set()
+    for route, kind, targs in calls:
+        v = [(64 if dt == "f32" else 128) if t == "B" else int(t) for t in targs.split(", ")]
+        if kind == "Tile":
+            for r in (conv_routes if route == "route" else [route]):
+                named.add(("tile", *v) + routes[r])
+        elif dt != "f32" and kind == "Glds":
+            named.add(("glds", 128, 192, 64, 96, v[0]) + routes[route])
+        elif dt != "f32" and (built >> ((0 if v[1] == 1 else 2) + (v[0] == 32))) & 1:      # conv_direct_on
+            named.add(("direct", v[0], v[1], 0, 0, 0) + routes[route])
+    return named
+
+
+def test_gemm_case_lists_reach_the_kernels_they_state():
+    """tests/gemmcases.py states, next to every case of the GPU GEMM tests, the kernel it was written for; gcv_gemm_plan must
+    agree for the launch as the test makes it (shape, leading dimensions, operand alignment)."""
+    from tests import gemmcases as gc
+    for dt in ("f32", "f16", "bf16"):
+        for l, kernel in gc.gpu_launches(dt):
+            assert gc.plan(dt, l)[:6] == gc.resolve(kernel, dt), (dt, l, gc.plan(dt, l))
+    # and the alignment rules: the launch next to each aligned one leaves the LDS-DMA / direct kernel in 16-bit storage
+    kinds = [gc.plan("f16", l)[0] for l in gc.ALIGNMENT]
+    assert kinds == ["glds", "tile", "tile", "glds", "tile", "tile", "direct", "tile", "tile", "direct", "direct", "tile"], kinds
+
+
+def test_every_gemm_kernel_has_a_gpu_parity_case():
+    """Per storage dtype, the kernels that gcv_gemm_plan picks for the launches of the GPU parity tests (tests/gemmcases.py)
+    are ALL the kernels gemm_select (csrc/gemm_impl.h) names, as (kind, tile, a_mode, epilogue); one activation per kernel
+    is enough.  A kernel added to gemm_select without a GPU case — or a case that stops reaching its kernel — fails here,
+    without a GPU."""
+    from tests import gemmcases as gc
+    for dt in ("f32", "f16", "bf16"):
+        named = _gemm_kernels_named(dt)
+        assert len(named) == (17 if dt == "f32" else 30), (dt, len(named))
+        got = {gc.plan(dt, l)[:6] + (l.a_mode, l.epi) for l, _ in gc.gpu_launches(dt)}
+        assert got == named, (dt, sorted(got ^ named, key=str))
+
+
 _ARCH_DIMS = {0: (96, 192, 384, 768), 1: (192, 384, 768, 1536)}      # GCV_CONVNEXT_TINY / _LARGE (csrc/net.h)
 
 

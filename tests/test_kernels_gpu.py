@@ -16,7 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from genconvit_amd import _lib
-from tests import dwcases, kcases, kutil
+from tests import dwcases, gemmcases, kcases, kutil
 from tests.kutil import DTYPES, dev, gemm, ptr, rnd, tol
 
 pytestmark = pytest.mark.gpu
@@ -55,17 +55,7 @@ def assert_close(got, want, atol, what=""):
 
 # ----------------------------------------------------------------------------- GEMM, plain A
 @pytest.mark.parametrize("dt", ALL)
-@pytest.mark.parametrize("M,N,K,act", [
-    (300, 384, 96, 2),      # 128x96 tiles, M tail, GELU (ConvNeXt pw1 shape class)
-    (200, 1000, 768, 0),    # 128x128 tiles with N tail (head fc)
-    (40, 500, 2000, 2),     # 64x128 tiles, N tail (GenConViT fc)
-    (8, 1000, 768, 1),      # 32x128 tiles
-    (130, 192, 1536, 0),    # downsample-conv shape class, long K
-    (256, 96, 48, 3),       # K shorter than one 16-bit K tile
-    (9000, 384, 384, 2),    # pw1 at K = 384 on the LDS-DMA kernel: 142 tiles + an M tail, GELU
-    (8200, 192, 384, 0),    # ... one N tile, no activation
-    (70000, 1536, 384, 2),  # ... the stage-2 shape class at full N: several rounds of workgroups
-])
+@pytest.mark.parametrize("M,N,K,act", gemmcases.cases(gemmcases.BIAS_ACT))
 def test_gemm_bias_act(dt, M, N, K, act):
     dtype = DTYPES[dt]
     case = kcases.gemm("bias_act", M, N, K, dtype, act=act)
@@ -103,7 +93,7 @@ def test_gelu_nan_behaviour_is_documented(dt):
 
 
 @pytest.mark.parametrize("dt", ALL)
-@pytest.mark.parametrize("M,N,K", [(300, 96, 384), (150, 256, 64), (129, 768, 3072)])
+@pytest.mark.parametrize("M,N,K", gemmcases.cases(gemmcases.RESID))
 def test_gemm_layerscale_residual(dt, M, N, K):
     _resid_case(DTYPES[dt], M, N, K)
 
@@ -118,7 +108,7 @@ def _resid_case(dtype, M, N, K):
 
 
 @pytest.mark.parametrize("dt", ALL)
-@pytest.mark.parametrize("M,N,K,splitk,kps", [(8, 256, 512, 4, 128), (40, 384, 1024, 2, 512), (130, 128, 640, 3, 256)])
+@pytest.mark.parametrize("M,N,K,splitk,kps", gemmcases.cases(gemmcases.SPLITK))
 def test_gemm_splitk(dt, M, N, K, splitk, kps):
     dtype = DTYPES[dt]
     case = kcases.gemm("splitk", M, N, K, dtype, k_per_split=kps)
@@ -131,8 +121,7 @@ def test_gemm_splitk(dt, M, N, K, splitk, kps):
 
 # ----------------------------------------------------------------------------- conv as GEMM
 @pytest.mark.parametrize("dt", ALL)
-@pytest.mark.parametrize("n,H,cin,cout", [(2, 16, 16, 32), (3, 8, 32, 64), (2, 14, 128, 256), (1, 28, 64, 128),
-                                          (3, 112, 16, 32)])     # 37632 rows: 294 tiles (256-row tiles were tried for such launches: 99 vs 79 us at B=128)
+@pytest.mark.parametrize("n,H,cin,cout", gemmcases.cases(gemmcases.CONV_POOL))
 def test_conv3x3_relu_maxpool(dt, n, H, cin, cout):
     """ED encoder layers 2-5 (model/genconvit_ed.py:18-32): conv3x3 s1 p1 -> ReLU -> maxpool2."""
     dtype = DTYPES[dt]
@@ -147,7 +136,7 @@ def test_conv3x3_relu_maxpool(dt, n, H, cin, cout):
 
 
 @pytest.mark.parametrize("dt", ALL)
-@pytest.mark.parametrize("n,H,cin,cout", [(2, 16, 16, 32), (3, 8, 32, 64), (2, 28, 64, 128)])
+@pytest.mark.parametrize("n,H,cin,cout", gemmcases.cases(gemmcases.CONV_S2))
 def test_conv3x3_stride2_leaky(dt, n, H, cin, cout):
     """VAE encoder layers 2-4 (model/genconvit_vae.py:19-30), BatchNorm folded by the caller."""
     dtype = DTYPES[dt]
@@ -162,7 +151,7 @@ def test_conv3x3_stride2_leaky(dt, n, H, cin, cout):
 
 
 @pytest.mark.parametrize("dt", ALL)
-@pytest.mark.parametrize("n,H,cin,cout,act", [(2, 7, 256, 128, 1), (3, 14, 64, 32, 3), (2, 28, 32, 16, 1)])
+@pytest.mark.parametrize("n,H,cin,cout,act", gemmcases.cases(gemmcases.CONV_T))
 def test_conv_transpose_2x2(dt, n, H, cin, cout, act):
     """ED / VAE decoder ConvTranspose2d(k=2,s=2) layers (genconvit_ed.py:44-55, genconvit_vae.py:68-76)."""
     dtype = DTYPES[dt]
@@ -840,9 +829,9 @@ def test_fused_mlp_at_a_handful_of_tokens(dt, C, M):
 
 
 @pytest.mark.parametrize("dt", ALL)
-@pytest.mark.parametrize("M", [1, 3])
-@pytest.mark.parametrize("N,K", [(3072, 768), (768, 3072), (768, 1536)])
-@pytest.mark.parametrize("epi", ["bias_gelu", "layerscale_residual"])
+@pytest.mark.parametrize("M", gemmcases.STAGE3_ROWS)
+@pytest.mark.parametrize("N,K", gemmcases.STAGE3_NK)
+@pytest.mark.parametrize("epi", list(gemmcases.STAGE3_KERNEL))
 def test_gemm_at_one_and_three_rows_with_stage3_shapes(dt, M, N, K, epi):
     """The tile GEMMs of ConvNeXt-T's stage 3 (fc1, fc2, the down-sampling conv) as one small-resolution frame runs them:
     1 token at res 32, a few for a small batch.  Rows behind M carry a sentinel."""
@@ -930,14 +919,7 @@ def mlp_lnp_case(dtype, C, segs, **kw):
 
 # ----------------------------------------------------------------------------- LDS-DMA pipelined GEMM
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
-@pytest.mark.parametrize("M,N,K,act", [
-    (700, 1536, 384, 2),     # ConvNeXt stage-2 pw1 class (GELU)
-    (513, 192, 32, 0),       # one K tile  (pipeline shorter than the ring)
-    (256, 192, 64, 0),       # two K tiles
-    (300, 384, 96, 2),       # three K tiles, M tail
-    (384, 768, 128, 0),      # exactly ring depth
-    (1000, 384, 3072, 0),    # long K
-])
+@pytest.mark.parametrize("M,N,K,act", gemmcases.cases(gemmcases.DMA_BIAS_ACT))
 def test_gemm_lds_dma_pipeline_bias_act(dt, M, N, K, act):
     dtype = DTYPES[dt]
     A, W = q(rnd((M, K), 1), dtype), q(rnd((N, K), 2, 1 / math.sqrt(K)), dtype)
@@ -948,13 +930,13 @@ def test_gemm_lds_dma_pipeline_bias_act(dt, M, N, K, act):
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
-@pytest.mark.parametrize("M,N,K", [(1000, 384, 1536), (257, 768, 3072), (640, 192, 768)])
+@pytest.mark.parametrize("M,N,K", gemmcases.cases(gemmcases.DMA_RESID))
 def test_gemm_lds_dma_pipeline_residual(dt, M, N, K):
     _resid_case(DTYPES[dt], M, N, K)
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
-@pytest.mark.parametrize("M,N,K,act", [(8229, 1536, 384, "gelu"), (12544, 3072, 768, "gelu"), (16400, 768, 128, "none")])
+@pytest.mark.parametrize("M,N,K,act", gemmcases.cases(gemmcases.DMA_BIAS_ACT_MANY))
 def test_gemm_lds_dma_many_tiles_bias_act(dt, M, N, K, act):
     """Several waves of tiles per CU (the B=128 shapes of stages 2/3); M has a ragged last tile."""
     dtype = DTYPES[dt]
@@ -968,7 +950,7 @@ def test_gemm_lds_dma_many_tiles_bias_act(dt, M, N, K, act):
 
 
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
-@pytest.mark.parametrize("M,N,K", [(32868, 384, 1536), (16500, 768, 3072)])
+@pytest.mark.parametrize("M,N,K", gemmcases.cases(gemmcases.DMA_RESID_MANY))
 def test_gemm_lds_dma_many_tiles_residual(dt, M, N, K):
     _resid_case(DTYPES[dt], M, N, K)
 

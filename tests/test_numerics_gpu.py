@@ -12,7 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from genconvit_amd import _lib
-from tests import kutil, numutil as nu
+from tests import gemmcases, kutil, numutil as nu
 from tests.kutil import DTYPES, dev, gemm, ptr, rnd
 
 pytestmark = pytest.mark.gpu
@@ -65,18 +65,10 @@ def _judge_gelu(dt, offgrid, got, pre, what, delta):
     assert ok, f"{what}: error beyond rounding {ex:.3e} > delta {delta:.3e}"
 
 
-# (name, storage dtypes, M, N = K, ldc): the tile configuration launch_gemm (csrc/gemm_impl.h) picks for A_PLAIN, EPI_BIAS_ACT
-# from M, N and t128 = ceil(M / 128) * ceil(N / 128); N = 128 / 96 and an ldc that is no multiple of 8 keep the 16-bit launches
-# off the LDS-DMA kernel (gemm_glds_applicable), which the last case is for.  M is never a multiple of the tile.
-_GEMM_SITES = [
-    ("f32", ["f32"], 1021, 128, 128),          # fp32 storage: act_fn / erf_fast
-    ("C1", H16, 517, 128, 128),                # t128 = 5 < 48: 32 x 128 tiles
-    ("C2", H16, 6200, 128, 128),               # t128 = 49 in [48, 96): 64 x 128 tiles
-    ("C3S", H16, 12300, 96, 96),               # t128 = 97, N % 96 == 0, K % 64 = 32: 128 x 96 tiles on 32-deep K tiles
-    ("C3", H16, 6200, 192, 196),               # t128 = 98, N % 96 == 0, K % 64 == 0: 128 x 96 tiles (ldc 196: not LDS-DMA)
-    ("C4", H16, 12300, 128, 128),              # t128 = 97: 128 x 128 tiles
-    ("glds", H16, 331, 192, 192),              # N = 192, M >= 256, everything 16-byte aligned: gemm_glds_kernel
-]
+# (name, storage dtypes, M, N = K, ldc) from tests/gemmcases.py: one site per tile of the plain bias + activation launch and the
+# LDS-DMA kernel, each asserted below through gcv_gemm_plan
+_GEMM_SITES = gemmcases.cases(gemmcases.GELU_SITES)
+_GEMM_KERNEL = {c[0]: k for c, k in gemmcases.GELU_SITES}
 
 
 @pytest.mark.parametrize("offgrid", [False, True], ids=["ongrid", "offgrid"])
@@ -85,6 +77,8 @@ def test_gelu_gemm_epilogue_over_every_value(site, dt, offgrid):
     """gcv_k_gemm, EPI_BIAS_ACT with GELU and Wt = I: the accumulator is A exactly, the pre-activation fp32(A + bias)."""
     name, _, M, N, ldc = site
     dtype = DTYPES[dt]
+    launch = gemmcases.linear(M, N, N, _lib.ACT_GELU, ldc=ldc)
+    assert gemmcases.plan(dt, launch)[:6] == gemmcases.resolve(_GEMM_KERNEL[name], dt)
     vals = _values(dt, offgrid)
     A = nu.tile_to(vals, M * N).reshape(M, N)
     bias = nu.offgrid_bias(N) if offgrid else torch.zeros(N)
