@@ -77,6 +77,8 @@ SIGNATURES = {
     "gcv_face_crop_preprocess": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "gcv_cam_overlay": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_float,
                                 c_int, c_void_p, c_void_p]),
+    "gcv_scan_annotate": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
+                                  c_void_p, c_void_p]),
     "gcv_track_match": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gcv_track_chain": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gcv_frame_hist": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
@@ -1022,6 +1024,82 @@ def cam_overlay(frames_u8, boxes, maps, alpha=0.5, weighted=True, lut=None, out=
     check(lib.gcv_cam_overlay(src.data_ptr(), nf, h, w, bd.data_ptr() if n else None, n, maps.data_ptr() if n else None,
                               mh, mw, lut.data_ptr(), float(alpha), 1 if weighted else 0, out.data_ptr(),
                               current_stream_ptr(dev)), "gcv_cam_overlay")
+    return out
+
+
+ANNOTATE_THICK_MAX, ANNOTATE_LABEL_MAX, ANNOTATE_LANES_MAX = 16, 999, 8
+
+
+def _check_marks(what, marks, nf, h, w):
+    """``marks`` as an (n,8) int32 host tensor (``gcv_scan_annotate``, include/genconvit_hip.h); a mark outside its (h, w)
+    frame, a ``thick`` outside 1 ... 16, a ``label`` outside -1 ... 999 or a colour outside 0 ... 0xFFFFFF is an error that
+    names the row."""
+    import torch
+    m = torch.as_tensor(marks, dtype=torch.int64).reshape(-1, 8).cpu()
+    if m.numel():
+        f, top, right, bottom, left, colour, thick, label = m.unbind(1)
+        ok = (f >= 0) & (f < nf) & (top >= 0) & (left >= 0) & (bottom <= h) & (right <= w) & (top < bottom) & (left < right)
+        for bad, why in ((~ok, f"lies outside its {h}x{w} frame"),
+                         ((thick < 1) | (thick > ANNOTATE_THICK_MAX), f"has a thick outside 1 ... {ANNOTATE_THICK_MAX}"),
+                         ((label < -1) | (label > ANNOTATE_LABEL_MAX), f"has a label outside -1 ... {ANNOTATE_LABEL_MAX}"),
+                         ((colour < 0) | (colour > 0xFFFFFF), "has a colour outside 0 ... 0xFFFFFF")):
+            if bool(bad.any()):
+                raise GenConViTHipError(f"{what}: mark {int(bad.nonzero()[0])} {why}")
+    return m.to(torch.int32)
+
+
+def scan_annotate(frames_u8, frame_no, marks, timeline=None, strip=0, out=None):
+    """Draw a scan's marks and its timeline onto the frames (``gcv_scan_annotate``, include/genconvit_hip.h: the arithmetic
+    is stated there).  ``frames_u8``: (F,H,W,3) uint8 device tensor (RGB), of any alignment; ``frame_no``: F integers, each
+    frame's number on the timeline; ``marks``: (n,8) integers (frame index, top, right, bottom, left, colour, thick,
+    label), applied in row order — colours are packed r | g << 8 | b << 16, ``thick`` is the outline's width and the
+    label's cell size in pixels, 1 ... 16, ``label`` a number 0 ... 999 drawn in the box's corner or -1 for none;
+    ``timeline``: (L, T) integer tensor of packed colours, 1 <= L <= 8, drawn over the lowest ``strip`` rows of every
+    frame, lane l over its share of them, with a white cursor at ``frame_no``; ``strip`` = 0 (then ``timeline`` may be
+    None): no timeline; ``out``: a contiguous tensor like the frames to write into (``out=frames_u8`` draws in place).
+    Returns the (F,H,W,3) uint8 frames with the drawing."""
+    import torch
+    src, (nf, h, w) = _check_frames(frames_u8, "scan_annotate: frames must be a uint8 device tensor of shape (F,H,W,3)",
+                                    on_device=False)
+    dev = frames_u8.device
+    m = _check_marks("scan_annotate", marks, nf, h, w)
+    n = m.shape[0]
+    try:
+        fno = torch.as_tensor(frame_no).reshape(-1).cpu()
+    except (TypeError, ValueError, RuntimeError):
+        fno = None
+    if fno is None or fno.is_floating_point() or fno.dtype == torch.bool or fno.numel() != nf:
+        raise GenConViTHipError(f"scan_annotate: frame_no must hold {nf} integers, one per frame")
+    if isinstance(strip, bool) or not isinstance(strip, int) or strip < 0:
+        raise GenConViTHipError(f"scan_annotate: strip {strip} must be an integer >= 0")
+    lanes = t = 0
+    if strip > 0:
+        if not (torch.is_tensor(timeline) and not timeline.is_floating_point() and not timeline.is_complex()
+                and timeline.dtype != torch.bool and timeline.dim() == 2 and timeline.shape[0] >= 1 and timeline.shape[1] >= 1):
+            raise GenConViTHipError("scan_annotate: timeline must be an (L, T) integer tensor, L, T >= 1")
+        lanes, t = (int(v) for v in timeline.shape)
+        if lanes > ANNOTATE_LANES_MAX or lanes > strip:
+            raise GenConViTHipError(f"scan_annotate: a timeline of {lanes} lanes on a strip of {strip} rows; at most "
+                                    f"{ANNOTATE_LANES_MAX} lanes, and no more lanes than rows")
+        if strip > h:
+            raise GenConViTHipError(f"scan_annotate: a strip of {strip} rows on frames of {h}")
+        if t * w >= 1 << 31:
+            raise GenConViTHipError(f"scan_annotate: a timeline of T = {t} on frames {w} wide; T * W must stay below 2^31")
+    if out is not None and not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.shape == frames_u8.shape
+                                and out.device == dev and out.is_contiguous()):
+        raise GenConViTHipError(f"scan_annotate: out must be a contiguous uint8 tensor of shape {tuple(frames_u8.shape)} on {dev}")
+    if not frames_u8.is_cuda:                # last, so that the checks above do not need a device
+        raise GenConViTHipError("scan_annotate: frames must be a uint8 device tensor of shape (F,H,W,3); there is no CPU path")
+    if out is None:
+        out = torch.empty((nf, h, w, 3), dtype=torch.uint8, device=dev)
+    lib = load()
+    if nf * h * w == 0:
+        return out
+    md, fd = m.to(dev), fno.to(torch.int32).to(dev)
+    tl = (timeline.to(dev).long() & 0xFFFFFF).to(torch.int32).contiguous() if strip > 0 else None
+    check(lib.gcv_scan_annotate(src.data_ptr(), nf, h, w, fd.data_ptr(), md.data_ptr() if n else None, n,
+                                tl.data_ptr() if strip > 0 else None, lanes, t, strip, out.data_ptr(),
+                                current_stream_ptr(dev)), "gcv_scan_annotate")
     return out
 
 

@@ -829,6 +829,14 @@ int gcv_cam_overlay(const void* frames_u8_nhwc, int nframes, int H, int W, const
                             weighted, (unsigned char*)out_u8_nhwc, (hipStream_t)stream);
 }
 
+int gcv_scan_annotate(const void* frames_u8_nhwc, int nframes, int H, int W, const int* frame_no, const int* marks8, int n,
+                      const unsigned* timeline, int lanes, int T, int strip, void* out_u8_nhwc, gcv_stream stream) {
+  GCV_REQUIRE(frames_u8_nhwc && out_u8_nhwc && (marks8 || n <= 0) && ((frame_no && timeline) || strip <= 0),
+              "scan annotate: null pointer");
+  return launch_scan_annotate((const unsigned char*)frames_u8_nhwc, nframes, H, W, frame_no, marks8, n, timeline, lanes, T,
+                              strip, (unsigned char*)out_u8_nhwc, (hipStream_t)stream);
+}
+
 int gcv_track_match(const void* frames_u8_nhwc, int nframes, int H, int W, const int* jobs17, int n, int grid, int radius,
                     int* out4, gcv_stream s) {
   GCV_REQUIRE(n <= 0 || (frames_u8_nhwc && jobs17 && out4), "track match: null pointer");

@@ -79,6 +79,9 @@ template <typename T> int launch_face_crop_preprocess(const unsigned char* frame
 int launch_cam_overlay(const unsigned char* frames, int nframes, int H, int W, const int* boxes5, int n, const float* maps,
                        int mh, int mw, const unsigned char* lut768, float alpha, int weighted, unsigned char* out,
                        hipStream_t s);
+// annotate.hip: a scan's marks (outline, number tab) and its timeline strip drawn onto the frames, uint8 RGB in and out
+int launch_scan_annotate(const unsigned char* frames, int nframes, int H, int W, const int* frame_no, const int* marks8,
+                         int n, const unsigned* timeline, int lanes, int T, int strip, unsigned char* out, hipStream_t s);
 // follow.hip: block matching of a face between two detector frames, n jobs of 17 ints -> n rows (oy, ox, cost, cost0)
 int launch_track_match(const unsigned char* frames, int nframes, int H, int W, const int* jobs17, int n, int grid,
                        int radius, int* out4, hipStream_t s);

@@ -5,7 +5,7 @@ Same names and argument meaning (``load_genconvit``, ``preprocess_frame``, ``pre
 ``is_video``, ``set_result``, ``store_result``), plus what the reference lacks: evidence maps (``explain_*``) and the
 whole-video scan with per-track sliding-window verdicts (``scan_frames``, ``scan_video``; ``follow_tracks`` moves the
 boxes of frames the detector skipped onto the face, ``shot_cuts`` finds the hard cuts at which tracks end, ``shot_transitions`` the fades and dissolves whose frames stay out
-of them).  ``prediction.py`` star-imports this module and
+of them; ``render_scan`` / ``render_video`` draw the scan's result back onto the frames).  ``prediction.py`` star-imports this module and
 relies on ``torch``/``os``/``np`` coming along, so they stay module globals.  The heavy CPU-side
 dependencies (dlib, face_recognition, decord) are imported lazily inside the video / face
 functions so the model path imports on a box without them; cv2 is not needed any more (the crop +
@@ -1246,6 +1246,168 @@ def scan_video(vid, model, every=1, max_frames=None, **kw):
     res = scan_frames(frames, model, **kw)
     res["frame_index"] = [int(i) for i in index]
     return res
+
+
+RENDER_NO_SCORE, RENDER_QUIET, RENDER_FAKE = 0x404040, 0x202020, 0x0000FF     # packed r | g << 8 | b << 16
+
+
+def _render_plan(what, fr, res, label, eps, lut, thick, strip, max_frames, max_batch, which):
+    """The checks of ``render_scan``, all before anything runs, and everything it draws that does not need a device: returns
+    ``(rows, marks, timeline, strip, evidence)`` — the crop rows, one mark per row (``gcv_scan_annotate``'s 8 columns, frame
+    numbers of the whole video), the (2, F) int64 timeline, the strip height, and the sorted indices of the rows inside a
+    FAKE segment of their track."""
+    nf, h, w = (int(v) for v in fr.shape[:3])
+    need = ("boxes", "track_offsets", "frame_scores", "segments")
+    if not isinstance(res, dict) or any(k not in res for k in need):
+        raise ValueError(f"{what}: res must be the dict scan_frames returned, with {', '.join(need)}")
+    if label not in ("track", "person", None):
+        raise ValueError(f"{what}: unknown label {label!r}: accepted values are 'track', 'person' and None")
+    if label == "person" and "persons" not in res:
+        raise ValueError(f"{what}: label='person' needs res['persons'] (scan_frames(..., persons=True))")
+    if which not in ("ed", "vae", "mean"):
+        raise ValueError(f"unknown map {which!r}: accepted values are 'ed', 'vae' and 'mean'")
+    for name, v in (("max_frames", max_frames), ("max_batch", max_batch)):
+        if not _is_whole(v) or v < 1:
+            raise ValueError(f"{what}: {name} {v} must be an integer >= 1")
+    rows = [tuple(int(v) for v in b) for b in res["boxes"]]
+    offsets = [int(v) for v in res["track_offsets"]]
+    n, scores = len(rows), res["frame_scores"]
+    if not offsets or offsets[0] != 0 or offsets[-1] != n or any(a > b for a, b in zip(offsets, offsets[1:])):
+        raise ValueError(f"{what}: res['track_offsets'] does not partition the {n} crop rows")
+    if not (torch.is_tensor(scores) and scores.dim() == 2 and scores.shape[0] == n and (n == 0 or scores.shape[1] >= 1)):
+        raise ValueError(f"{what}: res['frame_scores'] must hold one row per crop row ({n})")
+    for i, b in enumerate(rows):
+        if len(b) != 5 or not 0 <= b[0] < nf:
+            raise ValueError(f"{what}: crop row {i} is not (frame, top, right, bottom, left) on one of the {nf} frames")
+    if eps is not None and eps.shape[0] != n:
+        raise ValueError(f"{what}: eps holds {eps.shape[0]} rows for {n} crops")
+    if thick is None:
+        thick = min(16, max(1, min(h, w) // 240))
+    if not _is_whole(thick) or not 1 <= thick <= _lib.ANNOTATE_THICK_MAX:
+        raise ValueError(f"{what}: thick {thick} must be an integer in 1 ... {_lib.ANNOTATE_THICK_MAX}")
+    if strip is None:
+        strip = min(h, max(4, h // 36)) if h >= 2 else 0
+    if not _is_whole(strip) or not (strip == 0 or 2 <= strip <= h):
+        raise ValueError(f"{what}: strip {strip} must be 0 or an integer in 2 ... {h}: two lanes, one row each at the least")
+    ntracks = len(offsets) - 1
+    track_of = [t for t in range(ntracks) for _ in range(offsets[t + 1] - offsets[t])]
+    names = list(range(ntracks)) if label == "track" else [int(v) for v in res["persons"]["of_track"]] if label == "person" \
+        else [-1] * ntracks
+    if len(names) != ntracks:
+        raise ValueError(f"{what}: res['persons']['of_track'] holds {len(names)} entries for {ntracks} tracks")
+    lut = (_lib.jet_lut() if lut is None else lut).cpu().to(torch.int64)
+    if tuple(lut.shape) != (256, 3):
+        raise ValueError(f"{what}: lut must be a (256,3) uint8 tensor")
+    colours = (lut[:, 0] | lut[:, 1] << 8 | lut[:, 2] << 16).tolist()
+    fake = scores[:, 0].float().cpu() if n else torch.empty(0)
+    k = torch.round(fake * 255.0).clamp(0, 255).to(torch.int64).tolist()
+    marks = [(*rows[i], colours[k[i]], int(thick), names[track_of[i]] if 0 <= names[track_of[i]] <= _lib.ANNOTATE_LABEL_MAX else -1)
+             for i in range(n)]
+    try:
+        _lib._check_marks(what, marks, nf, h, w)
+    except _lib.GenConViTHipError as e:
+        raise ValueError(str(e)) from None
+    timeline =torch.tensor([[RENDER_NO_SCORE] * nf, [RENDER_QUIET] * nf], dtype=torch.int64)
+    best = {}
+    for i, b in enumerate(rows):                                    # the highest FAKE score on each frame
+        best[b[0]] = max(best.get(b[0], 0), k[i])
+    for f, kk in best.items():
+        timeline[0, f] = colours[kk]
+    evidence = set()
+    for seg in res["segments"]:
+        t, first, last = (int(v) for v in seg[:3])
+        if not 0 <= t < ntracks:
+            raise ValueError(f"{what}: segment {tuple(seg)} names track {t} of {ntracks}")
+        timeline[1, max(first, 0):min(last, nf - 1) + 1] = RENDER_FAKE
+        evidence.update(i for i in range(offsets[t], offsets[t + 1]) if first <= rows[i][0] <= last)
+    return rows, marks, timeline, int(strip), sorted(evidence)
+
+
+def render_scan(frames, res, model=None, evidence=True, label="track", eps=None, layer="s3", which="mean", alpha=0.5,
+                weighted=True, lut=None, thick=None, strip=None, max_frames=128, max_batch=128, sink=None):
+    """The result of ``scan_frames`` drawn onto the frames it was run on, for the reviewer of a flagged video.  ``frames``:
+    the uint8 (F,H,W,3) RGB frames that were scanned, numpy or a tensor on either device (they are not changed); ``res``:
+    what ``scan_frames`` returned for them — ``boxes``, ``track_offsets``, ``frame_scores`` and ``segments`` are read, and
+    ``persons`` for ``label="person"``.  Anything else, a crop row on a frame the video does not have, a ``label`` other than
+    "track", "person" or None, and "person" without ``res["persons"]`` are a ValueError before anything runs.  Drawn, by
+    ``_lib.scan_annotate`` (``gcv_scan_annotate``, include/genconvit_hip.h), all policy being this function's:
+      marks     one per crop row, in the (track, frame) order of ``res["boxes"]``: the box's outline, ``thick`` pixels wide
+                (default min(16, max(1, min(H, W) // 240))), in the colour ``lut[k]``, k = round(255 * the row's FAKE score)
+                — column 0 of ``frame_scores``, the class ``real_or_fake`` calls FAKE; ``lut``: (256,3) uint8, default
+                ``_lib.jet_lut()`` — and in the box's corner the number of its track, or of its person
+                (``res["persons"]["of_track"]``) for ``label="person"``; numbers above 999, and ``label=None``, draw no tab
+      timeline  the lowest ``strip`` rows of every frame (default min(H, max(4, H // 36)); 0: none), one column span per
+                scanned frame, T = F, in two lanes: above, the ``lut`` colour of the highest FAKE score among the crops on
+                that frame, 0x404040 where there is none; below, red on the frames inside a segment of any track,
+                0x202020 elsewhere; a white cursor marks the frame's own place
+      evidence  when ``model`` is given and ``evidence`` is true: for the crop rows inside a FAKE segment of their own track
+                (first <= frame <= last for a segment (track, first, last, _)), the Grad-CAM map of a forward of ``model``
+                is drawn over the box before the marks, as ``explain_frames`` does: sub-batches of at most ``max_batch``
+                rows, each one ``_lib.face_crop_preprocess`` on the group's slab, one ``model.explain(x, eps=their rows of
+                eps, upsample=False, layer=layer)`` and one ``_lib.cam_overlay`` of ``_overlay_maps(model, cams, which)``
+                with ``alpha``, ``weighted`` and ``lut``.  A sub-batch shorter than ``max_batch`` is filled up to it with
+                copies of its last row, whose maps are dropped: the 16-bit networks choose their kernels by batch size,
+                and a row's map differs in its last bits between a batch of 2 and a batch of 7 (it does not depend on
+                the row's place or on the other rows), so without the fill the drawn frames would depend on how many
+                such rows share a group, that is on ``max_frames``.  They do depend on ``max_batch``.  ``eps``:
+                (n_crops, latent) in crop order, as ``scan_frames`` takes it.  With ``eps=None`` the VAE draws its own noise: the maps are then those of a fresh forward, not
+                of the scan's.  The logits of these forwards are dropped (``reference_logits_dtype`` does not matter).
+    Consecutive frames [g, g + ``max_frames``) form a group: one upload of the group's frames, the overlay calls, one
+    ``_lib.scan_annotate`` in place, so device memory is bounded by the group.  Every frame is rendered, faceless ones
+    included: they carry the timeline.  With ``sink``, ``sink(g, slab)`` is called per group in order with the rendered
+    uint8 (m,H,W,3) device tensor (the caller encodes or stores it; the slab is not reused) and None is returned; otherwise
+    the rendered frames come back as one uint8 (F,H,W,3) CPU tensor.  With no crop row the frames carry the timeline only
+    (they are untouched when ``strip`` is 0) and ``model`` is not called.
+    Not shown: how accurate the scores are, and whether a Grad-CAM map is faithful to what the network used.  Encoding the
+    frames into a video file is the caller's."""
+    fr = _as_frames("render_scan", frames)
+    nf, h, w = (int(v) for v in fr.shape[:3])
+    rows, marks, timeline, strip, rows_ev = _render_plan("render_scan", fr, res, label, eps, lut, thick, strip, max_frames,
+                                                         max_batch, which)
+    p = next(model.parameters()) if model is not None else None
+    dev = p.device if p is not None else fr.device if fr.is_cuda else torch.device(device)
+    if model is None or not evidence:
+        rows_ev = []
+    timeline = timeline.to(dev)
+    lut = None if lut is None else lut.to(dev)
+    done = []
+    with torch.no_grad():
+        for g in range(0, nf, max_frames):
+            m = min(max_frames, nf - g)
+            slab = fr[g:g + m].to(dev, copy=True)                   # one upload; drawn on in place
+            ids = [i for i in rows_ev if g <= rows[i][0] < g + m]
+            for s in range(0, len(ids), max_batch):
+                sub = ids[s:s + max_batch]
+                full = sub + sub[-1:] * (max_batch - len(sub))      # always max_batch rows: see the docstring
+                boxes = [(rows[i][0] - g, *rows[i][1:]) for i in full]
+                x = _lib.face_crop_preprocess(slab, boxes, dtype=p.dtype)
+                noise = None if eps is None else eps[torch.as_tensor(full, device=eps.device)].to(dev)
+                _, cams = model.explain(x, eps=noise, upsample=False, layer=layer)
+                _lib.cam_overlay(slab, boxes[:len(sub)], _overlay_maps(model, cams, which)[:len(sub)], alpha, weighted, lut,
+                                 out=slab)
+            here = [(mk[0] - g, *mk[1:]) for mk in marks if g <= mk[0] < g + m]
+            _lib.scan_annotate(slab, list(range(g, g + m)), here, timeline if strip else None, strip, out=slab)
+            if sink is not None:
+                sink(g, slab)
+            else:
+                done.append(slab.cpu())
+    if sink is not None:
+        return None
+    return torch.cat(done) if done else fr.cpu().clone()
+
+
+def render_video(vid, model, every=1, max_frames=None, scan=None, **kw):
+    """``scan_frames`` and ``render_scan`` on the frames ``range(0, len, every)[:max_frames]`` of the video file ``vid``, read
+    once: returns ``(res, rendered)``.  ``scan``: a dict of ``scan_frames``'s keyword arguments; ``kw``: ``render_scan``'s
+    (its own ``max_frames`` keeps its default here).  ``res`` also holds ``frame_index``, as ``scan_video``'s does.  An
+    ``eps`` is given to each of the two on its own.  Decoding is third-party CPU code (decord) and encoding the rendered
+    frames is the caller's."""
+    if every < 1:
+        raise ValueError(f"render_video: every {every} must be at least 1")
+    frames, index = _read_frames(vid, lambda n: list(range(0, n, every))[:max_frames])
+    res = scan_frames(frames, model, **(scan or {}))
+    res["frame_index"] = [int(i) for i in index]
+    return res, render_scan(frames, res, model, **kw)
 
 
 def df_face(vid, num_frames, net):

@@ -223,6 +223,43 @@ int gcv_cam_overlay(const void* frames_u8_nhwc, int nframes, int H, int W, const
                     int mh, int mw, const unsigned char* lut768, float alpha, int weighted, void* out_u8_nhwc,
                     gcv_stream stream);
 
+/* The way back of a whole-video scan: draw its result onto the frames — per crop row an outline of the face box with a
+ * number tab in its corner, and along the bottom edge a timeline strip with a cursor at the frame's own place.  All marks
+ * of a group of frames and the strip in one launch, one read and one write of the frames.
+ *   frames    (nframes,H,W,3) uint8 RGB on the device, any byte alignment      out  the same shape; out == frames (in place)
+ *             is allowed, and blocks that nothing touches are then not written
+ *   frame_no  int32 device array of nframes: each frame's number on the timeline (read only where strip > 0)
+ *   marks8    int32 device array of n rows (frame, top, right, bottom, left, colour, thick, label); frame counts the
+ *             frames of this call
+ *   timeline  (lanes, T) uint32 on the device; lanes, T, strip: see below.  strip == 0: no timeline, the three are ignored
+ * Colours are packed r | g << 8 | b << 16; the top byte is ignored.  Everything is integer arithmetic (fixed, so that a CPU
+ * restatement is bit-equal: tests/annotateutil.py); a / b is floor division of non-negative integers.  Pixel (f, y, x)
+ * starts as p = frames[f][y][x] and goes through the following, later steps over earlier ones:
+ *   marks     in row order.  A row takes part when frame == f, 0 <= top < bottom <= H, 0 <= left < right <= W,
+ *             1 <= thick <= 16 and -1 <= label <= 999; any other row draws nothing.  A mark draws inside its box only
+ *             (top <= y < bottom, left <= x < right):
+ *               outline  p = colour when y - top < thick || bottom - 1 - y < thick || x - left < thick || right - 1 - x < thick
+ *               tab      when label >= 0: nd = the number of decimal digits of label (1 ... 3); cy = (y - top) / thick,
+ *                        cx = (x - left) / thick; the pixel is in the tab when cy < 7 && cx < 4 nd + 1 (the box clips the
+ *                        tab; the tab is over the outline).  In the tab p = colour, unless the pixel is ink: 1 <= cy <= 5,
+ *                        cx >= 1, gx = (cx - 1) % 4 < 3 and bit (cy - 1) * 3 + gx of FONT[digit (cx - 1) / 4 of label,
+ *                        most significant first] set.  Ink is 0x000000 when (77 r + 150 g + 29 b) >> 8 >= 128 for the
+ *                        mark's colour, else 0xFFFFFF.
+ *               FONT     3 x 5 cells per digit, rows top to bottom, bit row * 3 + column:
+ *                          0: 111 101 101 101 111    1: 010 110 010 010 111    2: 111 001 111 100 111    3: 111 001 111 001 111
+ *                          4: 101 101 111 001 001    5: 111 100 111 001 111    6: 111 100 111 101 111    7: 111 001 001 001 001
+ *                          8: 111 101 111 101 111    9: 111 101 111 001 111
+ *   timeline  when strip > 0, over the marks: 1 <= lanes <= 8, lanes <= strip <= H, T >= 1, T W < 2^31.  For y >= H - strip:
+ *               lane = ((y - (H - strip)) lanes) / strip;  t = (x T) / W;  p = timeline[lane T + t] & 0xFFFFFF
+ *               cursor  c = frame_no[f]; if 0 <= c < T: x0 = (c W) / T, x1 = max(x0 + 1, ((c + 1) W) / T), and p = 0xFFFFFF
+ *                       for x0 <= x < x1
+ * Every pixel is read and written by one thread, so overlapping and nested marks are deterministic.  n == 0 && strip == 0
+ * copies the frames (nothing is launched when in place).  Refused before anything is launched (gcv_last_error() says
+ * why): nframes, H or W outside 1 ... 65536, nframes H W >= 2^31, n or strip negative, the timeline limits above.  The call
+ * allocates, copies and synchronises nothing.  Not done here: text other than the number, anti-aliasing, video encoding. */
+int gcv_scan_annotate(const void* frames_u8_nhwc, int nframes, int H, int W, const int* frame_no, const int* marks8, int n,
+                      const unsigned* timeline, int lanes, int T, int strip, void* out_u8_nhwc, gcv_stream stream);
+
 /* Follow a face between two detector frames: integer block matching of n (track, skipped frame) jobs in one launch.
  * A whole-video scan runs its CPU face detector on every k-th frame; in a skipped frame the face is searched around the
  * interpolated ("prior") box, with the two detected faces around the gap as templates.
