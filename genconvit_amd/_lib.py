@@ -104,6 +104,8 @@ SIGNATURES = {
                                 c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "gcv_k_dwconv7_ln": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                  c_int, c_int, c_float, c_void_p]),
+    "gcv_k_dwconv7_ln2": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p]),
     "gcv_dw_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "gcv_convnext_res_ok": (c_int, [c_int, c_int]),
     "gcv_k_ln_patchify": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,

@@ -661,6 +661,13 @@ int gcv_k_dwconv7_ln(int dtype, const void* x, const float* wdw, const float* bd
   DISPATCH_DT(dtype, launch_dwconv7_ln<T>((const T*)x, wdw, bdw, lnw, lnb, (T*)y, nimg, H, W, C, eps, (hipStream_t)s));
 }
 
+int gcv_k_dwconv7_ln2(int dtype, const void* x0, void* y0, int nimg0, int H0, int W0, const void* x1, void* y1,
+                      int nimg1, int H1, int W1, const float* wdw, const float* bdw, const float* lnw, const float* lnb,
+                      int C, float eps, gcv_stream s) {
+  DISPATCH_DT(dtype, launch_dwconv7_ln2<T>((const T*)x0, (T*)y0, nimg0, H0, W0, (const T*)x1, (T*)y1, nimg1, H1, W1, wdw,
+                                           bdw, lnw, lnb, C, eps, (hipStream_t)s));
+}
+
 int gcv_dw_plan(int dtype, int nimg, int H, int W, int C, int aligned, int* out5) {
   GCV_REQUIRE(out5, "null out5");
   DwPlan p;

@@ -1,5 +1,5 @@
 // The depthwise 7x7 + LayerNorm of the ConvNeXt block (run tag cnx.dwconv7_ln): dw_select picks one of its six kernels and
-// plans its grid, launch_dwconv7_ln launches from that plan.  Included by dw_{f32,f16,bf16}.hip, which compile the band
+// plans its grid, launch_dwconv7_ln launches from that plan, launch_dwconv7_ln2 two such plans in one grid.  Included by dw_{f32,f16,bf16}.hip, which compile the band
 // kernels with -fno-slp-vectorize: left alone, hipcc packs the rolling kernel's tap FMAs into v_pk_fma_f32 (no faster than
 // two v_fma_f32 on gfx950) whose even-aligned register pairs cost ~290 spilled registers.  The tile kinds are compiled in
 // kern_{f32,f16,bf16}.hip (kernels_impl.h, launch_dw_tile).
@@ -11,6 +11,7 @@
 #include "dwconv_pair.h"
 #include "dwconv_roll.h"
 #include "kernels.h"
+#include "kernels_dev.h"
 
 namespace gcv {
 
@@ -134,9 +135,134 @@ int launch_dwconv7_ln(const T* x, const float* wdw, const float* bdw, const floa
   });
 }
 
+// ---- two image groups in one launch (the 224- and the 112-pixel segment of the VAE's merged backbone pass) ----
+// Each group keeps the kernel, bands and grid dw_select plans for it alone; the two grids are laid end to end and a workgroup
+// runs the body of the group its index falls into, so every image's bands are computed by the device code of the
+// single-group launch under the same plan.  The launch takes the larger block and the larger LDS of the two; the waves the
+// smaller body has no use for return before its first barrier.
+template <typename T> struct DwGroupArgs {
+  const T* x;
+  T* y;
+  int H, band_rows, nbands;
+};
+
+// the body of a kind as a device function of (LDS base, workgroup index, workgroups of its group)
+template <typename T, class S> struct DwBody;
+template <typename T, int C, int N> struct DwBody<T, DwShape<DwKind::Roll, C, N>> {
+  static constexpr int NT = DwRollLds<T, C, N>::NT, lds = DwRollLds<T, C, N>::bytes;
+  __device__ static __forceinline__ void run(unsigned char* l, int bid, int nwg, const DwGroupArgs<T>& a, const float* wdw,
+                                             const float* bdw, const float* lnw, const float* lnb, float eps) {
+    dwconv7_ln_roll_body<T, C, N>(l, bid, nwg, a.x, wdw, bdw, lnw, lnb, a.y, a.H, a.band_rows, a.nbands, eps);
+  }
+};
+template <typename T, int C, int N> struct DwBody<T, DwShape<DwKind::Mfma, C, N>> {
+  static constexpr int NT = DwMfmaLds<T, C, N>::NT, lds = DwMfmaLds<T, C, N>::bytes;
+  __device__ static __forceinline__ void run(unsigned char* l, int bid, int nwg, const DwGroupArgs<T>& a, const float* wdw,
+                                             const float* bdw, const float* lnw, const float* lnb, float eps) {
+    dwconv7_ln_mfma_body<T, C, N>(l, bid, nwg, a.x, wdw, bdw, lnw, lnb, a.y, a.H, a.band_rows, a.nbands, eps);
+  }
+};
+template <typename T, int C, int S> struct DwBody<T, DwShape<DwKind::Tiny, C, S>> {
+  static constexpr int NT = C, lds = 0;              // its partial sums are static LDS, in front of the dynamic block
+  __device__ static __forceinline__ void run(unsigned char*, int bid, int, const DwGroupArgs<T>& a, const float* wdw,
+                                             const float* bdw, const float* lnw, const float* lnb, float eps) {
+    dwconv7_ln_tiny_body<T, C, S>(bid, a.x, wdw, bdw, lnw, lnb, a.y, eps);
+  }
+};
+
+// The pairs with a merged kernel, group 0 the wider map: stages 1 - 3 of ConvNeXt-T's 224- + 112-pixel pass.
+//   Roll<192,4> + Roll<192,2>,  Roll<384,2> + Roll<384,1>,  Roll<768,1> + Tiny<768,3>
+// Stage 0, (Mfma<96,8> | Roll<96,8>) + Roll<96,4>, keeps two launches: all three kernels sit at the 128 registers of a
+// 16-wave workgroup (Roll<96,4> with one dword of scratch, isa_report.py), and either merged kernel came out with a
+// second spilled register, the thread index carried across the tap waves' loop for the staging waves.
+// Tiny at S = 3 only: a two-segment pass is the VAE's, whose maps are 7 and 7 / 2 = 3 pixels at stage 3, and no other
+// resolution that cnx_res_ok accepts puts a 7-pixel map beside a 1-, 2- or 4-pixel one.  Everything else (Tile, Pair,
+// TinyPair, unaligned operands, ConvNeXt-L, groups in the other order) keeps two launches as well.
+template <class S0, class S1> constexpr bool dw_two_roll_pair() {
+  return S0::kind == DwKind::Roll && S1::kind == DwKind::Roll && S0::C == S1::C && S0::N == 2 * S1::N &&
+         S0::N * S0::C == 768 && S0::C != 96;
+}
+template <class S0> constexpr bool dw_two_tiny_pair() { return S0::kind == DwKind::Roll && S0::C == 768 && S0::N == 1; }
+constexpr int kDwTwoTinyS = 3;
+
+template <typename T, class S0, class S1>
+__global__ void __launch_bounds__((DwBody<T, S0>::NT > DwBody<T, S1>::NT ? DwBody<T, S0>::NT : DwBody<T, S1>::NT), 4)
+dwconv7_ln_two_kernel(const DwGroupArgs<T> a0, const DwGroupArgs<T> a1, const int grid0, const float* __restrict__ wdw,
+                      const float* __restrict__ bdw, const float* __restrict__ lnw, const float* __restrict__ lnb, float eps) {
+  typedef DwBody<T, S0> B0;
+  typedef DwBody<T, S1> B1;
+  constexpr int NT = B0::NT > B1::NT ? B0::NT : B1::NT;
+  static_assert(B0::NT % 64 == 0 && B1::NT % 64 == 0, "whole waves leave");
+  extern __shared__ __attribute__((aligned(16))) unsigned char dw2_lds[];
+  const int bx = blockIdx.x;
+  // Whole waves leave (the test is on the wave's first lane: a scalar branch), and group 1's workgroups end their program
+  // behind its body: were the two bodies to meet in a common exit block, the thread index would stay live across both
+  // and cost each a spilled register.
+  const int t0 = __builtin_amdgcn_readfirstlane((int)threadIdx.x);
+  if (bx >= grid0) {
+    if (B1::NT == NT || t0 < B1::NT) B1::run(dw2_lds, bx - grid0, (int)gridDim.x - grid0, a1, wdw, bdw, lnw, lnb, eps);
+    __builtin_amdgcn_endpgm();
+  }
+  if (B0::NT == NT || t0 < B0::NT) B0::run(dw2_lds, bx, grid0, a0, wdw, bdw, lnw, lnb, eps);
+}
+
+// f(p0, S0, p1, S1) for a pair the table covers, otherwise g()
+template <class S0, class S1, class F, class G> int dw_two_dispatch(const DwPlan& p0, const DwPlan& p1, F& f, G& g) {
+  if constexpr (dw_two_roll_pair<S0, S1>()) {
+    return f(p0, S0{}, p1, S1{});
+  } else if constexpr (dw_two_tiny_pair<S0>() && S1::kind == DwKind::Tiny) {
+    return p1.n == kDwTwoTinyS ? f(p0, S0{}, p1, DwShape<DwKind::Tiny, 768, kDwTwoTinyS>{}) : g();
+  } else {
+    return g();
+  }
+}
+
+// plans both groups (x / y 16-byte `aligned` or not, per group) and calls f or g as dw_two_dispatch
+template <typename T, class F, class G>
+int dw_select2(int nimg0, int H0, int W0, bool al0, int nimg1, int H1, int W1, bool al1, int C, F&& f, G&& g) {
+  return dw_select<T>(nimg0, H0, W0, C, al0, [&](const DwPlan& p0, auto sh0) -> int {
+    return dw_select<T>(nimg1, H1, W1, C, al1, [&](const DwPlan& p1, auto sh1) -> int {
+      return dw_two_dispatch<decltype(sh0), decltype(sh1)>(p0, p1, f, g);
+    });
+  });
+}
+
+template <typename T> bool dw_two_merged(int nimg0, int H0, int W0, int nimg1, int H1, int W1, int C, bool aligned) {
+  return dw_select2<T>(nimg0, H0, W0, aligned, nimg1, H1, W1, aligned, C,
+                       [](const DwPlan&, auto, const DwPlan&, auto) { return 1; }, [] { return 0; }) == 1;
+}
+
+template <typename T>
+int launch_dwconv7_ln2(const T* x0, T* y0, int nimg0, int H0, int W0, const T* x1, T* y1, int nimg1, int H1, int W1,
+                       const float* wdw, const float* bdw, const float* lnw, const float* lnb, int C, float eps,
+                       hipStream_t s) {
+  auto al = [](const T* x, const T* y) { return ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15u) == 0; };
+  return dw_select2<T>(
+      nimg0, H0, W0, al(x0, y0), nimg1, H1, W1, al(x1, y1), C,
+      [&](const DwPlan& p0, auto sh0, const DwPlan& p1, auto sh1) -> int {
+        typedef DwBody<T, decltype(sh0)> B0;
+        typedef DwBody<T, decltype(sh1)> B1;
+        DwPlan p = p0;
+        p.grid = p0.grid + p1.grid;
+        p.block = std::max(B0::NT, B1::NT);
+        p.lds = std::max(B0::lds, B1::lds);
+        const DwGroupArgs<T> a0{x0, y0, H0, p0.band_rows, p0.band_rows ? cdiv(H0, p0.band_rows) : 0};
+        const DwGroupArgs<T> a1{x1, y1, H1, p1.band_rows, p1.band_rows ? cdiv(H1, p1.band_rows) : 0};
+        return dw_launch(p, dwconv7_ln_two_kernel<T, decltype(sh0), decltype(sh1)>, s, a0, a1, p0.grid, wdw, bdw, lnw, lnb,
+                         eps);
+      },
+      [&]() -> int {
+        GCV_TRY(launch_dwconv7_ln<T>(x0, wdw, bdw, lnw, lnb, y0, nimg0, H0, W0, C, eps, s));
+        return launch_dwconv7_ln<T>(x1, wdw, bdw, lnw, lnb, y1, nimg1, H1, W1, C, eps, s);
+      });
+}
+
 #define GCV_INSTANTIATE_DW(T)                                                                                        \
   template int dw_plan<T>(DwPlan&, int, int, int, int, bool);                                                        \
   template int launch_dwconv7_ln<T>(const T*, const float*, const float*, const float*, const float*, T*, int, int,   \
-                                    int, int, float, hipStream_t);
+                                    int, int, float, hipStream_t);                                                   \
+  template bool dw_two_merged<T>(int, int, int, int, int, int, int, bool);                                           \
+  template int launch_dwconv7_ln2<T>(const T*, T*, int, int, int, const T*, T*, int, int, int, const float*,         \
+                                     const float*, const float*, const float*, int, float, hipStream_t);
 
 }  // namespace gcv

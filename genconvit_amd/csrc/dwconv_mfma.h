@@ -77,23 +77,24 @@ template <> struct Mfma4<bf16_t> {
   }
 };
 
+// the body as a device function, as dwconv7_ln_roll_body; every one of the workgroup's NT threads must enter it
 template <typename T, int C, int NS>
-__global__ void __launch_bounds__((DwMfmaLds<T, C, NS>::NT), 4)
-dwconv7_ln_mfma_kernel(const T* __restrict__ x, const float* __restrict__ wdw /*[49][C]*/,
-                       const float* __restrict__ bdw, const float* __restrict__ lnw, const float* __restrict__ lnb,
-                       T* __restrict__ y, int H, int band_rows, int nbands, float eps) {
+__device__ __forceinline__ void
+dwconv7_ln_mfma_body(unsigned char* const dwm_lds, const int bid, const int nwg, const T* __restrict__ x,
+                     const float* __restrict__ wdw /*[49][C]*/, const float* __restrict__ bdw,
+                     const float* __restrict__ lnw, const float* __restrict__ lnb, T* __restrict__ y, int H,
+                     int band_rows, int nbands, float eps) {
   static_assert(sizeof(T) == 2, "16-bit storage (fp32 storage: dwconv_roll.h)");
   typedef DwElem<T> EL;
   typedef DwMfmaLds<T, C, NS> LY;
   constexpr int NCONV = LY::NCONV, NLN = LY::NLN;
   constexpr int W = LY::W, P = W, NXG = LY::NXG, TPW = LY::TPW, PITCH = LY::PITCH, SLOT = LY::SLOT, SP = LY::SP;
   constexpr int EPC = EL::EPC;
-  extern __shared__ __attribute__((aligned(16))) unsigned char dwm_lds[];
   unsigned char* const in_ring = dwm_lds;
   float* const sval_ring = reinterpret_cast<float*>(dwm_lds + LY::IN_BYTES);
 
   const int tid = threadIdx.x;
-  const int wg = xcd_remap(blockIdx.x, gridDim.x);
+  const int wg = xcd_remap(bid, nwg);
   const int band = wg % nbands, img = wg / nbands;
   const int ob = band * band_rows;
   const int nrows = min(band_rows, H - ob);
@@ -348,6 +349,15 @@ dwconv7_ln_mfma_kernel(const T* __restrict__ x, const float* __restrict__ wdw /*
     }
     ln_row(ob + nit - 7, (nit - 1) & 1);
   }
+}
+
+template <typename T, int C, int NS>
+__global__ void __launch_bounds__((DwMfmaLds<T, C, NS>::NT), 4)
+dwconv7_ln_mfma_kernel(const T* __restrict__ x, const float* __restrict__ wdw /*[49][C]*/,
+                       const float* __restrict__ bdw, const float* __restrict__ lnw, const float* __restrict__ lnb,
+                       T* __restrict__ y, int H, int band_rows, int nbands, float eps) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char dwm_lds[];
+  dwconv7_ln_mfma_body<T, C, NS>(dwm_lds, blockIdx.x, gridDim.x, x, wdw, bdw, lnw, lnb, y, H, band_rows, nbands, eps);
 }
 
 }  // namespace gcv

@@ -105,11 +105,14 @@ template <typename T, int C, int NS> struct DwRollLds {
 // grid: nimg * nbands workgroups of (NS * C) * 4 / 3 threads, NS = W / 7; workgroup = (image, band of `band_rows`
 // output rows).  Waves are specialised: threads [0, NS * C) run the taps, the last third stages input rows and does
 // LayerNorm + the stores of the row the tap waves finished one step earlier; the two meet at one barrier per row.
+// The body is a device function of (workgroup index bid of nwg, dynamic LDS base): dwconv7_ln_roll_kernel below runs it
+// over its own grid, dwconv7_ln_two_kernel (dwconv_impl.h) over one half of a grid shared by two image groups.
 template <typename T, int C, int NS>
-__global__ void __launch_bounds__((DwRollLds<T, C, NS>::NT), 4)
-dwconv7_ln_roll_kernel(const T* __restrict__ x, const float* __restrict__ wdw /*[49][C]*/,
-                       const float* __restrict__ bdw, const float* __restrict__ lnw, const float* __restrict__ lnb,
-                       T* __restrict__ y, int H, int band_rows, int nbands, float eps) {
+__device__ __forceinline__ void
+dwconv7_ln_roll_body(unsigned char* const dwr_lds, const int bid, const int nwg, const T* __restrict__ x,
+                     const float* __restrict__ wdw /*[49][C]*/, const float* __restrict__ bdw,
+                     const float* __restrict__ lnw, const float* __restrict__ lnb, T* __restrict__ y, int H,
+                     int band_rows, int nbands, float eps) {
   typedef DwElem<T> EL;
   typedef DwRollLds<T, C, NS> LY;
   constexpr bool FULLW = (NS == 1);
@@ -118,12 +121,11 @@ dwconv7_ln_roll_kernel(const T* __restrict__ x, const float* __restrict__ wdw /*
   constexpr int P = LY::P, HP = LY::HP, IN_ROW = LY::IN_ROW;
   constexpr int EPC = EL::EPC;
   constexpr int S0 = FULLW ? 3 : 0, S1 = FULLW ? 10 : 13;   // halo columns that can hold data
-  extern __shared__ __attribute__((aligned(16))) unsigned char dwr_lds[];
   float* const in_ring = reinterpret_cast<float*>(dwr_lds);
   float* const sval_ring = reinterpret_cast<float*>(dwr_lds + LY::IN_BYTES);
 
   const int tid = threadIdx.x;
-  const int wg = xcd_remap(blockIdx.x, gridDim.x);    // an XCD walks neighbouring bands / images: apron rows hit its L2
+  const int wg = xcd_remap(bid, nwg);                 // an XCD walks neighbouring bands / images: apron rows hit its L2
   const int band = wg % nbands, img = wg / nbands;
   const int ob = band * band_rows;
   const int nrows = min(band_rows, H - ob);
@@ -402,6 +404,15 @@ dwconv7_ln_roll_kernel(const T* __restrict__ x, const float* __restrict__ wdw /*
     }
     if (!(GCV_DWR_ABLATE & 2)) ln_row(ob + nit - 7, (nit - 1) & 1);
   }
+}
+
+template <typename T, int C, int NS>
+__global__ void __launch_bounds__((DwRollLds<T, C, NS>::NT), 4)
+dwconv7_ln_roll_kernel(const T* __restrict__ x, const float* __restrict__ wdw /*[49][C]*/,
+                       const float* __restrict__ bdw, const float* __restrict__ lnw, const float* __restrict__ lnb,
+                       T* __restrict__ y, int H, int band_rows, int nbands, float eps) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char dwr_lds[];
+  dwconv7_ln_roll_body<T, C, NS>(dwr_lds, blockIdx.x, gridDim.x, x, wdw, bdw, lnw, lnb, y, H, band_rows, nbands, eps);
 }
 
 }  // namespace gcv

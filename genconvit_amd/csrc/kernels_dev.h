@@ -413,15 +413,17 @@ dwconv7_ln_kernel(const T* __restrict__ x, const float* __restrict__ wdw /*[49][
 // (2S-1)^2 of the 49 that can reach a pixel.  One workgroup per image, one thread per channel, inputs, outputs and taps in
 // registers, LayerNorm statistics (two passes) through per-wave partial sums.  The generic tile kernel walked a 13 x 13
 // masked halo window for these nine pixels: 28 us per launch at 128 images, against 3 here.
+// The body is a device function of the image index: dwconv7_ln_tiny_kernel below runs it over its own grid,
+// dwconv7_ln_two_kernel (dwconv_impl.h) behind the bands of the 224-pixel pass in one grid.  Threads [0, C) enter it.
 template <typename T, int C, int S>
-__global__ void __launch_bounds__(C) dwconv7_ln_tiny_kernel(const T* __restrict__ x, const float* __restrict__ wdw /*[49][C]*/,
-                                                            const float* __restrict__ bdw, const float* __restrict__ lnw,
-                                                            const float* __restrict__ lnb, T* __restrict__ y, float eps) {
+__device__ __forceinline__ void dwconv7_ln_tiny_body(const int img, const T* __restrict__ x, const float* __restrict__ wdw /*[49][C]*/,
+                                                     const float* __restrict__ bdw, const float* __restrict__ lnw,
+                                                     const float* __restrict__ lnb, T* __restrict__ y, float eps) {
   static_assert(S >= 1 && S <= 4 && C % 64 == 0, "tiny maps");
   constexpr int NPX = S * S, NW = C / 64;
   __shared__ float part[2][NW][NPX];
   const int c = threadIdx.x, wave = c >> 6, lane = c & 63;
-  const T* xb = x + (int64_t)blockIdx.x * NPX * C + c;
+  const T* xb = x + (int64_t)img * NPX * C + c;
   float xin[NPX], acc[NPX];
 #pragma unroll
   for (int p = 0; p < NPX; ++p) xin[p] = to_f(xb[p * C]);
@@ -460,7 +462,7 @@ __global__ void __launch_bounds__(C) dwconv7_ln_tiny_kernel(const T* __restrict_
   }
   __syncthreads();
   const float lw = lnw[c], lb = lnb[c];
-  T* yb = y + (int64_t)blockIdx.x * NPX * C + c;
+  T* yb = y + (int64_t)img * NPX * C + c;
 #pragma unroll
   for (int p = 0; p < NPX; ++p) {
     float t = 0.0f;
@@ -469,6 +471,13 @@ __global__ void __launch_bounds__(C) dwconv7_ln_tiny_kernel(const T* __restrict_
     rstd[p] = rsqrtf(t * (1.0f / C) + eps);
     yb[p * C] = from_f<T>((acc[p] - mean[p]) * rstd[p] * lw + lb);
   }
+}
+
+template <typename T, int C, int S>
+__global__ void __launch_bounds__(C) dwconv7_ln_tiny_kernel(const T* __restrict__ x, const float* __restrict__ wdw /*[49][C]*/,
+                                                            const float* __restrict__ bdw, const float* __restrict__ lnw,
+                                                            const float* __restrict__ lnb, T* __restrict__ y, float eps) {
+  dwconv7_ln_tiny_body<T, C, S>(blockIdx.x, x, wdw, bdw, lnw, lnb, y, eps);
 }
 
 // ------------------------------------------------------------------ K6: LN2d + space-to-depth

@@ -738,17 +738,37 @@ template <typename T> struct NetImpl : NetBase {
           for (int s = 0; s < nseg; ++s) segs[s].in3->x[j] = Xc + moff[s] * C;
           Xn = X3[j + 1];
         }
-        for (int s = 0; s < nseg;) {
-          // neighbouring segments of one geometry (ED: reconstruction + original pass) are contiguous in the token
-          // buffer: one launch over all their images (256 images fill the 256 CUs with whole-image row bands)
-          int e = s + 1, nimg = segs[s].n;
-          int64_t mm = m[s];
-          while (e < nseg && h[e] == h[s] && wd[e] == wd[s]) { nimg += segs[e].n; mm += m[e]; ++e; }
-          GCV_TRY(run("cnx.dwconv7_ln", 2.0 * 49 * mm * C, 2.0 * sizeof(T) * (double)mm * C + 49.0 * C * 4, [&] {
-            return launch_dwconv7_ln<T>(Xc + moff[s] * C, k.dw_w, k.dw_b, k.ln_w, k.ln_b, Y + moff[s] * C, nimg, h[s],
-                                        wd[s], C, 1e-6f, cur);
-          }));
+        // neighbouring segments of one geometry (ED: reconstruction + original pass) are contiguous in the token
+        // buffer: one launch over all their images (256 images fill the 256 CUs with whole-image row bands)
+        int gs[4], gn[4], ng = 0;                        // geometry groups: first segment, images, tokens
+        int64_t gm[4];
+        for (int s = 0; s < nseg; ++ng) {
+          GCV_REQUIRE(ng < 4, "at most four segments");
+          int e = s + 1;
+          gs[ng] = s; gn[ng] = segs[s].n; gm[ng] = m[s];
+          while (e < nseg && h[e] == h[s] && wd[e] == wd[s]) { gn[ng] += segs[e].n; gm[ng] += m[e]; ++e; }
           s = e;
+        }
+        auto dw_bytes = [&](int q) { return 2.0 * sizeof(T) * (double)gm[q] * C + 49.0 * C * 4; };
+        const T* gx[2] = {Xc + moff[gs[0]] * C, Xc + moff[gs[ng - 1]] * C};
+        T* gy[2] = {Y + moff[gs[0]] * C, Y + moff[gs[ng - 1]] * C};
+        // two groups (VAE: the 224- and the 112-pixel segment) whose kernels have a merged form share one grid: the small
+        // group's workgroups follow the large one's without a launch boundary (dwconv_impl.h, launch_dwconv7_ln2)
+        const bool al2 = ((reinterpret_cast<uintptr_t>(gx[0]) | reinterpret_cast<uintptr_t>(gx[1]) |
+                           reinterpret_cast<uintptr_t>(gy[0]) | reinterpret_cast<uintptr_t>(gy[1])) & 15u) == 0;
+        if (ng == 2 && dw_two_merged<T>(gn[0], h[gs[0]], wd[gs[0]], gn[1], h[gs[1]], wd[gs[1]], C, al2)) {
+          GCV_TRY(run("cnx.dwconv7_ln", 2.0 * 49 * (gm[0] + gm[1]) * C, dw_bytes(0) + dw_bytes(1), [&] {
+            return launch_dwconv7_ln2<T>(gx[0], gy[0], gn[0], h[gs[0]], wd[gs[0]], gx[1], gy[1], gn[1], h[gs[1]], wd[gs[1]],
+                                         k.dw_w, k.dw_b, k.ln_w, k.ln_b, C, 1e-6f, cur);
+          }));
+        } else {
+          for (int q = 0; q < ng; ++q) {
+            const int s = gs[q];
+            GCV_TRY(run("cnx.dwconv7_ln", 2.0 * 49 * gm[q] * C, dw_bytes(q), [&] {
+              return launch_dwconv7_ln<T>(Xc + moff[s] * C, k.dw_w, k.dw_b, k.ln_w, k.ln_b, Y + moff[s] * C, gn[q], h[s],
+                                          wd[s], C, 1e-6f, cur);
+            }));
+          }
         }
         // the last block of stages 0..2 may apply the stage boundary's LayerNorm2d + space-to-depth in its epilogue and write
         // the down-sampling GEMM's operand (into Hd: Y is still being read as x_ln); the residual stream then ends there

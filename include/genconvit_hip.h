@@ -605,6 +605,13 @@ int gcv_k_stem_ln_c(int dtype, const void* x, int64_t sb, int64_t sc, int64_t sy
                     float eps, gcv_stream s);
 int gcv_k_dwconv7_ln(int dtype, const void* x, const float* wdw, const float* bdw, const float* lnw,
                      const float* lnb, void* y, int nimg, int H, int W, int C, float eps, gcv_stream s);
+/* The same on two image groups of one C, (x0, y0): nimg0 maps of H0 x W0 and (x1, y1): nimg1 maps of H1 x W1, in ONE launch
+ * where the two kernels gcv_dw_plan names for them have a merged form (group 0 the wider map: mfma or roll 96x56 + roll
+ * 96x28, roll 192x28 + 192x14, roll 384x14 + 384x7, roll 768x7 + tiny 768x3x3; the VAE's 224- + 112-pixel pass), in two
+ * launches otherwise.  Each group keeps its gcv_dw_plan; the outputs are bit for bit those of two gcv_k_dwconv7_ln calls. */
+int gcv_k_dwconv7_ln2(int dtype, const void* x0, void* y0, int nimg0, int H0, int W0, const void* x1, void* y1,
+                      int nimg1, int H1, int W1, const float* wdw, const float* bdw, const float* lnw, const float* lnb,
+                      int C, float eps, gcv_stream s);
 /* Test query: the kernel and grid that gcv_k_dwconv7_ln picks for nimg H x W x C images, x and y 16-byte aligned or not.
  * out5 = {kind (0 tile, 1 tiny, 2 tiny-pair, 3 roll, 4 mfma, 5 pair), workgroups, threads per workgroup, dynamic LDS bytes,
  * rows per band (roll, mfma, pair; else 0)}; or the launcher's error.  No HIP call: works without a GPU. */
