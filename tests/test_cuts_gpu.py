@@ -77,12 +77,13 @@ def test_noise_and_an_odd_base_pointer(regions):
 
 def test_many_frames_take_the_unsplit_path_at_every_size():
     """70 frames of 37 x 53 at R = 4 are 1 120 regions: one workgroup each, plain stores, regions of 9-10 rows"""
-    frames = _cached("many", lambda: cu.noise_video(F=70, seed=12))
+    frames = _cached("many", cu.many_video)
+    assert cu.hist_slices(70, 37, 4) == 1
     _assert_same(frames, torch.as_tensor(frames).cuda(), 4)
 
 
 def test_one_pixel_per_region():
-    frames = _cached("tiny", lambda: cu.noise_video(F=2, H=8, W=8, seed=13))
+    frames = _cached("tiny", cu.tiny_video)
     hist, dist = _assert_same(frames, torch.as_tensor(frames).cuda(), 8)
     assert int(hist.max()) == 1 and set(dist.flatten().tolist()) <= {0, 2}
 
@@ -98,6 +99,17 @@ def test_flat_frames_fill_one_bin(regions):
     assert dist.tolist() == [(2 * n).tolist()]
     if regions == 1:
         assert int(hist.max()) == 67600 and dist.tolist() == [[135200]]
+
+
+@pytest.mark.parametrize("regions", [1, 2])
+def test_the_first_and_the_last_bin(regions):
+    """2 x 16 x 24, white, then black with every third column white: bins 0 and 63 hold everything (noise almost never
+    reaches Y >= 252), and bin 63 is the last lane of hist_diff's wave"""
+    frames, dev = _video("ends_pair")
+    hist, dist = _assert_same(frames, dev, regions)
+    n = cu.region_pixels(16, 24, regions)
+    assert hist[0, :, 63].tolist() == n.tolist() and hist[1, :, 63].tolist() == (n // 3).tolist()
+    assert hist[1, :, 0].tolist() == (n - n // 3).tolist() and dist.tolist() == [(2 * (n - n // 3)).tolist()]
 
 
 @pytest.mark.parametrize("regions", [1, 2])

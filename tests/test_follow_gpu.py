@@ -44,8 +44,10 @@ def test_track_match_path_case():
 @pytest.mark.parametrize("radius", [0, 1, 5, 8])
 @pytest.mark.parametrize("grid", [16, 32])
 def test_track_match_random_jobs(grid, radius):
-    """3 x 120 x 160 frames, two of noise and a smooth one (cost ties); 48 jobs with sides that are no multiple of the grid,
-    three different sizes per job, weights with wa = 0 and wb = 0, priors on all four borders"""
+    """3 x 120 x 160 frames, two of noise and a smooth one; 48 jobs with sides that are no multiple of the grid, three
+    different sizes per job, weights with wa = 0 and wb = 0, priors on all four borders.  No two candidates of a job share
+    its smallest cost (tests/test_follow_sensitivity_cpu.py asserts it): the key's tie-break is decided by the tie cases
+    below, not here."""
     frames, jobs = _cached(("fuzz", grid), lambda: fu.fuzz_case(lo=grid))
     sides = [(j[c + 3] - j[c + 1], j[c + 2] - j[c + 4]) for j in jobs for c in (0, 5, 11)]
     assert all(grid <= s <= 100 and s % 16 for hw in sides for s in hw)
@@ -60,8 +62,37 @@ def test_track_match_random_jobs(grid, radius):
 @pytest.mark.parametrize("radius", [32, 16])
 def test_track_match_largest_configuration(radius):
     """grid 64 with radius 32: the largest LDS footprint and the most candidates; 3 x 256 x 256 frames, boxes of 64 ... 120"""
-    frames, jobs = _cached("large", lambda: fu.fuzz_case(H=256, W=256, n=12, lo=64, hi=120, seed=23))
+    frames, jobs = _cached("large", fu.largest_case)
     _assert_same(frames, jobs, 64, radius)
+
+
+@pytest.mark.parametrize("grid,k,radius", fu.TIE_CASES)
+def test_track_match_ties_are_broken_by_d2_then_dy_then_dx(grid, k, radius):
+    """two identical frames that are constant along the anti-diagonals: job A costs 0 on all of dy + dx = +1, job B on all of
+    dy + dx = -2, and the rows are what d2, then dy, then dx pick — at radius 8 among 289 candidates, so the equal costs sit
+    in different waves and in both trips of the candidate loop"""
+    frames, jobs = _cached(("tie", grid, k), lambda: fu.tie_case(grid, k))
+    got = _assert_same(frames, jobs, grid, radius).cpu()
+    assert got.tolist() == fu.TIE_ROWS[(grid, k, radius)]
+
+
+@pytest.mark.parametrize("up,left", [(8, 7), (6, 6)])
+@pytest.mark.parametrize("grid,k", [(16, 3), (32, 2)])
+def test_track_match_best_in_the_second_trip_and_the_fourth_wave(grid, k, up, left):
+    """the tie frames with the prior far off, radius 8: (8, 7) leaves cost 0 to candidates 271 and 287 alone, both in the
+    second trip of the 256-lane loop; (6, 6) gives the row to candidate 252, in the fourth wave"""
+    frames, jobs = _cached(("far tie", grid, k, up, left), lambda: fu.far_tie_case(grid, k, up, left))
+    got = _assert_same(frames, jobs, grid, 8).cpu()
+    want = [7 * k, 8 * k, 0] if (up, left) == (8, 7) else [6 * k, 6 * k, 0]
+    assert got[0, :3].tolist() == want
+
+
+def test_track_match_at_the_cost_bound():
+    """grid 64, black templates on a white window, wa + wb = 1024: cost = 1024 * 4096 * 255 = 1 069 547 520, the kernel's
+    stated bound; every candidate costs that, so the answer is (0, 0)"""
+    frames, jobs, grid, radius = _cached("bound", fu.bound_case)
+    got = _assert_same(frames, jobs, grid, radius).cpu()
+    assert got.tolist() == [[0, 0, fu.COST_BOUND, fu.COST_BOUND]] * 3 and fu.COST_BOUND == 1069547520
 
 
 def test_track_match_refusals_and_no_jobs():

@@ -8,7 +8,6 @@ import torch
 from genconvit_amd import _lib
 from genconvit_amd.model import pred_func
 from genconvit_amd.model.genconvit import GenConViT
-from tests import followutil as fu
 from tests import qualityutil as qu
 
 pytestmark = pytest.mark.gpu
@@ -37,14 +36,8 @@ def _assert_same(frames, boxes, grid, dev=None):
 
 
 def _fuzz(grid):
-    """followutil's 3 x 120 x 160 frames (two of noise, a smooth one) and the 48 prior boxes of its jobs: sides from the grid
-    to 100 that are no multiple of 16, touching each of the four borders"""
-    frames, jobs = _cached(("fuzz", grid), lambda: fu.fuzz_case(lo=grid))
-    return frames, [tuple(j[:5]) for j in jobs]
-
-
-def _corners(f, H, W, h, w):
-    return [(f, 0, w, h, 0), (f, 0, W, h, W - w), (f, H - h, w, H, 0), (f, H - h, W, H, W - w)]
+    """qualityutil.fuzz_boxes, made once per grid"""
+    return _cached(("fuzz", grid), lambda: qu.fuzz_boxes(grid))
 
 
 @pytest.mark.parametrize("grid", [16, 32])
@@ -60,17 +53,12 @@ def test_face_quality_random_boxes(grid):
 def test_face_quality_edge_boxes(grid):
     """boxes one pixel over the grid in one direction, the whole frame, and a box in each corner of the frame"""
     frames, _ = _fuzz(16)
-    boxes = [(0, 7, 11 + grid + 1, 7 + grid, 11), (1, 7, 11 + grid, 7 + grid + 1, 11), (2, 3, 5 + grid, 3 + grid, 5),
-             (0, 0, 160, 120, 0), (2, 0, 160, 120, 0)]
-    boxes += _corners(1, 120, 160, grid + 5, grid + 21) + _corners(2, 120, 160, 67, 71)
-    _assert_same(frames, boxes, grid)
+    _assert_same(frames, qu.edge_boxes(grid), grid)
 
 
 @pytest.mark.parametrize("grid", [16, 32, 64])
 def test_face_quality_flat_black_and_white_frames(grid):
-    frames = np.stack([qu.flat(70, 90, 0), qu.flat(70, 90, 0), qu.flat(70, 90, 255)])
-    frames[0] = (10, 200, 30)                                                              # Y = 124
-    boxes = [(f, 0, 90, 70, 0) for f in range(3)] + [(f, 2, 88, 69, 1) for f in range(3)]
+    frames, boxes = qu.flat_case()                                                         # Y = 124, black, white
     got = _assert_same(frames, boxes, grid)
     n = grid * grid
     assert got[:3].tolist() == [[grid, n * 124, n * 124 * 124, 0, 0, 0, 0, 0], [grid, 0, 0, 0, 0, 0, n, 0],
@@ -79,20 +67,30 @@ def test_face_quality_flat_black_and_white_frames(grid):
 
 def test_face_quality_on_an_unaligned_slice():
     """frames of 37 x 53 taken as frames[1:]: the base pointer is 5 883 bytes into the allocation"""
-    frames = np.random.default_rng(31).integers(0, 256, (4, 37, 53, 3), dtype=np.uint8)
+    frames, boxes = qu.unaligned_case()
     dev = torch.as_tensor(frames).cuda()[1:]
     assert dev.data_ptr() % 2 == 1 and dev.is_contiguous()
-    boxes = [(f, 0, 53, 37, 0) for f in range(3)] + _corners(0, 37, 53, 16, 17) + _corners(2, 37, 53, 21, 16) + \
-        [(1, 9, 40, 30, 12)]
     _assert_same(frames[1:], boxes, 16, dev=dev)
 
 
 def test_face_quality_largest_configuration():
     """grid 64, every lane 16 cells; 2 frames of 300 x 400 with the whole frame as a box: the most pixels a cell holds here"""
-    frames = np.random.default_rng(32).integers(0, 256, (2, 300, 400, 3), dtype=np.uint8)
-    frames[1] = qu.box_blur(qu.texture(300, 400, seed=6), 3, 3)
-    boxes = [(0, 0, 400, 300, 0), (1, 0, 400, 300, 0), (1, 13, 399, 300, 101), (0, 100, 164, 164, 100)]
+    frames, boxes = qu.largest_case()
     _assert_same(frames, boxes, 64)
+
+
+@pytest.mark.parametrize("grid", [16, 32, 64])
+def test_face_quality_checkerboard_reaches_the_largest_sums(grid):
+    """squares of 2 x 2 pixels that alternate between 0 and 255, the whole frame as the box: every interior Laplacian is
+    +-1020.  At grid 64 a lane's 16 cells add 16 * 1020^2, a wave 16 * 62 * 1020^2 (both just inside the 24 and 31 bits the
+    kernel counts on), and L2 = 3 999 297 600 is more than a signed 32-bit total holds."""
+    frames, boxes = qu.checkerboard(grid, 2)
+    got = _assert_same(frames, boxes, grid)
+    n = grid * grid
+    assert got.tolist() == [[grid, n // 2 * 255, n // 2 * 255 ** 2, (grid - 2) ** 2 * 1020 ** 2, grid * (grid - 1) * 255 ** 2,
+                             grid * (grid - 1) * 255 ** 2, n // 2, n // 2]]
+    if grid == 64:
+        assert got.tolist() == [qu.CHECKERBOARD_64] and qu.CHECKERBOARD_64[3] == 3999297600 > 2 ** 31
 
 
 def test_face_quality_guard_and_refusals_through_the_c_entry():

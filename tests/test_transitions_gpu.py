@@ -1,7 +1,6 @@
 """``gcv_frame_cells``, ``gcv_blend_fit`` and ``gcv_hist_diff_lag`` on the MI355X, bit for bit against their CPU restatement
 (tests/transutil.py: ``torch.equal``, no tolerance — the arithmetic is integer), their refusals, and
 ``pred_func.shot_transitions`` / ``scan_frames(transitions=True)`` end to end with synthetic weights."""
-import numpy as np
 import pytest
 import torch
 
@@ -70,21 +69,22 @@ def test_noise_and_an_odd_base_pointer(grid):
 
 
 def test_one_pixel_per_cell():
-    frames, dev = _video("tiny", lambda: cu.noise_video(F=2, H=32, W=32, seed=13))
+    frames, dev = _video("tiny", tu.tiny_video)
     cells = _assert_cells(frames, dev, 32)
     assert torch.equal(cells.cpu().long(), torch.as_tensor(cu.luma(frames)).reshape(2, -1))
 
 
 def test_many_frames_take_the_unsplit_path():
     """70 frames of 37 x 53 at G = 16 are 1 120 rows of cells: one workgroup each, plain stores, rows of 2-3 pixel rows"""
-    frames, dev = _video("many", lambda: cu.noise_video(F=70, seed=12))
+    frames, dev = _video("many", cu.many_video)
+    assert tu.cells_slices(70, 37, 16) == 1
     _assert_cells(frames, dev, 16)
 
 
 @pytest.mark.parametrize("grid", [8, 32])
 def test_rows_wider_than_a_workgroup(grid):
     """1 x 37 x 1103: 276 groups a row, more than the 256 threads — a thread's next group is in the same pixel row"""
-    frames, dev = _video("wide", lambda: cu.noise_video(F=1, H=37, W=1103, seed=14))
+    frames, dev = _video("wide", tu.wide_video)
     _assert_cells(frames, dev, grid)
 
 
@@ -92,10 +92,11 @@ def test_tall_frames_take_the_split_path():
     """few frames of many rows: a row of cells is split over several workgroups, merged by atomic adds into a zeroed
     output.  1 x 512 x 512 flat 255 at G = 8 (8 slices of 8 pixel rows): every cell is exactly 255 * 4096; 2 x 161 x 53
     noise at G = 8 (2 slices of the 20-21 rows, 10 and 10-11)."""
-    flat = _cached("flat", lambda: np.full((1, 512, 512, 3), 255, dtype=np.uint8))
+    flat = _cached("flat", tu.flat_video)
+    assert tu.cells_slices(1, 512, 8) == 8 and tu.cells_slices(2, 161, 8) == tu.cells_slices(1, 161, 8) == 2
     cells = _assert_cells(flat, torch.as_tensor(flat).cuda(), 8)
     assert bool((cells == 255 * 4096).all())
-    frames, dev = _video("tall", lambda: cu.noise_video(F=2, H=161, W=53, seed=15))
+    frames, dev = _video("tall", tu.tall_video)
     _assert_cells(frames, dev, 8)
     _assert_cells(frames[1:], dev[1:], 8)
 
@@ -120,6 +121,15 @@ def test_fits_of_the_transition_video(grid):
     cells = _cells_ref("transition_video", frames, grid).numpy()
     for lag in (2, 4, 8, 32):
         _assert_fit(cells, lag)
+
+
+@pytest.mark.parametrize("grid", [16, 32])
+def test_fits_beyond_float64_across_waves_and_cells_of_a_thread(grid):
+    """the sums near 2^63 at G = 16 (four waves, summed in 64 bits through LDS) and G = 32 (four cells a thread as well)"""
+    cells = tu.extreme_cells(grid)
+    for lag in (2, 3, 5):
+        fit = _assert_fit(cells, lag)
+        assert int(fit.max()) > 2 ** 62 and tuple(fit.shape) == (6 - lag, 2 * lag - 1)
 
 
 def test_fits_beyond_float64_and_the_shortest_inputs():
@@ -221,7 +231,7 @@ def test_refusals_and_a_valid_call_after_them():
     buf = torch.full((6, 64), -7, dtype=torch.int32, device="cuda")
     assert _lib.frame_cells(dev, 8, out=buf[1:5]).data_ptr() == buf[1:5].data_ptr()
     assert torch.equal(buf[1:5].cpu().long(), want) and bool((buf[0] == -7).all()) and bool((buf[5] == -7).all())
-    tall, tall_dev = _video("tall", lambda: cu.noise_video(F=2, H=161, W=53, seed=15))
+    tall, tall_dev = _video("tall", tu.tall_video)
     buf.fill_(-7)
     _lib.frame_cells(tall_dev, 8, out=buf[2:4])
     assert torch.equal(buf[2:4].cpu().long(), torch.as_tensor(tu.frame_cells_ref(tall, 8)))

@@ -1,7 +1,8 @@
-"""Helpers of tests/test_transitions_cpu.py and tests/test_transitions_gpu.py: the CPU restatement of ``gcv_frame_cells``,
-``gcv_blend_fit`` and ``gcv_hist_diff_lag`` (include/genconvit_hip.h states the arithmetic; this file is written from that
-statement: cells by slices, fits in Python integers), of the rule ``pred_func.shot_transitions`` applies to them, and the
-synthetic videos.  No tests here."""
+"""Helpers of tests/test_transitions_cpu.py, tests/test_transitions_gpu.py and tests/test_transitions_sensitivity_cpu.py: the
+CPU restatement of ``gcv_frame_cells``, ``gcv_blend_fit`` and ``gcv_hist_diff_lag`` (include/genconvit_hip.h states the
+arithmetic; this file is written from that statement: cells by slices, fits in Python integers), of the rule
+``pred_func.shot_transitions`` applies to them, a second writing of the first two that can be given a defect (the third's
+is ``cutsutil.hist_diff_alt``), and the synthetic videos.  No tests here."""
 import numpy as np
 import torch
 
@@ -188,3 +189,112 @@ def extreme_cells(grid=8, F=6):
     cells[3, 1::4] = v - 1
     assert all(sum(int(c) ** 2 for c in row) < 2 ** 62 for row in cells)
     return cells.astype(np.int32)
+
+
+def tiny_video():
+    """2 x 32 x 32 noise: at G = 32 a cell is one pixel"""
+    return cu.noise_video(F=2, H=32, W=32, seed=13)
+
+
+def wide_video():
+    """1 x 37 x 1103 noise: 276 groups a row, more than the 256 threads"""
+    return cu.noise_video(F=1, H=37, W=1103, seed=14)
+
+
+def flat_video():
+    """1 x 512 x 512 flat 255: at G = 8 every cell is 255 * 4096, in 8 slices of 8 pixel rows"""
+    return np.full((1, 512, 512, 3), 255, dtype=np.uint8)
+
+
+def tall_video():
+    """2 x 161 x 53 noise: at G = 8 a row of cells has 20-21 pixel rows, in 2 slices of 10 and 10-11"""
+    return cu.noise_video(F=2, H=161, W=53, seed=15)
+
+
+def cells_slices(nframes, H, grid):
+    """S of ``launch_frame_cells``: the row slices a row of cells is split into"""
+    return cu.launch_slices(nframes * grid, H // grid)
+
+
+# ----------------------------------------------------------------------------- the same entries, written again, with defects
+CELL_DEFECTS = ("luma without rounding", "a group's whole sum given to its first pixel's cell",
+                "at most one edge crossed per group", "the cell index taken from x G / W", "column edges rounded",
+                "cells transposed", "the slice-boundary row counted twice", "the slice-boundary row dropped")
+FIT_DEFECTS = ("D taken at lag - 1", "m relative to B", "the Smd / Smm columns shifted by one k",
+               "cells j >= 1 of a thread dropped", "one wave's partial dropped", "products accumulated in float64",
+               "products in 32 bits")
+
+
+def _column_cells(W, G, defect):
+    """the cell column every pixel column's luma goes to, as the kernel's 4-pixel groups walk a row: the cell of the group's
+    first pixel from one division, then on to the next cell at every edge crossed"""
+    half = G // 2 if defect == "column edges rounded" else 0
+    ex = [(v * W + half) // G for v in range(G + 1)]
+    out = np.zeros(W, dtype=np.int64)
+    for x in range(0, W, 4):
+        v = (x * G) // W if defect == "the cell index taken from x G / W" else ((x + 1) * G - 1) // W
+        while half and not ex[v] <= x < ex[v + 1]:           # rounded edges: the first pixel's cell among those edges
+            v += 1 if x >= ex[v + 1] else -1
+        first, crossed = v, 0
+        for k in range(min(4, W - x)):
+            if x + k >= ex[v + 1] and (k or defect != "the cell index taken from x G / W") and \
+                    not (defect == "at most one edge crossed per group" and crossed):
+                v, crossed = v + 1, crossed + 1
+            out[x + k] = first if defect == "a group's whole sum given to its first pixel's cell" else v
+    return out
+
+
+def frame_cells_alt(frames, grid, defect=None):
+    """``frame_cells_ref`` written a second time, the way csrc/cuts.hip walks a frame: a map from every pixel to the cell
+    that receives its luma (columns by 4-pixel group, rows by row of cells and slice) and one weighted bincount per frame.
+    ``defect``: None or one of ``CELL_DEFECTS``.  "the cell index taken from x G / W" is a kernel that trusts x G / W for the
+    group's first pixel (it can be one cell short) and looks for edges from the second pixel on."""
+    assert defect is None or defect in CELL_DEFECTS, defect
+    f = _numpy(frames).astype(np.int64)
+    y = (77 * f[..., 0] + 150 * f[..., 1] + 29 * f[..., 2] + (0 if defect == "luma without rounding" else 128)) >> 8
+    F, H, W = y.shape
+    G = int(grid)
+    ey = cu.edges(H, G)
+    S = cells_slices(F, H, G)
+    col = _column_cells(W, G, defect)
+    row, mult = np.zeros(H, dtype=np.int64), np.zeros(H, dtype=np.int64)
+    for u in range(G):
+        row[ey[u]:ey[u + 1]] = u
+        mult[ey[u]:ey[u + 1]] = cu.slice_rows(ey[u], ey[u + 1], S, {"the slice-boundary row counted twice": "twice",
+                                                                   "the slice-boundary row dropped": "dropped"}.get(defect))
+    cell = col[None, :] * G + row[:, None] if defect == "cells transposed" else row[:, None] * G + col[None, :]
+    out = np.zeros((F, G * G), dtype=np.int64)
+    for k in range(F):
+        out[k] = np.bincount(cell.ravel(), weights=(y[k] * mult[:, None]).ravel(), minlength=G * G).astype(np.int64)
+    return out
+
+
+def blend_fit_alt(cells, lag, defect=None):
+    """``blend_fit_ref`` written a second time, in numpy int64 as the kernel's registers hold it (cell c belongs to thread
+    c % 256 as its cell c // 256, threads 64 w ... 64 w + 63 are wave w).  ``defect``: None or one of ``FIT_DEFECTS``."""
+    assert defect is None or defect in FIT_DEFECTS, defect
+    c = _numpy(cells).astype(np.int64)
+    F, GG = c.shape
+    keep = np.ones(GG, dtype=bool)
+    if defect == "cells j >= 1 of a thread dropped":
+        keep[256:] = False
+    if defect == "one wave's partial dropped" and GG >= 256:
+        keep[np.arange(GG) % 256 >= 192] = False
+
+    def dot(p, q):
+        prod = p[keep] * q[keep]
+        if defect == "products in 32 bits":
+            prod = prod.astype(np.int32).astype(np.int64)
+        if defect == "products accumulated in float64":
+            return int(prod.astype(np.float64).sum())
+        return int(prod.sum())
+    out = np.zeros((max(0, F - lag), 2 * lag - 1), dtype=np.int64)
+    for p in range(max(0, F - lag)):
+        a, b = c[p], c[p + lag]
+        d = (c[p + lag - 1] if defect == "D taken at lag - 1" else b) - a
+        out[p, 0] = dot(d, d)
+        for k in range(1, lag):
+            m = c[p + (k - 1 if defect == "the Smd / Smm columns shifted by one k" else k)] - \
+                (b if defect == "m relative to B" else a)
+            out[p, k], out[p, lag - 1 + k] = dot(m, d), dot(m, m)
+    return out
