@@ -380,6 +380,17 @@ int gcv_vae_explain(gcv_handle* h, const void* x_nchw, const float* eps, int bat
   return gcv_vae_explain_at(h, x_nchw, eps, batch, target, 3, logits, cam_raw, cam224, stream);
 }
 
+// The ensemble's hand-off to the VAE network for one forward (NetBase::in_ensemble, NetBase::after_chain).  The callback
+// captures its caller's locals, so both are reset on every way out of the scope.
+struct EnsembleScope {
+  NetBase* vae;
+  EnsembleScope(NetBase* v, std::function<int()> after_chain) : vae(v) {
+    vae->in_ensemble = true;               // schedule hint: merged backbone pass (net_impl.h, vae_split_env)
+    vae->after_chain = std::move(after_chain);
+  }
+  ~EnsembleScope() { vae->after_chain = nullptr; vae->in_ensemble = false; }
+};
+
 // gcv_genconvit_forward / gcv_genconvit_explain: ex_ed / ex_vae null for the plain forward
 static int genconvit_run(gcv_handle* he, gcv_handle* hv, const void* x_nchw, const float* eps, int batch, float* logits,
                          gcv_stream stream, const Explain* ex_ed, const Explain* ex_vae) {
@@ -410,21 +421,17 @@ static int genconvit_run(gcv_handle* he, gcv_handle* hv, const void* x_nchw, con
     return ex_ed ? he->net->ed_explain(x_nchw, batch, logits, *ex_ed, he->side[0])
                  : he->net->ed_forward(x_nchw, batch, logits, he->side[0]);
   };
-  hv->net->in_ensemble = true;             // schedule hint: merged backbone pass (net_impl.h, vae_split_env)
-#ifdef GCV_ENQUEUE_ED_FIRST                // A/B builds: the round-2/3 order
-  ed_called = true;
-  rc_ed = run_ed();
-#endif
-  hv->net->after_chain = [&]() -> int {
-    if (ed_called) return 0;
-    ed_called = true;
-    rc_ed = run_ed();
-    return 0;                              // (an ED error is reported below; the VAE enqueue completes either way)
-  };
-  int rc = ex_vae ? hv->net->vae_explain(x_nchw, eps, batch, logits + (size_t)batch * 2, *ex_vae, he->side[1])
-                  : hv->net->vae_forward(x_nchw, eps, batch, logits + (size_t)batch * 2, nullptr, nullptr, nullptr, he->side[1]);
-  hv->net->after_chain = nullptr;
-  hv->net->in_ensemble = false;
+  int rc;
+  {
+    EnsembleScope hand_off(hv->net, [&]() -> int {
+      if (ed_called) return 0;
+      ed_called = true;
+      rc_ed = run_ed();
+      return 0;                            // (an ED error is reported below; the VAE enqueue completes either way)
+    });
+    rc = ex_vae ? hv->net->vae_explain(x_nchw, eps, batch, logits + (size_t)batch * 2, *ex_vae, he->side[1])
+                : hv->net->vae_forward(x_nchw, eps, batch, logits + (size_t)batch * 2, nullptr, nullptr, nullptr, he->side[1]);
+  }
   if (!ed_called) rc_ed = run_ed();   // the VAE failed before its chain was through
   if (!rc) rc = rc_ed;
   // join even after an error: whatever was enqueued must be ordered before the caller's next work on `stream`

@@ -1,6 +1,6 @@
 // Diagnostic switches of the kernels, in one place.  A product build (the Makefile's) defines none of them: every
 // GCV_*_ABLATE mask is 0, every *_STAMP(...) expands to nothing and no stamp buffer or reader exists in the library.
-// Only the variant builds of profiles/build_variant.sh (-DGCV_XS_STAMPS=1, -DGCV_P2_ABLATE=2, -DGCV_EXPERIMENTS, ...) turn
+// Only the variant builds of profiles/build_variant.sh (-DGCV_XS_STAMPS=1, -DGCV_P2_ABLATE=2, ...) turn
 // anything on; their outputs are read by profiles/*_stamps.py.
 #pragma once
 

@@ -31,10 +31,7 @@
 namespace gcv {
 
 constexpr int TM_THREADS = 256;
-#ifndef GCV_TC_THREADS
-#define GCV_TC_THREADS 1024                                 // profiles/extend_threads_ab.json: 2.78 ms at 256, 1.94 at 512, 1.56
-#endif
-constexpr int TC_THREADS = GCV_TC_THREADS;
+constexpr int TC_THREADS = 1024;                            // profiles/extend_threads_ab.json: 2.78 ms at 256, 1.94 at 512, 1.56
 constexpr int TM_RMAX = 32;
 constexpr int TC_STEPS_MAX = 1024;
 

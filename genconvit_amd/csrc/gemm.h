@@ -91,66 +91,15 @@ template <int ACT> __device__ __forceinline__ float act_fn(float x) {
   return x;
 }
 
-/// GELU for the 16-bit storage paths, four values at a time on the packed fp32 pipe (v_pk_fma_f32: two lanes of
-// work per issue slot).  The A&S form above costs ~13 VALU + 2 quarter-rate transcendentals per value and made the
-// hidden-layer epilogues VALU-bound; here
-//     gelu(x) = max(x, 0) - h(min(|x|, 4.5)),   h(a) = a * 0.5 * erfc(a / sqrt 2)
-// with h a degree-10 minimax polynomial in t = a * (2/4.5) - 1 (fit in profiles/gelu_fit.py; |error| <= 1.5e-5
-// over all x, i.e. 30x below the fp16 rounding step of the stored result; h(4.5) = 1.5e-5 is the tail that is cut).
+// GELU for the 16-bit storage paths.  The A&S form above costs ~13 VALU + 2 quarter-rate transcendentals per value and
+// made the hidden-layer epilogues VALU-bound; the 16-bit paths evaluate
+//     gelu(x) = max(x, 0) - h(min(|x|, a_max)),   h(a) = a * 0.5 * erfc(a / sqrt 2)
+// with h a minimax polynomial (fit in profiles/gelu_fit.py).  Its first form was a degree-10 fit on [0, 4.5] in fp32
+// (|error| <= 1.5e-5 over all x, i.e. 30x below the fp16 rounding step of the stored result; h(4.5) = 1.5e-5 is the tail
+// that is cut), on v_pk_fma_f32 or on plain v_fma_f32: alone on a SIMD the packed form is ~6 % faster
+// (profiles/micro/gelu_rate.hip, which keeps both: 18.7 vs 19.9 ns per element with two waves), but beside MFMAs a
+// v_pk_fma_f32 stalls the matrix pipe (~22 cycles each, MI355X guide "price of one filler beside MFMAs").
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 splat2(float c) { return (f32x2){c, c}; }
-// NCH independent Horner chains advance in lockstep: a dependent v_pk_fma_f32 needs wait states, so one chain at a
-// time leaves the packed pipe half idle (the compiler pads it with s_nop); 4 chains keep it issuing back to back.
-template <int NCH> __device__ __forceinline__ void gelu_pk_n(f32x2 (&x)[NCH]) {
-  constexpr float kC[11] = {2.749713404e-02f, -1.330395067e-01f, 2.465923971e-01f, -1.472158060e-01f,
-                            -2.029683018e-01f, 4.347813707e-01f, -2.049071560e-01f, -1.763150062e-01f,
-                            1.763803063e-01f, 2.178248281e-02f, -4.258673483e-02f};
-  f32x2 t[NCH], p[NCH];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const f32x2 a = {fminf(fabsf(x[c][0]), 4.5f), fminf(fabsf(x[c][1]), 4.5f)};
-    t[c] = __builtin_elementwise_fma(a, splat2(0.44444444444f), splat2(-1.0f));
-    p[c] = __builtin_elementwise_fma(splat2(kC[10]), t[c], splat2(kC[9]));
-  }
-#pragma unroll
-  for (int k = 8; k >= 0; --k) {
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) p[c] = __builtin_elementwise_fma(p[c], t[c], splat2(kC[k]));
-  }
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const f32x2 r = {fmaxf(x[c][0], 0.0f), fmaxf(x[c][1], 0.0f)};
-    x[c] = r - p[c];
-  }
-}
-__device__ __forceinline__ f32x2 gelu_pk(f32x2 x) {
-  f32x2 v[1] = {x};
-  gelu_pk_n<1>(v);
-  return v[0];
-}
-
-// The same polynomial on plain v_fma_f32, NCH independent chains (bit-identical results: every lane of a v_pk_fma_f32 is an
-// IEEE fma).  Alone on a SIMD the packed form is ~6 % faster (profiles/micro/gelu_rate.hip: 18.7 vs 19.9 ns per element
-// with two waves), but beside MFMAs a v_pk_fma_f32 stalls the matrix pipe (~22 cycles each, MI355X guide "price of one
-// filler beside MFMAs"): kernels that interleave the GELU with MFMAs use this one and are built with -fno-slp-vectorize
-// (hipcc otherwise re-packs the chains).
-template <int NCH> __device__ __forceinline__ void gelu_fma_n(float (&x)[NCH]) {
-  constexpr float kC[11] = {2.749713404e-02f, -1.330395067e-01f, 2.465923971e-01f, -1.472158060e-01f,
-                            -2.029683018e-01f, 4.347813707e-01f, -2.049071560e-01f, -1.763150062e-01f,
-                            1.763803063e-01f, 2.178248281e-02f, -4.258673483e-02f};
-  float t[NCH], p[NCH];
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    t[c] = fmaf(fminf(fabsf(x[c]), 4.5f), 0.44444444444f, -1.0f);
-    p[c] = fmaf(kC[10], t[c], kC[9]);
-  }
-#pragma unroll
-  for (int k = 8; k >= 0; --k)
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) p[c] = fmaf(p[c], t[c], kC[k]);
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) x[c] = fmaxf(x[c], 0.0f) - p[c];
-}
 
 // GELU with the polynomial on the packed-fp16 pipe (16-bit storage paths).  Measured on gfx950
 // (profiles/micro/mfma_valu_overlap.hip): while MFMAs are in flight on a SIMD every vector instruction costs ~4-5 cycles
@@ -253,18 +202,10 @@ template <typename T, int NV> __device__ __forceinline__ void gelu_h16_frag(cons
   GeluH16::finish_frag<T, NV / 2>(x, st, out);
 }
 
-#ifndef GCV_GELU_H16
-#define GCV_GELU_H16 1        // act4n evaluates the 16-bit GELU with gelu_h16_n (0: the packed-fp32 polynomial, gelu_pk_n)
-#endif
-#ifndef GCV_GELU_SCALAR
-#define GCV_GELU_SCALAR 0     // 1: act4n evaluates the 16-bit GELU with gelu_fma_n (for translation units built with -fno-slp-vectorize)
-#endif
-
-// activation of NG groups of four consecutive channels (bias already added); for 16-bit GELU the 2*NG packed
-// pairs are the independent chains of gelu_pk_n
+// activation of NG groups of four consecutive channels (bias already added): the 16-bit GELU goes through gelu_h16_n,
+// everything else is element-wise
 template <int ACT, typename T, int NG> __device__ __forceinline__ void act4n(float (&v)[NG][4]) {
-#ifndef GCV_GELU_EXACT
-  if (ACT == ACT_GELU && sizeof(T) == 2 && GCV_GELU_H16 && !GCV_GELU_SCALAR) {
+  if (ACT == ACT_GELU && sizeof(T) == 2) {
     float x[4 * NG];
 #pragma unroll
     for (int g = 0; g < NG; ++g)
@@ -277,34 +218,6 @@ template <int ACT, typename T, int NG> __device__ __forceinline__ void act4n(flo
       for (int e = 0; e < 4; ++e) v[g][e] = x[4 * g + e];
     return;
   }
-  if (ACT == ACT_GELU && sizeof(T) == 2 && GCV_GELU_SCALAR) {
-    float x[4 * NG];
-#pragma unroll
-    for (int g = 0; g < NG; ++g)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) x[4 * g + e] = v[g][e];
-    gelu_fma_n<4 * NG>(x);
-#pragma unroll
-    for (int g = 0; g < NG; ++g)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[g][e] = x[4 * g + e];
-    return;
-  }
-  if (ACT == ACT_GELU && sizeof(T) == 2) {
-    f32x2 x[2 * NG];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      x[2 * g] = (f32x2){v[g][0], v[g][1]};
-      x[2 * g + 1] = (f32x2){v[g][2], v[g][3]};
-    }
-    gelu_pk_n<2 * NG>(x);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      v[g][0] = x[2 * g][0]; v[g][1] = x[2 * g][1]; v[g][2] = x[2 * g + 1][0]; v[g][3] = x[2 * g + 1][1];
-    }
-    return;
-  }
-#endif
 #pragma unroll
   for (int g = 0; g < NG; ++g)
 #pragma unroll

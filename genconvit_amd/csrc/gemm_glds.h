@@ -21,15 +21,13 @@
 
 namespace gcv {
 
-#ifndef GCV_GLDS_STAGES
-#define GCV_GLDS_STAGES 2     // 64-byte-row ring: 2 x 20 KB leaves room for THREE workgroups per CU (-5 % at K = 384 vs 4 stages)
-#endif
+constexpr int kGldsStages64 = 2;   // 64-byte-row ring: 2 x 20 KB leaves room for THREE workgroups per CU (-5 % at K = 384 vs 4 stages)
 constexpr int kGldsBM = 128, kGldsBN = 192;
 // ring geometry by bytes per LDS row: 64 B (32 k) x 2 stages (40 KB: the epilogue staging then sets the footprint, 53 KB,
 // three workgroups per CU), or 128 B (64 k, a whole 128-byte line per row) x 2 stages (80 KB, two per CU); whole-line
 // fetches fill LDS 1.3-1.4x faster (profiles/micro/lds_dma_rate.hip; the fill rate does not depend on the ring depth), so
 // 128 is used when K % 64 == 0 and K >= 512
-template <int BKB> struct GldsRing { static constexpr int stages = BKB == 64 ? GCV_GLDS_STAGES : 2; };
+template <int BKB> struct GldsRing { static constexpr int stages = BKB == 64 ? kGldsStages64 : 2; };
 
 template <typename T, int BKB = 64> struct GldsSmem {
   static constexpr int kStage = (kGldsBM + kGldsBN) * BKB;                 // 20480 / 40960

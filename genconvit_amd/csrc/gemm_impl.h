@@ -15,16 +15,6 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 // default LDS row: 64 B for fp32 (16 k), 128 B for 16-bit (64 k)
 template <typename T> struct DefBKB { static constexpr int v = sizeof(T) == 4 ? 64 : 128; };
 
-#ifndef GCV_IM2COL_SHORTK
-#define GCV_IM2COL_SHORTK 1     // 0: A/B builds (64-deep K tiles everywhere, the round-3 dispatch)
-#endif
-// A/B switches of the LDS-DMA kernel for profiling (builds with -DGCV_EXPERIMENTS only), read once
-struct GldsEnv {
-  bool off = exp_env("GCV_NO_GLDS") != nullptr;         // no launch takes the LDS-DMA kernel
-  bool row64 = exp_env("GCV_GLDS_ROW64") != nullptr;    // its launches all take the 64-byte-row ring
-};
-static inline const GldsEnv& glds_env() { static const GldsEnv e; return e; }
-
 // The three kinds of kernel.  plan<T, EPI>(g): tile fields, grid, threads and dynamic LDS bytes of the launch g;
 // kernel<T, AMODE, EPI, ACT>(): the instantiation.
 template <int BM, int BN, int WM, int WN, int BKB> struct TileShape {
@@ -116,10 +106,10 @@ template <typename T, class F> int gemm_select(const GemmArgs& g, int a_mode, in
   const bool short_k = h16 && (g.K % 64) != 0 && (g.K % 64) <= 32;
   // gemm_glds_kernel (gemm_glds.h), 16-bit storage: whole 128 x 192 tiles along N, no K tail, at least two M tiles, 16-byte
   // stores (what the checks above leave open of them; EPI_RESID also reads resid 8 bytes at a time)
-  const bool dma = h16 && !glds_env().off && g.N % kGldsBN == 0 && g.K % 32 == 0 && g.M >= 256 && g.ldc % 8 == 0 &&
+  const bool dma = h16 && g.N % kGldsBN == 0 && g.K % 32 == 0 && g.M >= 256 && g.ldc % 8 == 0 &&
                    aligned16(g.C) && (epi != EPI_RESID || (reinterpret_cast<uintptr_t>(g.resid) & 7u) == 0);
   // ... on 128-byte LDS rows (K = 384: 6 stages, the 4-deep ring of 64-byte rows wins)
-  const bool dma128 = g.K % 64 == 0 && g.K >= 512 && !glds_env().row64;
+  const bool dma128 = g.K % 64 == 0 && g.K >= 512;
 
   if (a_mode == A_PLAIN && epi == EPI_BIAS_ACT) {
     if constexpr (h16)
@@ -172,10 +162,9 @@ template <typename T, class F> int gemm_select(const GemmArgs& g, int a_mode, in
     }
     // K = 144 / 288 (16 / 32 input channels): 32-deep K tiles instead of a 64-deep one that is three quarters / half padding
     // (round 4, paired runs on one box: ed.enc 0.200 -> 0.171 ms, vae.enc 0.077 -> 0.068 ms per step)
-    const bool k32 = short_k && GCV_IM2COL_SHORTK;
     auto tiles = [&](auto route) {
-      if (g.N <= 32 && k32) return go(route, TileShape<128, 32, 32, 32, 64>{});
-      if (g.N <= 64 && k32) return go(route, TileShape<128, 64, 32, 64, 64>{});
+      if (g.N <= 32 && short_k) return go(route, TileShape<128, 32, 32, 32, 64>{});
+      if (g.N <= 64 && short_k) return go(route, TileShape<128, 64, 32, 64, 64>{});
       if (g.N <= 32) return go(route, TileShape<128, 32, 32, 32, B>{});
       if (g.N <= 64) return go(route, TileShape<128, 64, 32, 64, B>{});
       return go(route, TileShape<128, 128, 64, 64, B>{});

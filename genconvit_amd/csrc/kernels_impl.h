@@ -16,12 +16,11 @@ static int launch_stem_ln_c(const T* x, int64_t sb, int64_t sc, int64_t sy, int6
   GCV_REQUIRE(total > 0, "stem: empty");
   GCV_REQUIRE((reinterpret_cast<uintptr_t>(wp) & 15u) == 0, "stem: packed weights must be 16-byte aligned");
   if constexpr (sizeof(T) == 2) {
-    // matrix-pipe stem: the two frame layouts of the path with 8-byte aligned patch pieces (GCV_STEM_VALU=1: A/B switch)
-    static const bool valu = exp_env("GCV_STEM_VALU") != nullptr;
+    // matrix-pipe stem: the two frame layouts of the path with 8-byte aligned patch pieces
     const bool al = (reinterpret_cast<uintptr_t>(x) & 7u) == 0 && ((sb | sy) & 3) == 0 &&
                     (reinterpret_cast<uintptr_t>(out) & 15u) == 0;
     const bool nchw4 = al && sx == 1 && (sc & 3) == 0, nhwc4 = al && sc == 1 && sx == 3;
-    if (!valu && (nchw4 || nhwc4) && total < (int64_t)1 << 30) {
+    if ((nchw4 || nhwc4) && total < (int64_t)1 << 30) {
       const int ntiles = (int)cdiv64(total, 32);
       const int grid = std::min(cdiv(ntiles, 4), 256 * 8);
       hipLaunchKernelGGL((stem_ln_mfma_kernel<T, C / 32>), dim3(grid), dim3(256), 0, s, x, sb, sc, sy, nhwc4 ? 1 : 0, wp, bias,
@@ -121,12 +120,11 @@ int launch_conv3_first(const T* x, int64_t sb, int64_t sc, int64_t sy, int64_t s
   GCV_REQUIRE(H % 2 == 0 && W % 2 == 0 && nimg > 0, "conv3_first: even H, W");
   const int64_t total = (int64_t)nimg * (H / 2) * (W / 2);
   if constexpr (sizeof(T) == 2) {
-    // matrix-pipe variant: NCHW frames up to 224 wide whose rows are 16-byte pieces (GCV_CONV3_VALU=1: A/B switch)
-    static const bool valu = exp_env("GCV_CONV3_VALU") != nullptr;
+    // matrix-pipe variant: NCHW frames up to 224 wide whose rows are 16-byte pieces
     const bool ok = sx == 1 && W % 32 == 0 && W <= kConv3MaxW && H % 8 == 0 && ((sb | sc | sy) & 7) == 0 &&
                     (reinterpret_cast<uintptr_t>(x) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 7u) == 0 &&
                     (reinterpret_cast<uintptr_t>(bias) & 15u) == 0;
-    if (ok && !valu) {
+    if (ok) {
       const dim3 g2((unsigned)(nimg * (H / 8)));
       if (pool)
         hipLaunchKernelGGL((conv3_first_mfma_kernel<T, true>), g2, dim3(256), 0, s, x, sb, sc, sy, wp, bias, out, nimg, H, W, act);
@@ -213,8 +211,7 @@ int launch_swin_window_attn(const T* qkv, const float* rpb, T* out, int nimg, in
   GCV_REQUIRE(shift == 0 || (shift == 3 && H > 7), "swin attention: shift is 0 or 3");
   const float scale = 0.17677669529663689f;   // 32^-0.5
   if constexpr (sizeof(T) == 2) {
-    static const bool valu_only = exp_env("GCV_SWIN_ATTN_VALU") != nullptr;   // A/B switch
-    if (!valu_only && (reinterpret_cast<uintptr_t>(qkv) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 7u) == 0 && C % 8 == 0) {
+    if ((reinterpret_cast<uintptr_t>(qkv) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out) & 7u) == 0 && C % 8 == 0) {
       hipLaunchKernelGGL((swin_window_attn_mfma_kernel<T>), dim3(nimg * (H / 7) * (W / 7), nH), dim3(64), 0, s, qkv, rpb,
                          out, H, W, C, nH, shift, scale);
       GCV_CHECK_HIP(hipGetLastError());

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Fit of the packed-fp32 GELU used by the 16-bit GEMM epilogues (genconvit_amd/csrc/gemm.h: gelu_pk).
+"""Fit of the fp32 GELU polynomial the 16-bit GEMM epilogues used first (kept in profiles/micro/gelu_rate.hip).
 
 gelu(x) = max(x, 0) - h(min(|x|, c)),  h(a) = a * 0.5 * erfc(a / sqrt 2): h is a smooth bump that decays to 0, so a
 plain polynomial in t = 2a/c - 1 fits it without the |x| error amplification an erf polynomial has.  Lawson-weighted

@@ -5,6 +5,33 @@
 #include "gemm.h"
 using namespace gcv;
 
+// The degree-10 fp32 polynomial the 16-bit paths used before the packed-fp16 one (gemm.h, GeluH16), on the packed fp32 pipe.
+// NCH independent Horner chains advance in lockstep: a dependent v_pk_fma_f32 needs wait states, so one chain at a
+// time leaves the packed pipe half idle (the compiler pads it with s_nop); 4 chains keep it issuing back to back.
+__device__ __forceinline__ f32x2 splat2(float c) { return (f32x2){c, c}; }
+template <int NCH> __device__ __forceinline__ void gelu_pk_n(f32x2 (&x)[NCH]) {
+  constexpr float kC[11] = {2.749713404e-02f, -1.330395067e-01f, 2.465923971e-01f, -1.472158060e-01f,
+                            -2.029683018e-01f, 4.347813707e-01f, -2.049071560e-01f, -1.763150062e-01f,
+                            1.763803063e-01f, 2.178248281e-02f, -4.258673483e-02f};
+  f32x2 t[NCH], p[NCH];
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const f32x2 a = {fminf(fabsf(x[c][0]), 4.5f), fminf(fabsf(x[c][1]), 4.5f)};
+    t[c] = __builtin_elementwise_fma(a, splat2(0.44444444444f), splat2(-1.0f));
+    p[c] = __builtin_elementwise_fma(splat2(kC[10]), t[c], splat2(kC[9]));
+  }
+#pragma unroll
+  for (int k = 8; k >= 0; --k) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) p[c] = __builtin_elementwise_fma(p[c], t[c], splat2(kC[k]));
+  }
+#pragma unroll
+  for (int c = 0; c < NCH; ++c) {
+    const f32x2 r = {fmaxf(x[c][0], 0.0f), fmaxf(x[c][1], 0.0f)};
+    x[c] = r - p[c];
+  }
+}
+
 // scalar-fma variant of the same polynomial, NCH independent chains
 template <int NCH> __device__ __forceinline__ void gelu_fma_n(float (&x)[NCH]) {
   constexpr float kC[11] = {2.749713404e-02f, -1.330395067e-01f, 2.465923971e-01f, -1.472158060e-01f,
@@ -33,7 +60,7 @@ template <int MODE> __global__ void k(float* out, long long* cyc, float seed) {
     if (MODE == 0) {                      // exact A&S erf, scalar
 #pragma unroll
       for (int i = 0; i < 16; ++i) v[i] = act_fn<ACT_GELU>(v[i]) + 0.25f;
-    } else if (MODE == 1) {               // packed polynomial, 4 chains (as in the kernels)
+    } else if (MODE == 1) {               // packed polynomial, 4 chains (as the kernels had it)
 #pragma unroll
       for (int g = 0; g < 16; g += 8) {
         f32x2 x[4] = {{v[g], v[g + 1]}, {v[g + 2], v[g + 3]}, {v[g + 4], v[g + 5]}, {v[g + 6], v[g + 7]}};

@@ -27,6 +27,18 @@ def test_library_exports_every_declared_symbol():
     assert declared == set(_lib.SIGNATURES), (declared ^ set(_lib.SIGNATURES))
 
 
+def test_library_reads_two_environment_variables():
+    """`strings libgenconvit_hip.so | grep ^GCV_` finds GCV_VAE_SPLIT and GCV_RCCL_PATH, nothing else.  A name
+    the library hands to getenv is a string of its own, so an A/B switch that grows back shows here."""
+    from genconvit_amd import _lib
+    _lib.load()
+    blob = open(_lib.LIB_PATH, "rb").read()
+    runs = re.findall(rb"[\x20-\x7e\t]{4,}", blob)          # what strings(1) prints: printable runs of four or more
+    assert len(runs) > 100, "no strings parsed"
+    found = {r.decode() for r in runs if r.startswith(b"GCV_")}
+    assert found == {"GCV_VAE_SPLIT", "GCV_RCCL_PATH"}, sorted(found)
+
+
 def test_library_has_no_hard_hip_runtime_dependency():
     """The .so must bind to the process's HIP runtime (torch's bundled one), not bring a second."""
     import subprocess
