@@ -179,7 +179,7 @@ template <typename T> struct MlpTestRunner {
 template <typename T>
 static int k_mlp_dispatch(int C, const void* x, const void* w1, const float* b1, const float* w2_f32, const float* b2,
                           const float* gamma, const void* resid, void* out, int M, hipStream_t s, int iters = 0,
-                          float* ms = nullptr, const LnpSpec* lnp = nullptr) {
+                          float* ms = nullptr, const LnpArgs* lnp = nullptr) {
   struct Bufs {                                    // freed on every exit path (after the stream has drained)
     hipStream_t s;
     std::vector<void*> p;
@@ -230,8 +230,8 @@ static int k_mlp_dispatch(int C, const void* x, const void* w1, const float* b1,
   return timed(nullptr, ms);
 }
 
-// the caller's segment tables of gcv_k_fused_mlp_lnp -> the network's LnpSpec (lnp_plan)
-static int lnp_from_tables(LnpSpec& l, int C, int M, const float* w, const float* b, float eps, int nseg, const int* tok0,
+// the caller's segment tables of gcv_k_fused_mlp_lnp -> the network's LnpArgs (lnp_plan)
+static int lnp_from_tables(LnpArgs& l, int C, int M, const float* w, const float* b, float eps, int nseg, const int* tok0,
                            const int* hw, const int* wd, const int* out0) {
   GCV_REQUIRE(nseg >= 1 && nseg <= 4 && w && b && tok0 && hw && wd && out0,
               "fused MLP with LN-patchify epilogue: 1..4 segments and their tables");
@@ -920,7 +920,7 @@ int gcv_k_fused_mlp_lnp(int dtype, int C, const void* x, const void* w1, const f
                         float eps, int nseg, const int* tok0, const int* hw, const int* wd, const int* out0, void* out, int M,
                         gcv_stream s) {
   GCV_REQUIRE(dtype == GCV_F16 || dtype == GCV_BF16, "the MLP kernels are built for 16-bit storage");
-  LnpSpec l;
+  LnpArgs l;
   GCV_TRY(lnp_from_tables(l, C, M, ln_w, ln_b, eps, nseg, tok0, hw, wd, out0));
   if (dtype == GCV_F16)
     return k_mlp_dispatch<half_t>(C, x, w1, b1, w2_f32, b2, gamma, resid, out, M, (hipStream_t)s, 0, nullptr, &l);

@@ -67,21 +67,15 @@ int pack_cnx_mlp(CnxMlpW<T>& w, int C, const float* w2_f32, Alloc&& alloc, hipSt
   return 0;
 }
 
-// The stage boundary's LayerNorm2d + 2x2 space-to-depth in the epilogue of the stage's last MLP (MlpArgs, XsMlpArgs): `out`
+// The stage boundary's LayerNorm2d + 2x2 space-to-depth in the epilogue of the stage's last MLP (LnpArgs, mlp_parts.h): `out`
 // then receives the patch rows (M/4, 4C) of the down-sampling GEMM and the (M, C) residual stream is not written.
-struct LnpSpec {
-  const float *w = nullptr, *b = nullptr;
-  float eps = 0.0f;
-  int nseg = 0;
-  int tok0[4], hw[4], wd[4], out0[4];   // per segment: first token, pixels per image, map width, first patch row
-};
-// whether kind has the epilogue at M tokens (C = 96: the LDS-resident kernel only)
+// Whether kind has the epilogue at M tokens (C = 96: the LDS-resident kernel only):
 static inline bool lnp_supported(MlpKind kind, int C, int64_t M) {
   return kind == MlpKind::Xs192 || (kind == MlpKind::Fused96 && fused_mlp_res_applies(C, M));
 }
 // Fills l for nseg (<= 4) token-contiguous segments of n[s] images with h[s] x wd[s] maps, and returns whether the
 // epilogue fuses: lnp_supported, and every map even (an odd map drops its last row / column: the separate kernel does that).
-static inline bool lnp_plan(LnpSpec& l, MlpKind kind, int C, int64_t M, int nseg, const int* n, const int* h,
+static inline bool lnp_plan(LnpArgs& l, MlpKind kind, int C, int64_t M, int nseg, const int* n, const int* h,
                             const int* wd) {
   bool even = true;
   int64_t t = 0, o = 0;
@@ -94,19 +88,13 @@ static inline bool lnp_plan(LnpSpec& l, MlpKind kind, int C, int64_t M, int nseg
   }
   return even && lnp_supported(kind, C, M);
 }
-template <typename A> static void set_lnp(A& a, const LnpSpec& l) {
-  a.lnp_w = l.w; a.lnp_b = l.b; a.lnp_eps = l.eps; a.lnp_nseg = l.nseg;
-  for (int s = 0; s < l.nseg; ++s) {
-    a.lnp_tok0[s] = l.tok0[s]; a.lnp_hw[s] = l.hw[s]; a.lnp_wd[s] = l.wd[s]; a.lnp_out0[s] = l.out0[s];
-  }
-}
 
 // Launches the MLP of w.kind over M tokens of x.  hidden: the (M, 4C) tensor of Gemm, the fragment-major one of Pair384
 // (mlp_pair_hidden_bytes).  lnp (lnp_plan returned true): the LN-patchify epilogue, into `out`.  Launches go through
 // r.run(tag, flops, bytes, f) and r.gemm(tag, GemmArgs, a_mode, epi) on stream s (NetImpl: tagged and profiled).
 template <typename T, class R>
 int launch_cnx_mlp(R& r, const CnxMlpW<T>& w, int C, const T* x, const T* resid, T* out, T* hidden, int M,
-                   const LnpSpec* lnp, hipStream_t s) {
+                   const LnpArgs* lnp, hipStream_t s) {
   GCV_REQUIRE(!lnp || lnp_supported(w.kind, C, M), "LN-patchify epilogue of an MLP kind without one");
   if constexpr (sizeof(T) == 2) {
     const double fused_flops = 16.0 * M * C * (double)C, fused_bytes = 3.0 * sizeof(T) * (double)M * C + 16.0 * C * C;
@@ -114,12 +102,12 @@ int launch_cnx_mlp(R& r, const CnxMlpW<T>& w, int C, const T* x, const T* resid,
       case MlpKind::Gemm: break;
       case MlpKind::Fused96: {
         MlpArgs a{x, w.w1, w.b1, w.w2c, w.b2, w.gamma, resid, out, M};
-        if (lnp) set_lnp(a, *lnp);
+        if (lnp) a.lnp = *lnp;
         return r.run("cnx.fused_mlp", fused_flops, fused_bytes, [&] { return launch_fused_mlp<T>(a, C, s); });
       }
       case MlpKind::Xs192: {
         XsMlpArgs a{x, w.wp, w.b1, w.b2, w.gamma, resid, out, M};
-        if (lnp) set_lnp(a, *lnp);
+        if (lnp) a.lnp = *lnp;
         return r.run("cnx.fused_mlp", fused_flops, fused_bytes, [&] { return launch_xs_mlp<T>(a, C, s); });
       }
       case MlpKind::Pair384: {

@@ -31,22 +31,14 @@ template <typename T> int launch_pack_w2_chunks(const float* w2_dev, T* out, int
   return 0;
 }
 
-template <typename T, int C, int NW> static int launch_mlp_c(const MlpArgs& a, hipStream_t s) {
-  constexpr int SMEM = MlpSmem<T, C, NW>::bytes;
-  GCV_ENSURE_LDS((fused_mlp_kernel<T, C, NW>), SMEM);
-  hipLaunchKernelGGL((fused_mlp_kernel<T, C, NW>), dim3(cdiv(a.M, NW * 32)), dim3(NW * 64), SMEM, s, a);
-  GCV_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
 template <typename T> int launch_fused_mlp_res(const MlpArgs& a, hipStream_t s) {
   constexpr int SMEM = MlpResSmem::bytes;
   GCV_ENSURE_LDS((fused_mlp_res_kernel<T>), SMEM);
   constexpr int nw = 8;
   const int wave_tiles = cdiv(a.M, 32);
   const int nwg = cdiv(wave_tiles, nw) < 256 ? cdiv(wave_tiles, nw) : 256;    // one persistent workgroup per CU
-  if (a.lnp_nseg > 0) {                                    // last block of the stage: LayerNorm2d + space-to-depth epilogue
-    GCV_REQUIRE(a.lnp_w && a.lnp_b && a.lnp_nseg <= 4, "fused MLP: LN-patchify epilogue arguments");
+  if (a.lnp.nseg > 0) {                                    // last block of the stage: LayerNorm2d + space-to-depth epilogue
+    GCV_REQUIRE(a.lnp.w && a.lnp.b && a.lnp.nseg <= 4, "fused MLP: LN-patchify epilogue arguments");
     GCV_ENSURE_LDS((fused_mlp_res_kernel<T, true>), SMEM);
     hipLaunchKernelGGL((fused_mlp_res_kernel<T, true>), dim3(nwg), dim3(64 * nw), SMEM, s, a);
   } else {
@@ -60,10 +52,13 @@ template <typename T> int launch_fused_mlp(const MlpArgs& a, int C, hipStream_t 
   GCV_REQUIRE(a.M > 0 && a.X && a.W1 && a.W2c && a.b1 && a.b2 && a.gamma && a.resid && a.out, "fused MLP: null argument");
   // with enough tokens to give every wave of the chip several tiles: weights resident in LDS, no barriers
   if (fused_mlp_res_applies(C, a.M)) return launch_fused_mlp_res<T>(a, s);
-  GCV_REQUIRE(a.lnp_nseg == 0, "fused MLP: the LN-patchify epilogue exists in the LDS-resident kernel only");
-  GCV_REQUIRE(C == 96, "fused MLP kernels of this file: C = 96");
-  // 4-wave workgroups: 81 KB LDS -> two independent workgroups per CU overlap each other's prologue / epilogue
-  return launch_mlp_c<T, 96, 4>(a, s);
+  GCV_REQUIRE(a.lnp.nseg == 0, "fused MLP: the LN-patchify epilogue exists in the LDS-resident kernel only");
+  GCV_REQUIRE(C == MlpSmem::C, "fused MLP kernels of this file: C = 96");
+  constexpr int SMEM = MlpSmem::bytes, NW = MlpSmem::NW;
+  GCV_ENSURE_LDS((fused_mlp_kernel<T>), SMEM);
+  hipLaunchKernelGGL((fused_mlp_kernel<T>), dim3(cdiv(a.M, NW * 32)), dim3(NW * 64), SMEM, s, a);
+  GCV_CHECK_HIP(hipGetLastError());
+  return 0;
 }
 
 }  // namespace gcv

@@ -37,7 +37,7 @@ struct MlpResSmem {
 __device__ __forceinline__ int mlp_res_swz(int row, int k16) { return (k16 & ~3) | ((k16 & 3) ^ ((row >> 2) & 3)); }
 
 // LNP: the epilogue applies the stage boundary's LayerNorm2d + 2x2 space-to-depth instead of storing the residual stream
-// (MlpArgs::lnp_*): a wave owns whole token rows (lanes l and l + 32 hold the two halves of a row's 96 channels), so the
+// (MlpArgs::lnp): a wave owns whole token rows (lanes l and l + 32 hold the two halves of a row's 96 channels), so the
 // statistics are 96 register operations and one cross-lane exchange, and LN-patchify's pass over the tensor (77 MB read +
 // 77 MB written per 128 images) disappears together with this kernel's own 77 MB store.
 template <typename T, bool LNP = false>
@@ -76,7 +76,7 @@ __global__ void __launch_bounds__(512, 1) fused_mlp_res_kernel(const MlpArgs a) 
     if (tid == 0) *reinterpret_cast<int*>(smem + MlpResSmem::kCtr) = (int)blockDim.x >> 6;   // slots 0 .. nwaves-1 are taken
     if (LNP) {
       float* sl = reinterpret_cast<float*>(smem + MlpResSmem::kLn);
-      for (int i = tid; i < 192; i += (int)blockDim.x) sl[i] = i < 96 ? a.lnp_w[i] : a.lnp_b[i - 96];
+      for (int i = tid; i < 192; i += (int)blockDim.x) sl[i] = i < 96 ? a.lnp.w[i] : a.lnp.b[i - 96];
     }
   }
   __syncthreads();
@@ -85,7 +85,6 @@ __global__ void __launch_bounds__(512, 1) fused_mlp_res_kernel(const MlpArgs a) 
   const T* __restrict__ Xp = (const T*)a.X;
   const T* Rp = (const T*)a.resid;
   T* Op = (T*)a.out;
-  typedef T t4 __attribute__((ext_vector_type(4)));
 
   const int ntiles = (a.M + 31) / 32;
   const int nwaves = (int)blockDim.x >> 6;
@@ -161,7 +160,8 @@ __global__ void __launch_bounds__(512, 1) fused_mlp_res_kernel(const MlpArgs a) 
 #pragma unroll
         for (int o = 0; o < NO; ++o) w2f[s][o] = *(const u32x4*)(base + 32 * o * ROW + frag_off(2 * (2 * j + s) + lh));
     };
-    auto read_b1 = [&](int g, f32x16& acc) {               // accumulator := bias of group g (token-on-lane layout)
+    auto read_b1 = [&](int g, f32x16& acc) {               // accumulator := bias of group g (token-on-lane layout;
+                                                           // not shared with the xs kernels: see xs_mlp_kernel's step)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const f32x4 bv = *(const f32x4*)(sB1 + g * 32 + 8 * q + 4 * lh);
@@ -266,61 +266,59 @@ __global__ void __launch_bounds__(512, 1) fused_mlp_res_kernel(const MlpArgs a) 
     const float* const sB2t = reinterpret_cast<const float*>(smem + oB2);
     const float* const sGt = reinterpret_cast<const float*>(smem + oG);
     // A row's 16 bytes (o, q) are split over the half-waves (lane lr: channels 8q .. 8q+3, lane lr+32: 8q+4 .. 8q+7).
-    // One v_permlane32_swap per dword of a (q, q+1) pair leaves lanes 0-31 with the 16 contiguous bytes of piece q
+    // The permlane32 exchange (mlp_parts.h) of a (q, q+1) pair leaves lanes 0-31 with the 16 contiguous bytes of piece q
     // and lanes 32-63 with those of piece q+1: six 16-byte stores per tile instead of twelve 8-byte ones (each store
     // instruction touches 32 rows; the epilogue was 5.6k of a tile's 26k cycles, bound by store issue).
-    if constexpr (LNP) {
-      // ---- out = LayerNorm2d(resid + gamma * (acc2 + b2)) at the patch position of token m
-      // the residual rows first (same permlane32 exchange as below), in place of the accumulators
-      float s1 = 0.0f, s2 = 0.0f;
+    // LNP: the values go back into the accumulators instead, with their sum and sum of squares.
+    // (xs_mlp_kernel's epilogue is this one with 4 lh in the pointers.  Shared __forceinline__ functions for this loop, the
+    // patch position and the normalising store were tried: the loop and the store each came out one VGPR lower with the
+    // code around them reordered, the patch position reordered the LNP variant; none reproduced the code, so they stay.)
+    float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
-      for (int o = 0; o < NO; ++o)
+    for (int o = 0; o < NO; ++o)
 #pragma unroll
-        for (int q = 0; q < 4; q += 2) {
-          const u32x4 rw = rres[o][q >> 1];
-          const auto rx = __builtin_amdgcn_permlane32_swap(rw[0], rw[2], false, false);
-          const auto ry = __builtin_amdgcn_permlane32_swap(rw[1], rw[3], false, false);
-          const t4 rr[2] = {__builtin_bit_cast(t4, uint2{rx[0], ry[0]}), __builtin_bit_cast(t4, uint2{rx[1], ry[1]})};
+      for (int q = 0; q < 4; q += 2) {
+        vec4<T> rr[2];
+        piece_to_halves<T>(rres[o][q >> 1], rr);
+        uint2 pk[2];
 #pragma unroll
-          for (int d = 0; d < 2; ++d) {
-            const int n = 32 * o + 8 * (q + d) + 4 * lh;
-            const f32x4 bv = *(const f32x4*)(sB2t + n);
-            const f32x4 gv = *(const f32x4*)(sGt + n);
+        for (int d = 0; d < 2; ++d) {
+          const int n = 32 * o + 8 * (q + d) + 4 * lh;
+          const f32x4 bv = *(const f32x4*)(sB2t + n);
+          const f32x4 gv = *(const f32x4*)(sGt + n);
+          vec4<T> o4;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const float v = fmaf(acc2[o][4 * (q + d) + e] + bv[e], gv[e], to_f(rr[d][e]));
+          for (int e = 0; e < 4; ++e) {
+            const float v = fmaf(acc2[o][4 * (q + d) + e] + bv[e], gv[e], to_f(rr[d][e]));
+            if constexpr (LNP) {
               acc2[o][4 * (q + d) + e] = v;
               s1 += v;
               s2 = fmaf(v, v, s2);
+            } else {
+              o4[e] = from_f<T>(v);
             }
           }
+          if constexpr (!LNP) pk[d] = __builtin_bit_cast(uint2, o4);
         }
-      s1 += __shfl_xor(s1, 32);                            // the other half of the row's channels lives in lane ^ 32
-      s2 += __shfl_xor(s2, 32);
-      const float mean = s1 * (1.0f / C);
-      float var = fmaf(-mean, mean, s2 * (1.0f / C));
-      if (var < s2 * (kLnRecentre / C)) {
-        // one pass cancels here (common.h, kLnRecentre): the squares of the centred values instead; lanes l and l + 32
-        // hold the same mean and s2 and decide alike
-        s2 = 0.0f;
-#pragma unroll
-        for (int o = 0; o < NO; ++o)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) s2 = fmaf(acc2[o][e] - mean, acc2[o][e] - mean, s2);
-        s2 += __shfl_xor(s2, 32);
-        var = s2 * (1.0f / C);
+        if constexpr (!LNP) {
+          const u32x4 w = halves_to_piece(pk);
+          const int n16 = 32 * o + 8 * q + 8 * lh;           // lanes 0-31: channels 8q .. 8q+7, lanes 32-63: 8q+8 .. 8q+15
+          if (m < a.M && (!(GCV_MLP_ABLATE & 8) || w[0] == 0x12345u)) *(u32x4*)(Op + m * C + n16) = w;
+        }
       }
-      const float rstd = __builtin_amdgcn_rsqf(fmaxf(var, 0.0f) + a.lnp_eps);
-      const float nmr = -mean * rstd;
+    if constexpr (LNP) {
+      // ---- out = LayerNorm2d(resid + gamma * (acc2 + b2)) at the patch position of token m
+      float rstd, nmr;
+      lnp_stats<C, true>(acc2, s1, s2, a.lnp.eps, rstd, nmr);   // the centred squares under a branch: registers allow it here
       // patch position of this lane's token: segment, image, (y, x) -> patch row and the quarter of its 4C columns
       int sg = 0;
 #pragma unroll
-      for (int t = 1; t < 4; ++t) sg += (t < a.lnp_nseg && (int)mc >= a.lnp_tok0[t]) ? 1 : 0;
-      const int local = (int)mc - a.lnp_tok0[sg];
-      const int hw = a.lnp_hw[sg], wd = a.lnp_wd[sg];
+      for (int t = 1; t < 4; ++t) sg += (t < a.lnp.nseg && (int)mc >= a.lnp.tok0[t]) ? 1 : 0;
+      const int local = (int)mc - a.lnp.tok0[sg];
+      const int hw = a.lnp.hw[sg], wd = a.lnp.wd[sg];
       const int img = local / hw, rem = local - img * hw;
       const int py = rem / wd, px = rem - py * wd;
-      const int64_t prow = (int64_t)a.lnp_out0[sg] + ((int64_t)img * (hw / wd / 2) + (py >> 1)) * (wd >> 1) + (px >> 1);
+      const int64_t prow = (int64_t)a.lnp.out0[sg] + ((int64_t)img * (hw / wd / 2) + (py >> 1)) * (wd >> 1) + (px >> 1);
       T* const dst = Op + prow * (4 * C) + ((py & 1) * 2 + (px & 1)) * C;
       int oLn = MlpResSmem::kLn;
       asm volatile("" : "+s"(oLn));
@@ -335,44 +333,16 @@ __global__ void __launch_bounds__(512, 1) fused_mlp_res_kernel(const MlpArgs a) 
             const int n = 32 * o + 8 * (q + d) + 4 * lh;
             const f32x4 wv = *(const f32x4*)(sLw + n);
             const f32x4 cv = *(const f32x4*)(sLw + 96 + n);
-            t4 o4;
+            vec4<T> o4;
 #pragma unroll
             for (int e = 0; e < 4; ++e) o4[e] = from_f<T>(fmaf(fmaf(acc2[o][4 * (q + d) + e], rstd, nmr), wv[e], cv[e]));
             pk[d] = __builtin_bit_cast(uint2, o4);
           }
-          auto sx = __builtin_amdgcn_permlane32_swap(pk[0].x, pk[1].x, false, false);
-          auto sy = __builtin_amdgcn_permlane32_swap(pk[0].y, pk[1].y, false, false);
-          const u32x4 w = {sx[0], sy[0], sx[1], sy[1]};
+          const u32x4 w = halves_to_piece(pk);
           const int n16 = 32 * o + 8 * q + 8 * lh;
           if (m < a.M) *(u32x4*)(dst + n16) = w;
         }
-    } else
-#pragma unroll
-    for (int o = 0; o < NO; ++o)
-#pragma unroll
-      for (int q = 0; q < 4; q += 2) {
-        uint2 pk[2];
-        const u32x4 rw = rres[o][q >> 1];
-        const auto rx = __builtin_amdgcn_permlane32_swap(rw[0], rw[2], false, false);
-        const auto ry = __builtin_amdgcn_permlane32_swap(rw[1], rw[3], false, false);
-        const t4 rr[2] = {__builtin_bit_cast(t4, uint2{rx[0], ry[0]}), __builtin_bit_cast(t4, uint2{rx[1], ry[1]})};
-#pragma unroll
-        for (int d = 0; d < 2; ++d) {
-          const int n = 32 * o + 8 * (q + d) + 4 * lh;
-          const f32x4 bv = *(const f32x4*)(sB2t + n);
-          const f32x4 gv = *(const f32x4*)(sGt + n);
-          t4 o4;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o4[e] = from_f<T>(fmaf(acc2[o][4 * (q + d) + e] + bv[e], gv[e], to_f(rr[d][e])));
-          pk[d] = __builtin_bit_cast(uint2, o4);
-        }
-        // vdst = piece q, src = piece q+1: lanes 32-63 of pk[0] <-> lanes 0-31 of pk[1]
-        auto sx = __builtin_amdgcn_permlane32_swap(pk[0].x, pk[1].x, false, false);
-        auto sy = __builtin_amdgcn_permlane32_swap(pk[0].y, pk[1].y, false, false);
-        const u32x4 w = {sx[0], sy[0], sx[1], sy[1]};
-        const int n16 = 32 * o + 8 * q + 8 * lh;           // lanes 0-31: channels 8q .. 8q+7, lanes 32-63: 8q+8 .. 8q+15
-        if (m < a.M && (!(GCV_MLP_ABLATE & 8) || w[0] == 0x12345u)) *(u32x4*)(Op + m * C + n16) = w;
-      }
+    }
     if (titer == 2) GCV_STAMP(6);
 #if GCV_MLP_STAMPS
     if (titer == 2 && blockIdx.x < 64 && threadIdx.x == 0) gcv_mlp_stamps[blockIdx.x * 16 + 9] = __builtin_amdgcn_s_memrealtime();

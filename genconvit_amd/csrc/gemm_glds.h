@@ -17,7 +17,7 @@
 // K has no tail by construction.  Epilogue as in gemm.h (tokens on lanes, LDS-staged coalesced
 // stores); the layer-scale residual is added in registers before staging so the stage stays 16-bit.
 #pragma once
-#include "gemm.h"
+#include "mlp_parts.h"
 
 namespace gcv {
 
@@ -145,8 +145,7 @@ __global__ void __launch_bounds__(256, 2) gemm_glds_kernel(const GemmArgs g) {
   // the residual rows of the tile (EPI_RESID: 24 independent 8-byte loads per lane) are issued here as well, ahead of every
   // DMA: they land under the K loop instead of costing the epilogue a round trip to HBM (48 registers held until then; the
   // kernel runs two workgroups per CU at K >= 512, where this epilogue is used, so 256 are available)
-  typedef T t4 __attribute__((ext_vector_type(4)));
-  t4 rres[EPI == EPI_RESID ? MI : 1][EPI == EPI_RESID ? NI : 1][4];
+  vec4<T> rres[EPI == EPI_RESID ? MI : 1][EPI == EPI_RESID ? NI : 1][4];
   auto load_resid = [&]() {
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
@@ -156,7 +155,7 @@ __global__ void __launch_bounds__(256, 2) gemm_glds_kernel(const GemmArgs g) {
       for (int j = 0; j < NI; ++j)
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-          rres[i][j][q] = *(const t4*)((const T*)g.resid + mm * g.ldc + n0 + wn0 + j * 32 + 8 * q + 4 * lh);
+          rres[i][j][q] = *(const vec4<T>*)((const T*)g.resid + mm * g.ldc + n0 + wn0 + j * 32 + 8 * q + 4 * lh);
     }
   };
   // (the 64-byte-row ring runs three workgroups per CU, 168 registers each: there the loads stay in the epilogue)
@@ -170,14 +169,13 @@ __global__ void __launch_bounds__(256, 2) gemm_glds_kernel(const GemmArgs g) {
   const int n_steady = nkt - (S - 2) > 0 ? nkt - (S - 2) : 0;
   for (int kt = 0; kt < n_steady; ++kt) {
     // my DMAs for stage kt have landed once at most (S-2) younger stages (QPW each) are outstanding
-    // (one asm statement so no LDS access can be scheduled between the wait and the barrier)
-    asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"((S - 2) * QPW) : "memory");   // stage kt landed everywhere; all left kt-1
+    GCV_WAIT_BARRIER((S - 2) * QPW);                                    // stage kt landed everywhere; all left kt-1
     if (kt == 0) GLDS_STAMP(1);
     if (!(GCV_GLDS_ABLATE & 2) && kt + S - 1 < nkt) issue(kt + S - 1); // refill the buffer stage kt-1 used
     if (!(GCV_GLDS_ABLATE & 1)) compute(kt);
   }
   for (int kt = n_steady; kt < nkt; ++kt) {  // drain: fewer stages outstanding, wait for all of them
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+    GCV_WAIT_BARRIER(0);
     if (!(GCV_GLDS_ABLATE & 1)) compute(kt);
   }
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // all waves done reading the ring before it is reused
@@ -212,12 +210,12 @@ __global__ void __launch_bounds__(256, 2) gemm_glds_kernel(const GemmArgs g) {
       for (int i = 0; i < MI; ++i) {
         const int ml = wm0 + i * 32 + lr;
         if (EPI == EPI_RESID && !(GCV_GLDS_ABLATE & 4)) {
-          const t4 r = rres[i][j][q];
+          const vec4<T> r = rres[i][j][q];
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[i][e] = fmaf(v[i][e], gv[e], to_f(r[e]));
         }
-        t4 o = {from_f<T>(v[i][0]), from_f<T>(v[i][1]), from_f<T>(v[i][2]), from_f<T>(v[i][3])};
-        *(t4*)(sC + ml * SROW + (nl >> 1)) = o;
+        vec4<T> o = {from_f<T>(v[i][0]), from_f<T>(v[i][1]), from_f<T>(v[i][2]), from_f<T>(v[i][3])};
+        *(vec4<T>*)(sC + ml * SROW + (nl >> 1)) = o;
       }
     }
   }

@@ -26,7 +26,7 @@
 #pragma once
 #include <type_traits>
 
-#include "gemm.h"
+#include "mlp_parts.h"
 
 namespace gcv {
 
@@ -80,9 +80,6 @@ template <int C, int NW, int D> struct XsPw1Smem {
   static constexpr int bytes = kBias + 4 * C * 4;
 };
 
-#define GCV_XS_WAIT(N) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory")
-
-
 // grid = (ceil(M / (32 NW)), nsplit): workgroup (bx, by) owns tokens [32 NW bx, +32 NW) and hidden chunks
 // [by * nch_split, +nch_split) of the 4C/32
 template <typename T, int C, int NW, int D>
@@ -111,7 +108,8 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) xs_pw1_kernel(const MlpPairAr
   const int nch = (NKC - g0) < nch_split ? (NKC - g0) : nch_split;
 
   // ---- x_ln fragments: k-step p, lane (token lr, half lh) holds k = 16p + 8lh .. +7.  Issued by hand so that they stay
-  // in flight under the ring prologue (hipcc would wait vmcnt(0) for an ordinary load before the first DMA)
+  // in flight under the ring prologue (hipcc would wait vmcnt(0) for an ordinary load before the first DMA).  (The same
+  // loop stands in xs_mlp_kernel: a shared __forceinline__ helper reordered this kernel's scalar prologue.)
   u32x4 xf[KP];
   {
     const T* xp = (const T*)a.X + mc * C + 8 * lh;
@@ -178,21 +176,16 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) xs_pw1_kernel(const MlpPairAr
   };
   auto gelu_b = [&]() { GeluH16::horner<4, 5, 2>(gst); };  // Horner levels 5 .. 2
   // max(x, 0) - h -> 16-bit -> one 1 KB half of the block.  Lane (token, lh) holds channels 8q + 4lh + e; one
-  // v_permlane32_swap per dword of a (q, q+1) pair gives lanes 0-31 the 16 bytes of piece q and lanes 32-63 those of
-  // piece q+1, i.e. the wave stores [kq][token][8] in lane order.
+  // halves_to_piece of a (q, q+1) pair gives lanes 0-31 the 16 bytes of piece q and lanes 32-63 those of piece q+1, i.e.
+  // the wave stores [kq][token][8] in lane order.
   auto gelu_c = [&](const f32x16& acc, int half, int kc) {
     uint32_t hw[4];
     GeluH16::horner<4, 1, 0>(gst);                         // Horner levels 1, 0
     GeluH16::finish_frag<T, 4>(gx, gst, hw);
     const uint2 pk[2] = {uint2{hw[0], hw[1]}, uint2{hw[2], hw[3]}};
     u32x4 w;
-    if (!(GCV_XS_ABLATE & 32)) {
-      const auto sx = __builtin_amdgcn_permlane32_swap(pk[0].x, pk[1].x, false, false);
-      const auto sy = __builtin_amdgcn_permlane32_swap(pk[0].y, pk[1].y, false, false);
-      w = (u32x4){sx[0], sy[0], sx[1], sy[1]};
-    } else {
-      w = (u32x4){pk[0].x, pk[0].y, pk[1].x, pk[1].y};
-    }
+    if (!(GCV_XS_ABLATE & 32)) w = halves_to_piece(pk);
+    else w = (u32x4){pk[0].x, pk[0].y, pk[1].x, pk[1].y};
     if (GCV_XS_ABLATE & 64) asm volatile("" ::"v"(w));      // keeps the whole GELU alive without the store
     else if (!(GCV_XS_ABLATE & 4) || w[0] == 0x12345u)
       __builtin_amdgcn_raw_buffer_store_b128(w, rsh, hbase + (unsigned)kc * 2048u + (unsigned)half * 1024u, 0, 0);
@@ -204,7 +197,7 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) xs_pw1_kernel(const MlpPairAr
 #pragma unroll
     for (int i = 0; i < 4; ++i) wf[i] = *(const u32x4*)(sw + (p0 + i) * 1024);
   };
-  auto read_bias = [&](f32x16& acc, int kc) {
+  auto read_bias = [&](f32x16& acc, int kc) {              // (as in xs_mlp_kernel's step; see there why not shared)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const f32x4 bv = *(const f32x4*)(sb + kc * 32 + 8 * q);
@@ -269,7 +262,7 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) xs_pw1_kernel(const MlpPairAr
   // slots of kc-2 and kc-1 are free; both needed chunks have landed when at most the 2 * PPW pieces of kc+2, kc+3 are
   // outstanding (the stores of the previous pair are younger still: the count is conservative by them)
   constexpr int WAITP = 2 * PPW;
-  GCV_XS_WAIT(WAITP);
+  GCV_WAIT_BARRIER(WAITP);
 #pragma unroll
   for (int p = 0; p < KP; ++p) asm volatile("" : "+v"(xf[p]));   // no use of xf may move above the wait
   issue();
@@ -279,7 +272,7 @@ __global__ void __launch_bounds__(NW * 64, NW / 4) xs_pw1_kernel(const MlpPairAr
 #pragma unroll 1
   for (int kc = 2; kc < nch; kc += 2) {
     if (kc >= 8 && kc < 16) XS_STAMP(2 * kc);
-    GCV_XS_WAIT(WAITP);
+    GCV_WAIT_BARRIER(WAITP);
     if (kc >= 8 && kc < 16) XS_STAMP(2 * kc + 1);
     if (!(GCV_XS_ABLATE & 2)) { issue(); issue(); }
     chunk(accB, accA, kc, std::true_type{});
@@ -330,7 +323,6 @@ __global__ void __launch_bounds__(512, 2) pw2f_kernel(const MlpPairArgs a) {
   constexpr int NPC = STAGE / 1024;                        // 40 / 28 pieces per stage
   constexpr int PPW = (NPC + 7) / 8;                       // 5 / 4 (BN = 192: waves 4-7 repeat the last piece)
   constexpr int WAITN = (D - 2) * PPW;
-  typedef T t4 __attribute__((ext_vector_type(4)));
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -436,9 +428,8 @@ __global__ void __launch_bounds__(512, 2) pw2f_kernel(const MlpPairArgs a) {
     constexpr int r = decltype(rc)::value;
     constexpr int i = r / (2 * NI), j = (r >> 1) % NI, pr = r & 1;
     const u32x4 rw = *(const u32x4*)(sres + (r % RD) * 1024 + lane * 16);
-    const auto rx = __builtin_amdgcn_permlane32_swap(rw[0], rw[2], false, false);
-    const auto ry = __builtin_amdgcn_permlane32_swap(rw[1], rw[3], false, false);
-    const t4 rq[2] = {__builtin_bit_cast(t4, uint2{rx[0], ry[0]}), __builtin_bit_cast(t4, uint2{rx[1], ry[1]})};
+    vec4<T> rq[2];
+    piece_to_halves<T>(rw, rq);
 #pragma unroll
     for (int d = 0; d < 2; ++d)
 #pragma unroll
@@ -505,7 +496,7 @@ __global__ void __launch_bounds__(512, 2) pw2f_kernel(const MlpPairArgs a) {
     constexpr int kc = decltype(kcc)::value;
     constexpr int lo = kc - (D - 2) > 0 ? kc - (D - 2) : 0, hi = kc < NPR ? kc : NPR;   // younger steps [lo, hi) issued a piece
     constexpr int WAITR = (D - 2) * PPW + (hi > lo ? hi - lo : 0);
-    GCV_XS_WAIT(WAITR);
+    GCV_WAIT_BARRIER(WAITR);
     if constexpr (kc >= RD) take_res(std::integral_constant<int, kc - RD>{});
     if constexpr (kc < NPR) issue_res(kc);
     __builtin_amdgcn_sched_barrier(0);
@@ -514,14 +505,14 @@ __global__ void __launch_bounds__(512, 2) pw2f_kernel(const MlpPairArgs a) {
 #pragma unroll 1
   for (int kc = NPR + RD; kc < NSTEADY; ++kc) {
     if (kc >= 32 && kc < 40) P2_STAMP(4 * (kc - 32));     // (diagnostic builds: steps 32 .. 39 are behind the trickle)
-    GCV_XS_WAIT(WAITN);
+    GCV_WAIT_BARRIER(WAITN);
     if (kc >= 32 && kc < 40) { P2_STAMP(4 * (kc - 32) + 1); P2_STAMP(4 * (kc - 32) + 2); }
     compute(std::true_type{});
     if (kc >= 32 && kc < 40) P2_STAMP(4 * (kc - 32) + 3);
   }
 #pragma unroll
   for (int kc = NSTEADY; kc < NKC; ++kc) {                 // drain: nothing left to issue
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+    GCV_WAIT_BARRIER(0);
     compute(std::false_type{});
   }
 
@@ -540,14 +531,12 @@ __global__ void __launch_bounds__(512, 2) pw2f_kernel(const MlpPairArgs a) {
         uint2 pk[2];
 #pragma unroll
         for (int d = 0; d < 2; ++d) {
-          t4 o4;
+          vec4<T> o4;
 #pragma unroll
           for (int e = 0; e < 4; ++e) o4[e] = from_f<T>(acc[i][j][4 * (2 * pr + d) + e]);
           pk[d] = __builtin_bit_cast(uint2, o4);
         }
-        const auto sx = __builtin_amdgcn_permlane32_swap(pk[0].x, pk[1].x, false, false);
-        const auto sy = __builtin_amdgcn_permlane32_swap(pk[0].y, pk[1].y, false, false);
-        const u32x4 w = {sx[0], sy[0], sx[1], sy[1]};
+        const u32x4 w = halves_to_piece(pk);               // (in front of the branch: all lanes take part in the exchange)
         if (mm < a.M) *(u32x4*)(Op + mm * C + ncol0 + 32 * j + 16 * pr + 8 * lh) = w;
       }
   }

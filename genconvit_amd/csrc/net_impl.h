@@ -772,7 +772,7 @@ template <typename T> struct NetImpl : NetBase {
         }
         // the last block of stages 0..2 may apply the stage boundary's LayerNorm2d + space-to-depth in its epilogue and write
         // the down-sampling GEMM's operand (into Hd: Y is still being read as x_ln); the residual stream then ends there
-        LnpSpec l;
+        LnpArgs l;
         const bool fuse = j == A.depths[i] - 1 && i < 3 && lnp_plan(l, k.mlp.kind, C, M, nseg, segn, h, wd);
         if (fuse) { l.w = w.down[i].ln_w; l.b = w.down[i].ln_b; l.eps = 1e-6f; }
         GCV_TRY(launch_cnx_mlp<T>(*this, k.mlp, C, Y, Xc, fuse ? Hd : Xn, Hd, (int)M, fuse ? &l : nullptr, cur));

@@ -1,4 +1,4 @@
-// Fused ConvNeXt MLP for the narrow stages (C = 96, 192), 16-bit storage, x-stationary with an LDS-DMA weight ring:
+// Fused ConvNeXt MLP for the second stage (C = 192), 16-bit storage, x-stationary with an LDS-DMA weight ring:
 //     out = resid + gamma * ( W2 . GELU( W1 . x_ln + b1 ) + b2 )            (timm ConvNeXtBlock; call sites
 //     model/genconvit_ed.py:82-83, model/genconvit_vae.py:111-112 of the reference)
 //
@@ -6,7 +6,7 @@
 // in registers (C/4 VGPRs), its 32 x C output tile is C/32 accumulators (C/2 VGPRs), and the 4C hidden channels are walked
 // in chunks of 32.  A chunk's weights are ONE contiguous record, packed at load time in the order the fragments are read
 // (pack_xs_mlp): [W1 rows 32kc .. +31 as C/16 A fragments | W2[:, chunk] as 2 x C/32 A fragments, hidden axis permuted for
-// the accumulator-as-operand hand-off], 12 KB (C = 96) / 24 KB (C = 192).  Records stream through a ring of D slots by
+// the accumulator-as-operand hand-off], 24 KB.  Records stream through a ring of D slots by
 // LDS-DMA (whole lines, no swizzle: a fragment read is `base + immediate`, lane-linear) and the walk simply continues into
 // the next pass, so the ring never drains.
 //
@@ -20,12 +20,13 @@
 // MFMAs cost ~4-5 issue cycles each however many waves share the SIMD (profiles/micro/mfma_valu_overlap.hip), so what
 // matters is that no wave ever sits in a vector-only or a matrix-only phase.
 //
-// What it replaces: fused_mlp_kernel (C = 192: register-staged 96-wide chunks, __syncthreads per chunk, 261 us at 256
-// images) and fused_mlp_res_kernel (C = 96: weights resident in LDS).
+// What it replaced: the C = 192 form of fused_mlp_kernel (register-staged 96-wide chunks, __syncthreads per chunk, 261 us
+// at 256 images).  (At C = 96 this scheme pays a barrier and a ring refill per twelve MFMAs and loses to the LDS-resident
+// fused_mlp_res_kernel; that configuration is gone.)
 #pragma once
 #include <type_traits>
 
-#include "gemm.h"
+#include "mlp_parts.h"
 
 namespace gcv {
 
@@ -38,16 +39,7 @@ struct XsMlpArgs {
   const void* resid;    // (M, C) block input (may alias out)
   void* out;            // (M, C)
   int M;
-  // Optional (last block of a stage): the stage boundary's LayerNorm2d + 2x2 space-to-depth in the epilogue, as in
-  // MlpArgs (fused_mlp.h): `out` is then the patchified (M/4, 4C) operand of the down-sampling GEMM
-  const float* lnp_w = nullptr;
-  const float* lnp_b = nullptr;
-  float lnp_eps = 0.0f;
-  int lnp_nseg = 0;
-  int lnp_tok0[4] = {0, 0, 0, 0};
-  int lnp_hw[4] = {1, 1, 1, 1};
-  int lnp_wd[4] = {1, 1, 1, 1};
-  int lnp_out0[4] = {0, 0, 0, 0};
+  LnpArgs lnp;          // LN-patchify epilogue of the last block of the stage (mlp_parts.h)
 };
 
 // W1 (4C, C) and W2 (C, 4C) row-major of type S on the device -> records of T.  Fragment f of a record is 512 elements
@@ -75,26 +67,23 @@ __global__ void __launch_bounds__(256) pack_xs_mlp_kernel(const T* __restrict__ 
 }
 
 template <int C> struct XsMlpCfg {
-  static constexpr int KP1 = C / 16, NO = C / 32, NM = KP1 + 2 * NO;    // MFMAs (= fragments) per chunk: 12 / 24
+  static_assert(C == 192, "the x-stationary MLP is built for the second ConvNeXt stage");
+  static constexpr int KP1 = C / 16, NO = C / 32, NM = KP1 + 2 * NO;    // MFMAs (= fragments) per chunk: 24
   static constexpr int REC = NM * 1024;                                 // record bytes
-  static constexpr int NKC = 4 * C / 32;                                // chunks: 12 / 24
-  static constexpr int D = C == 96 ? 10 : 6;                            // ring slots (120 KB / 144 KB)
+  static constexpr int NKC = 4 * C / 32;                                // chunks: 24
+  static constexpr int D = 6;                                           // ring slots (144 KB)
   static constexpr int PPW = 3;                                         // DMA pieces per loader wave and chunk
-  static constexpr int NLW = NM / PPW;                                  // loader waves: 4 / 8
+  static constexpr int NLW = NM / PPW;                                  // loader waves: 8
   static constexpr int kB1 = D * REC;                                   // b1 (4C floats)
   static constexpr int kBG = kB1 + 4 * C * 4;                           // b2 | gamma (2C floats)
   static constexpr int kLn = kBG + 2 * C * 4;                           // LNP variant: LayerNorm weight | bias (2C floats)
   static constexpr int bytes = kLn + 2 * C * 4;
-  static constexpr int NSB = NM / 4;                                    // sub-blocks of four MFMAs per step: 3 / 6
+  static constexpr int NSB = NM / 4;                                    // sub-blocks of four MFMAs per step: 6
 };
-
-
-#define GCV_XM_WAIT(N) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory")
 
 template <typename T, int C, bool LNP = false>
 __global__ void __launch_bounds__(512, 2) xs_mlp_kernel(const XsMlpArgs a, const int npass) {
   static_assert(sizeof(T) == 2, "16-bit storage");
-  static_assert(C == 96 || C == 192, "narrow ConvNeXt stages");
   typedef XsMlpCfg<C> CF;
   constexpr int KP1 = CF::KP1, NO = CF::NO, NM = CF::NM, REC = CF::REC, NKC = CF::NKC, D = CF::D, PPW = CF::PPW;
   constexpr int NLW = CF::NLW, NSB = CF::NSB;
@@ -103,7 +92,6 @@ __global__ void __launch_bounds__(512, 2) xs_mlp_kernel(const XsMlpArgs a, const
   // take chunks n+2 and n+3; the only DMAs outstanding before that refill are those of chunks n and n+1, issued one pair
   // earlier (~6000 cycles): vmcnt(0).  4 live + 2 incoming = 6 slots.
   static_assert(D >= 6 && NKC % 2 == 0, "ring: four live chunks and two incoming; passes are whole pairs of steps");
-  typedef T t4 __attribute__((ext_vector_type(4)));
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -121,7 +109,7 @@ __global__ void __launch_bounds__(512, 2) xs_mlp_kernel(const XsMlpArgs a, const
     for (int i = tid; i < 6 * C; i += 512) sf[i] = i < 4 * C ? a.b1[i] : (i < 5 * C ? a.b2[i - 4 * C] : a.gamma[i - 5 * C]);
     if (LNP) {
       float* sl = reinterpret_cast<float*>(smem + CF::kLn);
-      for (int i = tid; i < 2 * C; i += 512) sl[i] = i < C ? a.lnp_w[i] : a.lnp_b[i - C];
+      for (int i = tid; i < 2 * C; i += 512) sl[i] = i < C ? a.lnp.w[i] : a.lnp.b[i - C];
     }
   }
   __syncthreads();
@@ -156,6 +144,8 @@ __global__ void __launch_bounds__(512, 2) xs_mlp_kernel(const XsMlpArgs a, const
   int slot1 = 0;                                           // slot of the chunk whose W1 part this step reads
   auto slot_dec = [&](int s, int k) { return s - k < 0 ? s - k + D : s - k; };
 
+  // (hand-issued as in xs_pw1_kernel; a shared __forceinline__ helper reproduced this kernel but reordered that one's
+  // scalar prologue, so both keep the loop)
   u32x4 xf[KP1];
   auto load_x = [&](int64_t mc) {
     const T* xp = Xp + mc * C + 8 * lh;
@@ -227,12 +217,13 @@ __global__ void __launch_bounds__(512, 2) xs_mlp_kernel(const XsMlpArgs a, const
       constexpr int RING = decltype(ringc)::value;                      // 0: drain step, 1: head of a pair, 2: its second step
       constexpr int I0 = G1 ? 0 : KP1, I1 = G2 ? NM : KP1;              // MFMA ops of this step
       if (RING == 1) {
-        GCV_XM_WAIT(0);
+        GCV_WAIT_BARRIER(0);
         if (!(GCV_XM_ABLATE & 2)) { issue(); issue(); }
       }
       const unsigned char* s1 = smem + slot1 * REC + lane16;
       const unsigned char* s2 = smem + slot_dec(slot1, 2) * REC + lane16;
-      if (G1) {
+      if (G1) {   // accumulator := bias.  (A helper shared with xs_pw1_kernel and fused_mlp_res_kernel rescheduled this
+                  // kernel and that one, which also came out at 223 VGPRs instead of 232: written out in all three.)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const f32x4 bv = *(const f32x4*)(sb1 + kc * 32 + 8 * q);
@@ -317,63 +308,65 @@ __global__ void __launch_bounds__(512, 2) xs_mlp_kernel(const XsMlpArgs a, const
     slot1 = slot_dec(slot1, 1);
     if (it == 0) XM_STAMP(4);
 
-    // ---- epilogue: (acc2 + b2) * gamma + resid -> 16-bit, 16-byte pieces (v_permlane32_swap converts between a row's
-    // 16-byte piece and the accumulator's (8q + 4lh) halves, it is its own inverse)
+    // ---- epilogue: (acc2 + b2) * gamma + resid -> 16-bit, 16-byte pieces (mlp_parts.h: piece_to_halves / halves_to_piece
+    // convert between a row's 16-byte piece and the accumulator's (8q + 4lh) halves).  It is fused_mlp_res_kernel's but for
+    // the 4 lh in the pointers; shared __forceinline__ functions for this loop, for the patch position and for the
+    // normalising store were tried and did not reproduce this kernel's code (loop: the plain variant's main loop is
+    // scheduled differently; patch position: +2 spilled dwords in the LNP variant), so they are written out here.
     {
       // b2 | gamma behind b1, from the lane's live b1 pointer (+ 4 lh).  (A pointer laundered through an empty asm comes
       // back generic and turns these LDS reads into flat loads.)
       const float* const sB2 = sb1 + 4 * C;
       const float* const sG = sb1 + 5 * C;
-      if constexpr (LNP) {
-        // out = LayerNorm2d(resid + gamma * (acc2 + b2)) at the patch position of token m (see fused_mlp_res.h)
-        float s1 = 0.0f, s2 = 0.0f;
+      // LNP: the values go back into the accumulators instead, with their sum and sum of squares
+      float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
-        for (int o = 0; o < NO; ++o)
+      for (int o = 0; o < NO; ++o)
 #pragma unroll
-          for (int pr = 0; pr < 2; ++pr) {
-            const u32x4 rw = rres[2 * o + pr];
-            const auto rx = __builtin_amdgcn_permlane32_swap(rw[0], rw[2], false, false);
-            const auto ry = __builtin_amdgcn_permlane32_swap(rw[1], rw[3], false, false);
-            const t4 rq[2] = {__builtin_bit_cast(t4, uint2{rx[0], ry[0]}), __builtin_bit_cast(t4, uint2{rx[1], ry[1]})};
+        for (int pr = 0; pr < 2; ++pr) {
+          vec4<T> rq[2];
+          piece_to_halves<T>(rres[2 * o + pr], rq);
+          uint2 pk[2];
 #pragma unroll
-            for (int d = 0; d < 2; ++d) {
-              const int q = 2 * pr + d;
-              const int n = 32 * o + 8 * q;                 // (+ 4 lh: in the pointer)
-              const f32x4 bv = *(const f32x4*)(sB2 + n);
-              const f32x4 gv = *(const f32x4*)(sG + n);
+          for (int d = 0; d < 2; ++d) {
+            const int q = 2 * pr + d;
+            const int n = 32 * o + 8 * q;                 // (+ 4 lh: in the pointer)
+            const f32x4 bv = *(const f32x4*)(sB2 + n);
+            const f32x4 gv = *(const f32x4*)(sG + n);
+            vec4<T> o4;
 #pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                const float v = fmaf(acc2[o][4 * q + e] + bv[e], gv[e], to_f(rq[d][e]));
+            for (int e = 0; e < 4; ++e) {
+              const float v = fmaf(acc2[o][4 * q + e] + bv[e], gv[e], to_f(rq[d][e]));
+              if constexpr (LNP) {
                 acc2[o][4 * q + e] = v;
                 s1 += v;
                 s2 = fmaf(v, v, s2);
+              } else {
+                o4[e] = from_f<T>(v);
               }
             }
+            if constexpr (!LNP) pk[d] = __builtin_bit_cast(uint2, o4);
           }
-        s1 += __shfl_xor(s1, 32);
-        s2 += __shfl_xor(s2, 32);
-        const float mean = s1 * (1.0f / C);
-        // one pass cancels once the channels share an offset (common.h, kLnRecentre): the squares of the centred values
-        // are summed as well, without a branch (one more live register under a branch spills past the scratch budget),
-        // and stand in for E[x^2] - mean^2 where that is below E[x^2] / 16
-        float sc = 0.0f;
-#pragma unroll
-        for (int o = 0; o < NO; ++o)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) sc = fmaf(acc2[o][e] - mean, acc2[o][e] - mean, sc);
-        sc += __shfl_xor(sc, 32);
-        const float var1 = fmaf(-mean, mean, s2 * (1.0f / C));
-        const float var = var1 < s2 * (kLnRecentre / C) ? sc * (1.0f / C) : var1;
-        const float rstd = __builtin_amdgcn_rsqf(fmaxf(var, 0.0f) + a.lnp_eps);
-        const float nmr = -mean * rstd;
+          if constexpr (!LNP) {
+            const u32x4 w = halves_to_piece(pk);
+            if (m < a.M) *(u32x4*)(Op + m * C + 32 * o + 16 * pr + 8 * lh) = w;
+          }
+        }
+      if constexpr (LNP) {
+        // out = LayerNorm2d(resid + gamma * (acc2 + b2)) at the patch position of token m (see fused_mlp_res.h)
+        // the centred squares are summed without a branch: one more live register under a branch spills past the scratch
+        // budget
+        float rstd, nmr;
+        lnp_stats<C, false>(acc2, s1, s2, a.lnp.eps, rstd, nmr);
+        // patch position of this lane's token: segment, image, (y, x) -> patch row and the quarter of its 4C columns
         int sg = 0;
 #pragma unroll
-        for (int t = 1; t < 4; ++t) sg += (t < a.lnp_nseg && (int)mc >= a.lnp_tok0[t]) ? 1 : 0;
-        const int local = (int)mc - a.lnp_tok0[sg];
-        const int hw = a.lnp_hw[sg], wd = a.lnp_wd[sg];
+        for (int t = 1; t < 4; ++t) sg += (t < a.lnp.nseg && (int)mc >= a.lnp.tok0[t]) ? 1 : 0;
+        const int local = (int)mc - a.lnp.tok0[sg];
+        const int hw = a.lnp.hw[sg], wd = a.lnp.wd[sg];
         const int img = local / hw, rem = local - img * hw;
         const int py = rem / wd, px = rem - py * wd;
-        const int64_t prow = (int64_t)a.lnp_out0[sg] + ((int64_t)img * (hw / wd / 2) + (py >> 1)) * (wd >> 1) + (px >> 1);
+        const int64_t prow = (int64_t)a.lnp.out0[sg] + ((int64_t)img * (hw / wd / 2) + (py >> 1)) * (wd >> 1) + (px >> 1);
         T* const dst = Op + prow * (4 * C) + ((py & 1) * 2 + (px & 1)) * C;
         const float* const sLw = sb1 + 6 * C;              // LayerNorm weight | bias behind gamma
 #pragma unroll
@@ -387,42 +380,15 @@ __global__ void __launch_bounds__(512, 2) xs_mlp_kernel(const XsMlpArgs a, const
               const int n = 32 * o + 8 * q;                 // (+ 4 lh: in the pointer)
               const f32x4 wv = *(const f32x4*)(sLw + n);
               const f32x4 cv = *(const f32x4*)(sLw + C + n);
-              t4 o4;
+              vec4<T> o4;
 #pragma unroll
               for (int e = 0; e < 4; ++e) o4[e] = from_f<T>(fmaf(fmaf(acc2[o][4 * q + e], rstd, nmr), wv[e], cv[e]));
               pk[d] = __builtin_bit_cast(uint2, o4);
             }
-            const auto sx = __builtin_amdgcn_permlane32_swap(pk[0].x, pk[1].x, false, false);
-            const auto sy = __builtin_amdgcn_permlane32_swap(pk[0].y, pk[1].y, false, false);
-            const u32x4 w = {sx[0], sy[0], sx[1], sy[1]};
+            const u32x4 w = halves_to_piece(pk);
             if (m < a.M) *(u32x4*)(dst + 32 * o + 16 * pr + 8 * lh) = w;
           }
-      } else
-#pragma unroll
-      for (int o = 0; o < NO; ++o)
-#pragma unroll
-        for (int pr = 0; pr < 2; ++pr) {
-          const u32x4 rw = rres[2 * o + pr];
-          const auto rx = __builtin_amdgcn_permlane32_swap(rw[0], rw[2], false, false);
-          const auto ry = __builtin_amdgcn_permlane32_swap(rw[1], rw[3], false, false);
-          const t4 rq[2] = {__builtin_bit_cast(t4, uint2{rx[0], ry[0]}), __builtin_bit_cast(t4, uint2{rx[1], ry[1]})};
-          uint2 pk[2];
-#pragma unroll
-          for (int d = 0; d < 2; ++d) {
-            const int q = 2 * pr + d;
-            const int n = 32 * o + 8 * q;                 // (+ 4 lh: in the pointer)
-            const f32x4 bv = *(const f32x4*)(sB2 + n);
-            const f32x4 gv = *(const f32x4*)(sG + n);
-            t4 o4;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o4[e] = from_f<T>(fmaf(acc2[o][4 * q + e] + bv[e], gv[e], to_f(rq[d][e])));
-            pk[d] = __builtin_bit_cast(uint2, o4);
-          }
-          const auto sx = __builtin_amdgcn_permlane32_swap(pk[0].x, pk[1].x, false, false);
-          const auto sy = __builtin_amdgcn_permlane32_swap(pk[0].y, pk[1].y, false, false);
-          const u32x4 w = {sx[0], sy[0], sx[1], sy[1]};
-          if (m < a.M) *(u32x4*)(Op + m * C + 32 * o + 16 * pr + 8 * lh) = w;
-        }
+      }
     }
     // next pass's x rows (the wait at the top of the loop covers them)
     if (it + 1 < my_passes) {
@@ -438,9 +404,6 @@ __global__ void __launch_bounds__(512, 2) xs_mlp_kernel(const XsMlpArgs a, const
 template <typename T> int launch_xs_mlp(const XsMlpArgs& a, int C, hipStream_t s);
 // W1 (4C, C) of T and W2 (C, 4C) of S (T or float) on the device -> the packed records
 template <typename T, typename S> int launch_pack_xs_mlp(const T* w1, const S* w2, T* out, int C, hipStream_t s);
-// C = 96 works (and is what the template was first written for) but measured 270 us at 256 images against 215 us for the
-// LDS-resident fused_mlp_res_kernel: twelve steps of 12 MFMAs each pay a barrier and a ring refill per step.  The library
-// runs this kernel at C = 192 only.
 static inline bool xs_mlp_supported(int C) { return C == 192; }
 static inline size_t xs_mlp_packed_elems(int C) { return (size_t)(4 * C / 32) * (size_t)(C / 16 + 2 * (C / 32)) * 512; }
 
