@@ -106,7 +106,14 @@ SIGNATURES = {
                                  c_int, c_int, c_float, c_void_p]),
     "gcv_k_dwconv7_ln2": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p]),
+    "gcv_k_dwconv7_ln_planned": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                         c_int, c_int, c_float, c_int, c_void_p]),
+    "gcv_k_dwconv7_ln2_planned": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                                          c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_int,
+                                          c_void_p]),
     "gcv_dw_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "gcv_dw_plan2": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "gcv_mlp_plan": (c_int, [c_int, c_int, c_int, c_int, c_void_p]),
     "gcv_convnext_res_ok": (c_int, [c_int, c_int]),
     "gcv_k_ln_patchify": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
                                   c_void_p]),
@@ -148,6 +155,11 @@ SIGNATURES = {
     "gcv_k_fused_mlp_lnp": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_int, c_void_p]),
+    "gcv_k_fused_mlp_planned": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_int, c_int, c_void_p]),
+    "gcv_k_fused_mlp_lnp_planned": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "gcv_k_fused_mlp_timed": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
 }

@@ -175,11 +175,12 @@ template <typename T> struct MlpTestRunner {
 // device; both are packed here for the block's kind.  iters == 0: one launch.  iters > 0 (gcv_k_fused_mlp_timed): the
 // weights are packed once, then `iters` launches are timed with HIP events on the stream; ms[0] = average of the whole MLP,
 // ms[1] / ms[2] = pw1 / pw2 of the C = 384 pair (else 0).  lnp (gcv_k_fused_mlp_lnp): the stage boundary's LayerNorm2d +
-// 2x2 space-to-depth in the epilogue, `out` is then the patchified (M/4, 4C) tensor.
+// 2x2 space-to-depth in the epilogue, `out` is then the patchified (M/4, 4C) tensor.  wg_cap (gcv_k_fused_mlp*_planned):
+// the persistent kernels' workgroup limit.
 template <typename T>
 static int k_mlp_dispatch(int C, const void* x, const void* w1, const float* b1, const float* w2_f32, const float* b2,
                           const float* gamma, const void* resid, void* out, int M, hipStream_t s, int iters = 0,
-                          float* ms = nullptr, const LnpArgs* lnp = nullptr) {
+                          float* ms = nullptr, const LnpArgs* lnp = nullptr, int wg_cap = kMlpWgCap) {
   struct Bufs {                                    // freed on every exit path (after the stream has drained)
     hipStream_t s;
     std::vector<void*> p;
@@ -204,7 +205,7 @@ static int k_mlp_dispatch(int C, const void* x, const void* w1, const float* b1,
   GCV_REQUIRE(hidden || w.kind != MlpKind::Pair384, "hipMalloc of the hidden tensor");
   auto launch = [&](const char* only) {
     MlpTestRunner<T> r{s, only};
-    return launch_cnx_mlp<T>(r, w, C, (const T*)x, (const T*)resid, (T*)out, hidden, M, lnp, s);
+    return launch_cnx_mlp<T>(r, w, C, (const T*)x, (const T*)resid, (T*)out, hidden, M, lnp, s, wg_cap);
   };
   // timed(only, &avg): warm-up launch, then `iters` launches between two events
   auto timed = [&](const char* only, float* avg) -> int {
@@ -675,6 +676,27 @@ int gcv_k_dwconv7_ln2(int dtype, const void* x0, void* y0, int nimg0, int H0, in
                                            bdw, lnw, lnb, C, eps, (hipStream_t)s));
 }
 
+int gcv_k_dwconv7_ln_planned(int dtype, const void* x, const float* wdw, const float* bdw, const float* lnw,
+                             const float* lnb, void* y, int nimg, int H, int W, int C, float eps, int plan_nimg,
+                             gcv_stream s) {
+  DISPATCH_DT(dtype, launch_dwconv7_ln<T>((const T*)x, wdw, bdw, lnw, lnb, (T*)y, nimg, H, W, C, eps, (hipStream_t)s,
+                                          plan_nimg));
+}
+
+int gcv_k_dwconv7_ln2_planned(int dtype, const void* x0, void* y0, int nimg0, int H0, int W0, const void* x1, void* y1,
+                              int nimg1, int H1, int W1, const float* wdw, const float* bdw, const float* lnw,
+                              const float* lnb, int C, float eps, int plan_nimg0, int plan_nimg1, gcv_stream s) {
+  DISPATCH_DT(dtype, launch_dwconv7_ln2<T>((const T*)x0, (T*)y0, nimg0, H0, W0, (const T*)x1, (T*)y1, nimg1, H1, W1, wdw,
+                                           bdw, lnw, lnb, C, eps, (hipStream_t)s, plan_nimg0, plan_nimg1));
+}
+
+int gcv_dw_plan2(int dtype, int nimg0, int H0, int W0, int nimg1, int H1, int W1, int C, int* out1) {
+  GCV_REQUIRE(out1, "null out1");
+  GCV_REQUIRE(nimg0 > 0 && H0 > 0 && W0 > 0 && nimg1 > 0 && H1 > 0 && W1 > 0, "dwconv: empty");
+  auto put = [&](bool merged) { out1[0] = merged ? 1 : 0; return 0; };
+  DISPATCH_DT(dtype, put(dw_two_merged<T>(nimg0, H0, W0, nimg1, H1, W1, C, true)));
+}
+
 int gcv_dw_plan(int dtype, int nimg, int H, int W, int C, int aligned, int* out5) {
   GCV_REQUIRE(out5, "null out5");
   DwPlan p;
@@ -925,6 +947,37 @@ int gcv_k_fused_mlp_lnp(int dtype, int C, const void* x, const void* w1, const f
   if (dtype == GCV_F16)
     return k_mlp_dispatch<half_t>(C, x, w1, b1, w2_f32, b2, gamma, resid, out, M, (hipStream_t)s, 0, nullptr, &l);
   return k_mlp_dispatch<bf16_t>(C, x, w1, b1, w2_f32, b2, gamma, resid, out, M, (hipStream_t)s, 0, nullptr, &l);
+}
+
+int gcv_k_fused_mlp_planned(int dtype, int C, const void* x, const void* w1, const float* b1, const float* w2_f32,
+                            const float* b2, const float* gamma, const void* resid, void* out, int M, int wg_cap,
+                            gcv_stream s) {
+  GCV_REQUIRE(dtype == GCV_F16 || dtype == GCV_BF16, "the MLP kernels are built for 16-bit storage");
+  if (dtype == GCV_F16)
+    return k_mlp_dispatch<half_t>(C, x, w1, b1, w2_f32, b2, gamma, resid, out, M, (hipStream_t)s, 0, nullptr, nullptr, wg_cap);
+  return k_mlp_dispatch<bf16_t>(C, x, w1, b1, w2_f32, b2, gamma, resid, out, M, (hipStream_t)s, 0, nullptr, nullptr, wg_cap);
+}
+
+int gcv_k_fused_mlp_lnp_planned(int dtype, int C, const void* x, const void* w1, const float* b1, const float* w2_f32,
+                                const float* b2, const float* gamma, const void* resid, const float* ln_w,
+                                const float* ln_b, float eps, int nseg, const int* tok0, const int* hw, const int* wd,
+                                const int* out0, void* out, int M, int wg_cap, gcv_stream s) {
+  GCV_REQUIRE(dtype == GCV_F16 || dtype == GCV_BF16, "the MLP kernels are built for 16-bit storage");
+  LnpArgs l;
+  GCV_TRY(lnp_from_tables(l, C, M, ln_w, ln_b, eps, nseg, tok0, hw, wd, out0));
+  if (dtype == GCV_F16)
+    return k_mlp_dispatch<half_t>(C, x, w1, b1, w2_f32, b2, gamma, resid, out, M, (hipStream_t)s, 0, nullptr, &l, wg_cap);
+  return k_mlp_dispatch<bf16_t>(C, x, w1, b1, w2_f32, b2, gamma, resid, out, M, (hipStream_t)s, 0, nullptr, &l, wg_cap);
+}
+
+int gcv_mlp_plan(int dtype, int C, int M, int wg_cap, int* out8) {
+  GCV_REQUIRE(out8, "null out8");
+  GCV_REQUIRE(dtype == GCV_F32 || dtype == GCV_F16 || dtype == GCV_BF16, "unknown dtype");
+  MlpPlan p;
+  GCV_TRY(mlp_plan(p, dtype == GCV_F32 ? 4 : 2, C, M, wg_cap));
+  out8[0] = (int)p.kind;
+  for (int i = 0; i < 7; ++i) out8[i + 1] = p.v[i];
+  return 0;
 }
 
 int gcv_k_fused_mlp_timed(int dtype, int C, const void* x, const void* w1, const float* b1, const float* w2_f32,

@@ -89,12 +89,51 @@ static inline bool lnp_plan(LnpArgs& l, MlpKind kind, int C, int64_t M, int nseg
   return even && lnp_supported(kind, C, M);
 }
 
+// What launch_cnx_mlp launches at M tokens, from the launchers' own geometry rules (gcv_mlp_plan; no HIP call).
+// v by kind (include/genconvit_hip.h): Fused96 {LDS-resident kernel?, workgroups, wave tiles, most tiles per wave},
+// Xs192 {passes, workgroups, most passes per workgroup}, Pair384 {pw1 tiles, ns, chunks per workgroup, pw2 BN, D, TB, grid}
+struct MlpPlan {
+  MlpKind kind = MlpKind::Gemm;
+  int v[7] = {0, 0, 0, 0, 0, 0, 0};
+};
+static inline int mlp_plan(MlpPlan& p, size_t tsize, int C, int M, int wg_cap) {
+  GCV_REQUIRE(M > 0 && wg_cap >= 1 && wg_cap <= kMlpWgCap, "MLP plan: M > 0, workgroup cap in [1, 256]");
+  p = MlpPlan{};
+  p.kind = mlp_kind(tsize, C);
+  switch (p.kind) {
+    case MlpKind::Gemm: break;
+    case MlpKind::Fused96: {
+      const int tiles = fused_mlp_wave_tiles(M);
+      if (fused_mlp_res_applies(C, M)) {
+        const int nwg = mlp_persistent_wgs(cdiv(tiles, kMlpResWaves), wg_cap);
+        p.v[0] = 1; p.v[1] = nwg; p.v[2] = tiles; p.v[3] = cdiv(tiles, nwg * kMlpResWaves);
+      } else {
+        p.v[1] = fused_mlp_tile_wgs(M); p.v[2] = tiles; p.v[3] = 1;
+      }
+      break;
+    }
+    case MlpKind::Xs192: {
+      const int npass = xs_mlp_passes(M), nwg = mlp_persistent_wgs(npass, wg_cap);
+      p.v[0] = npass; p.v[1] = nwg; p.v[2] = cdiv(npass, nwg);
+      break;
+    }
+    case MlpKind::Pair384: {
+      const int nkc = 4 * C / 32, ntile = xs_pw1_tiles(M), ns = xs_pw1_pick_split(ntile, nkc);
+      const Pw2fTile t = pw2f_pick(M, C);
+      p.v[0] = ntile; p.v[1] = ns; p.v[2] = nkc / ns; p.v[3] = t.BN; p.v[4] = t.D; p.v[5] = t.TB; p.v[6] = t.grid;
+      break;
+    }
+  }
+  return 0;
+}
+
 // Launches the MLP of w.kind over M tokens of x.  hidden: the (M, 4C) tensor of Gemm, the fragment-major one of Pair384
 // (mlp_pair_hidden_bytes).  lnp (lnp_plan returned true): the LN-patchify epilogue, into `out`.  Launches go through
 // r.run(tag, flops, bytes, f) and r.gemm(tag, GemmArgs, a_mode, epi) on stream s (NetImpl: tagged and profiled).
+// wg_cap: the persistent kernels' workgroup limit; below kMlpWgCap from the kernel test entries only (mlp_parts.h).
 template <typename T, class R>
 int launch_cnx_mlp(R& r, const CnxMlpW<T>& w, int C, const T* x, const T* resid, T* out, T* hidden, int M,
-                   const LnpArgs* lnp, hipStream_t s) {
+                   const LnpArgs* lnp, hipStream_t s, int wg_cap = kMlpWgCap) {
   GCV_REQUIRE(!lnp || lnp_supported(w.kind, C, M), "LN-patchify epilogue of an MLP kind without one");
   if constexpr (sizeof(T) == 2) {
     const double fused_flops = 16.0 * M * C * (double)C, fused_bytes = 3.0 * sizeof(T) * (double)M * C + 16.0 * C * C;
@@ -103,12 +142,12 @@ int launch_cnx_mlp(R& r, const CnxMlpW<T>& w, int C, const T* x, const T* resid,
       case MlpKind::Fused96: {
         MlpArgs a{x, w.w1, w.b1, w.w2c, w.b2, w.gamma, resid, out, M};
         if (lnp) a.lnp = *lnp;
-        return r.run("cnx.fused_mlp", fused_flops, fused_bytes, [&] { return launch_fused_mlp<T>(a, C, s); });
+        return r.run("cnx.fused_mlp", fused_flops, fused_bytes, [&] { return launch_fused_mlp<T>(a, C, s, wg_cap); });
       }
       case MlpKind::Xs192: {
         XsMlpArgs a{x, w.wp, w.b1, w.b2, w.gamma, resid, out, M};
         if (lnp) a.lnp = *lnp;
-        return r.run("cnx.fused_mlp", fused_flops, fused_bytes, [&] { return launch_xs_mlp<T>(a, C, s); });
+        return r.run("cnx.fused_mlp", fused_flops, fused_bytes, [&] { return launch_xs_mlp<T>(a, C, s, wg_cap); });
       }
       case MlpKind::Pair384: {
         MlpPairArgs a{x, w.w1f, w.b1, w.w2f, w.b2, w.gamma, resid, out, hidden, M};

@@ -39,10 +39,14 @@ template <DwKind K, int C_ = 0, int N_ = 0> struct DwShape {
 // 4 x 4 (all four S of Tiny and TinyPair), and maps whose width is not a multiple of 7 (res 160: 5 x 5 at stage 3) or
 // unaligned operands reach Tile.  There is no Tile kernel at C = 1536: a 5- or 6-pixel map there (ConvNeXt-L at res
 // 160 ... 220) is this function's error, which is why cnx_res_ok (net.h) refuses those resolutions before the pass starts.
-// Every (kind, C, NS or S) returned here has a GPU parity case (tests/dwcases.py; tests/test_host_cpu.py checks the set).
+// Every (kind, C, NS or S) returned here has a GPU parity case (tests/dwcases.py; tests/test_host_cpu.py checks the set),
+// and so has every (band kernel, H, rows per band) that a batch of the networks reaches (tests/census.py).
 // Calls f(plan, DwShape) and returns its value, or sets the launcher's error.
-template <typename T, class F> int dw_select(int nimg, int H, int W, int C, bool aligned, F&& f) {
+// plan_nimg > 0 (the kernel-test entries gcv_k_dwconv7_ln*_planned): the kernel and the rows per band are those of a launch
+// of plan_nimg images, the grid covers nimg images; every network launch plans on its own count.
+template <typename T, class F> int dw_select(int nimg, int H, int W, int C, bool aligned, F&& f, int plan_nimg = 0) {
   GCV_REQUIRE(nimg > 0 && H > 0 && W > 0, "dwconv: empty");
+  const int pn = plan_nimg > 0 ? plan_nimg : nimg;
   const int ns = W % 7 == 0 ? W / 7 : 0;
   auto go = [&](auto sh) -> int {
     typedef decltype(sh) S;
@@ -60,7 +64,7 @@ template <typename T, class F> int dw_select(int nimg, int H, int W, int C, bool
       int nb;
       if constexpr (S::kind == DwKind::Pair) {
         p.block = kDwPairThreads;
-        nb = std::max(1, std::min(H, (512 + nimg - 1) / nimg));          // two workgroups per CU
+        nb = std::max(1, std::min(H, (512 + pn - 1) / pn));              // two workgroups per CU
       } else {
         typedef std::conditional_t<S::kind == DwKind::Mfma, DwMfmaLds<T, S::C, S::N>, DwRollLds<T, S::C, S::N>> LY;
         p.block = LY::NT;
@@ -72,8 +76,8 @@ template <typename T, class F> int dw_select(int nimg, int H, int W, int C, bool
         // re-read aprons come from L2)
         const int per_cu = std::max(1, std::min(160 * 1024 / LY::bytes, LY::NT > 512 ? 1 : 2));
         const int nb7 = std::max(1, H / 7);
-        const bool small_launch = nimg * nb7 <= 128;
-        nb = std::max(1, std::min((256 * per_cu + nimg - 1) / nimg, small_launch ? std::max(1, H / 2) : nb7));
+        const bool small_launch = (int64_t)pn * nb7 <= 128;
+        nb = std::max(1, std::min((256 * per_cu + pn - 1) / pn, small_launch ? std::max(1, H / 2) : nb7));
       }
       p.n = ns;
       p.band_rows = cdiv(H, nb);
@@ -85,7 +89,7 @@ template <typename T, class F> int dw_select(int nimg, int H, int W, int C, bool
     switch (C) {
       case 96:
         if constexpr (sizeof(T) == 2)
-          if (ns == 8 && (int64_t)nimg * H >= kDwMfmaMinImageRows) return go(DwShape<DwKind::Mfma, 96, 8>{});
+          if (ns == 8 && (int64_t)pn * H >= kDwMfmaMinImageRows) return go(DwShape<DwKind::Mfma, 96, 8>{});
         if (ns == 8) return go(DwShape<DwKind::Roll, 96, 8>{});
         if (ns == 4) return go(DwShape<DwKind::Roll, 96, 4>{});
         break;
@@ -121,7 +125,7 @@ template <typename T> int dw_plan(DwPlan& p, int nimg, int H, int W, int C, bool
 
 template <typename T>
 int launch_dwconv7_ln(const T* x, const float* wdw, const float* bdw, const float* lnw, const float* lnb, T* y,
-                      int nimg, int H, int W, int C, float eps, hipStream_t s) {
+                      int nimg, int H, int W, int C, float eps, hipStream_t s, int plan_nimg) {
   const bool aligned = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15u) == 0;
   return dw_select<T>(nimg, H, W, C, aligned, [&](const DwPlan& p, auto sh) -> int {
     typedef decltype(sh) S;
@@ -132,7 +136,7 @@ int launch_dwconv7_ln(const T* x, const float* wdw, const float* bdw, const floa
     else if constexpr (S::kind == DwKind::Mfma) return band(dwconv7_ln_mfma_kernel<T, S::C, S::N>);
     else if constexpr (S::kind == DwKind::Pair) return band(dwconv7_ln_pair_kernel<T, S::C, S::N>);
     else return launch_dw_tile<T>(p, x, wdw, bdw, lnw, lnb, y, nimg, H, W, eps, s);
-  });
+  }, plan_nimg);
 }
 
 // ---- two image groups in one launch (the 224- and the 112-pixel segment of the VAE's merged backbone pass) ----
@@ -217,14 +221,16 @@ template <class S0, class S1, class F, class G> int dw_two_dispatch(const DwPlan
   }
 }
 
-// plans both groups (x / y 16-byte `aligned` or not, per group) and calls f or g as dw_two_dispatch
+// plans both groups (x / y 16-byte `aligned` or not, per group; plan0 / plan1: their plan_nimg) and calls f or g as
+// dw_two_dispatch
 template <typename T, class F, class G>
-int dw_select2(int nimg0, int H0, int W0, bool al0, int nimg1, int H1, int W1, bool al1, int C, F&& f, G&& g) {
+int dw_select2(int nimg0, int H0, int W0, bool al0, int nimg1, int H1, int W1, bool al1, int C, F&& f, G&& g, int plan0 = 0,
+               int plan1 = 0) {
   return dw_select<T>(nimg0, H0, W0, C, al0, [&](const DwPlan& p0, auto sh0) -> int {
     return dw_select<T>(nimg1, H1, W1, C, al1, [&](const DwPlan& p1, auto sh1) -> int {
       return dw_two_dispatch<decltype(sh0), decltype(sh1)>(p0, p1, f, g);
-    });
-  });
+    }, plan1);
+  }, plan0);
 }
 
 template <typename T> bool dw_two_merged(int nimg0, int H0, int W0, int nimg1, int H1, int W1, int C, bool aligned) {
@@ -235,7 +241,7 @@ template <typename T> bool dw_two_merged(int nimg0, int H0, int W0, int nimg1, i
 template <typename T>
 int launch_dwconv7_ln2(const T* x0, T* y0, int nimg0, int H0, int W0, const T* x1, T* y1, int nimg1, int H1, int W1,
                        const float* wdw, const float* bdw, const float* lnw, const float* lnb, int C, float eps,
-                       hipStream_t s) {
+                       hipStream_t s, int plan0, int plan1) {
   auto al = [](const T* x, const T* y) { return ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15u) == 0; };
   return dw_select2<T>(
       nimg0, H0, W0, al(x0, y0), nimg1, H1, W1, al(x1, y1), C,
@@ -252,17 +258,17 @@ int launch_dwconv7_ln2(const T* x0, T* y0, int nimg0, int H0, int W0, const T* x
                          eps);
       },
       [&]() -> int {
-        GCV_TRY(launch_dwconv7_ln<T>(x0, wdw, bdw, lnw, lnb, y0, nimg0, H0, W0, C, eps, s));
-        return launch_dwconv7_ln<T>(x1, wdw, bdw, lnw, lnb, y1, nimg1, H1, W1, C, eps, s);
-      });
+        GCV_TRY(launch_dwconv7_ln<T>(x0, wdw, bdw, lnw, lnb, y0, nimg0, H0, W0, C, eps, s, plan0));
+        return launch_dwconv7_ln<T>(x1, wdw, bdw, lnw, lnb, y1, nimg1, H1, W1, C, eps, s, plan1);
+      }, plan0, plan1);
 }
 
 #define GCV_INSTANTIATE_DW(T)                                                                                        \
   template int dw_plan<T>(DwPlan&, int, int, int, int, bool);                                                        \
   template int launch_dwconv7_ln<T>(const T*, const float*, const float*, const float*, const float*, T*, int, int,   \
-                                    int, int, float, hipStream_t);                                                   \
+                                    int, int, float, hipStream_t, int);                                              \
   template bool dw_two_merged<T>(int, int, int, int, int, int, int, bool);                                           \
   template int launch_dwconv7_ln2<T>(const T*, T*, int, int, int, const T*, T*, int, int, int, const float*,         \
-                                     const float*, const float*, const float*, int, float, hipStream_t);
+                                     const float*, const float*, const float*, int, float, hipStream_t, int, int);
 
 }  // namespace gcv

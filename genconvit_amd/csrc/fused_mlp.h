@@ -36,6 +36,12 @@ struct MlpArgs {
 constexpr int kMlpHC = 96;
 // whether launch_fused_mlp runs the LDS-resident kernel (fused_mlp_res.h: the only one with the LN-patchify epilogue)
 static inline bool fused_mlp_res_applies(int C, int64_t M) { return C == 96 && M >= 256 * 8 * 32; }
+// launch geometry of the two kernels: a wave owns 32-token tiles; the LDS-resident kernel's workgroups of kMlpResWaves
+// waves are persistent (mlp_persistent_wgs) and deal the tiles out among their waves, fused_mlp_kernel's workgroups of
+// kMlpTileWaves waves take one tile per wave
+constexpr int kMlpResWaves = 8, kMlpTileWaves = 4;
+static inline int fused_mlp_wave_tiles(int M) { return cdiv(M, 32); }
+static inline int fused_mlp_tile_wgs(int M) { return cdiv(M, kMlpTileWaves * 32); }
 
 // fused_mlp_kernel: C = 96 in 4-wave workgroups (81 KB of LDS: two independent workgroups per CU overlap each other's
 // prologue and epilogue), 16-bit elements
@@ -254,7 +260,7 @@ __global__ void __launch_bounds__(MlpSmem::NW * 64, 2) fused_mlp_kernel(const Ml
   GCV_STAMP(6);
 }
 
-template <typename T> int launch_fused_mlp(const MlpArgs& a, int C, hipStream_t s);
+template <typename T> int launch_fused_mlp(const MlpArgs& a, int C, hipStream_t s, int wg_cap = kMlpWgCap);
 // W2 (C,4C) fp32 on device -> chunk-major, hidden-permuted T (see header)
 template <typename T> int launch_pack_w2_chunks(const float* w2_dev, T* out, int C, hipStream_t s);
 

@@ -31,12 +31,11 @@ template <typename T> int launch_pack_w2_chunks(const float* w2_dev, T* out, int
   return 0;
 }
 
-template <typename T> int launch_fused_mlp_res(const MlpArgs& a, hipStream_t s) {
+template <typename T> int launch_fused_mlp_res(const MlpArgs& a, hipStream_t s, int wg_cap) {
   constexpr int SMEM = MlpResSmem::bytes;
   GCV_ENSURE_LDS((fused_mlp_res_kernel<T>), SMEM);
-  constexpr int nw = 8;
-  const int wave_tiles = cdiv(a.M, 32);
-  const int nwg = cdiv(wave_tiles, nw) < 256 ? cdiv(wave_tiles, nw) : 256;    // one persistent workgroup per CU
+  constexpr int nw = kMlpResWaves;
+  const int nwg = mlp_persistent_wgs(cdiv(fused_mlp_wave_tiles(a.M), nw), wg_cap);    // one persistent workgroup per CU
   if (a.lnp.nseg > 0) {                                    // last block of the stage: LayerNorm2d + space-to-depth epilogue
     GCV_REQUIRE(a.lnp.w && a.lnp.b && a.lnp.nseg <= 4, "fused MLP: LN-patchify epilogue arguments");
     GCV_ENSURE_LDS((fused_mlp_res_kernel<T, true>), SMEM);
@@ -48,15 +47,17 @@ template <typename T> int launch_fused_mlp_res(const MlpArgs& a, hipStream_t s) 
   return 0;
 }
 
-template <typename T> int launch_fused_mlp(const MlpArgs& a, int C, hipStream_t s) {
+template <typename T> int launch_fused_mlp(const MlpArgs& a, int C, hipStream_t s, int wg_cap) {
   GCV_REQUIRE(a.M > 0 && a.X && a.W1 && a.W2c && a.b1 && a.b2 && a.gamma && a.resid && a.out, "fused MLP: null argument");
+  GCV_REQUIRE(wg_cap >= 1 && wg_cap <= kMlpWgCap, "fused MLP: workgroup cap in [1, 256]");
   // with enough tokens to give every wave of the chip several tiles: weights resident in LDS, no barriers
-  if (fused_mlp_res_applies(C, a.M)) return launch_fused_mlp_res<T>(a, s);
+  if (fused_mlp_res_applies(C, a.M)) return launch_fused_mlp_res<T>(a, s, wg_cap);
   GCV_REQUIRE(a.lnp.nseg == 0, "fused MLP: the LN-patchify epilogue exists in the LDS-resident kernel only");
   GCV_REQUIRE(C == MlpSmem::C, "fused MLP kernels of this file: C = 96");
   constexpr int SMEM = MlpSmem::bytes, NW = MlpSmem::NW;
   GCV_ENSURE_LDS((fused_mlp_kernel<T>), SMEM);
-  hipLaunchKernelGGL((fused_mlp_kernel<T>), dim3(cdiv(a.M, NW * 32)), dim3(NW * 64), SMEM, s, a);
+  static_assert(NW == kMlpTileWaves, "fused_mlp_tile_wgs");
+  hipLaunchKernelGGL((fused_mlp_kernel<T>), dim3(fused_mlp_tile_wgs(a.M)), dim3(NW * 64), SMEM, s, a);
   GCV_CHECK_HIP(hipGetLastError());
   return 0;
 }

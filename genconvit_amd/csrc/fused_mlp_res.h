@@ -351,6 +351,6 @@ __global__ void __launch_bounds__(512, 1) fused_mlp_res_kernel(const MlpArgs a) 
   RES_STAMP(12);
 }
 
-template <typename T> int launch_fused_mlp_res(const MlpArgs& a, hipStream_t s);
+template <typename T> int launch_fused_mlp_res(const MlpArgs& a, hipStream_t s, int wg_cap = kMlpWgCap);
 
 }  // namespace gcv

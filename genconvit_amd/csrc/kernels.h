@@ -32,14 +32,15 @@ struct DwPlan {
 template <typename T> int dw_plan(DwPlan& p, int nimg, int H, int W, int C, bool aligned);   // aligned: x, y 16-byte
 template <typename T> int launch_dwconv7_ln(const T* x, const float* wdw, const float* bdw, const float* lnw,
                                             const float* lnb, T* y, int nimg, int H, int W, int C, float eps,
-                                            hipStream_t s);
+                                            hipStream_t s, int plan_nimg = 0);   // plan_nimg: dw_select, test entries only
 // two image groups of one C (group 0 the wider map) behind one another in ONE grid where dw_select's kernels for them are
 // a pair dwconv_impl.h has a merged kernel for (dw_two_merged says so without a HIP call), in two launches otherwise; each
 // group's kernel, bands and workgroups are those of launch_dwconv7_ln on it alone, and so is every output bit
 template <typename T> bool dw_two_merged(int nimg0, int H0, int W0, int nimg1, int H1, int W1, int C, bool aligned);
 template <typename T> int launch_dwconv7_ln2(const T* x0, T* y0, int nimg0, int H0, int W0, const T* x1, T* y1, int nimg1,
                                              int H1, int W1, const float* wdw, const float* bdw, const float* lnw,
-                                             const float* lnb, int C, float eps, hipStream_t s);
+                                             const float* lnb, int C, float eps, hipStream_t s, int plan_nimg0 = 0,
+                                             int plan_nimg1 = 0);
 template <typename T> int launch_dw_tile(const DwPlan& p, const T* x, const float* wdw, const float* bdw, const float* lnw,
                                          const float* lnb, T* y, int nimg, int H, int W, float eps, hipStream_t s);
 // launches kernel with p's grid, block and dynamic LDS (raising the kernel's limit first where p needs more than 64 KiB)

@@ -550,6 +550,37 @@ template <typename T> int launch_pw2f(const MlpPairArgs& a, int C, hipStream_t s
 template <typename T, typename S> int launch_pack_w1_frag(const S* w1, T* out, int C, hipStream_t s);
 template <typename T, typename S> int launch_pack_w2_frag(const S* w2, const float* gamma, T* out, int C, hipStream_t s);
 static inline bool mlp_pair_supported(int C) { return C == 384; }
+
+// ---- launch geometry of the pair, in one place for the launchers (mlp_pair_impl.h) and gcv_mlp_plan ----
+// Work split of pw1 over 256-token tiles x ns hidden ranges: a workgroup costs its x tile (~3 chunk times) plus its hidden
+// chunks; workgroups beyond the CU count queue behind the first round (one workgroup per CU: the ring takes the whole LDS)
+constexpr int kXsPw1TileTokens = 256;
+static inline int xs_pw1_tiles(int M) { return cdiv(M, kXsPw1TileTokens); }
+static inline int xs_pw1_pick_split(int ntile, int nkc) {
+  int best = 1;
+  long best_cost = -1;
+  for (int ns = 1; ns <= 24; ++ns) {
+    if (nkc % ns || (nkc / ns) % 2) continue;             // whole pairs of chunks per workgroup (two per barrier)
+    const long rounds = ((long)ntile * ns + 255) / 256;
+    const long cost = rounds * (nkc / ns + 3);
+    if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = ns; }
+  }
+  return best;
+}
+// pw2's tile: BN output channels x 32 TB tokens, ring depth D, and its grid
+struct Pw2fTile { int BN, D, TB, grid; };
+static inline Pw2fTile pw2f_pick(int M, int C) {
+  const int ntm = cdiv(M, 256);
+  Pw2fTile t;
+  // full-width tiles halve the operand bytes per FLOP but need >= ~0.7 x 256 of them to keep the chip busy
+  if (ntm >= 180) t = Pw2fTile{C, 3, 8, 0};
+  else if (ntm * (C / 192) >= 128) t = Pw2fTile{192, 4, 8, 0};
+  // a few thousand tokens (batches of 32, the 112-pixel pass): 128-token tiles, twice the workgroups, each with half the
+  // MFMAs per K chunk
+  else t = Pw2fTile{192, 5, 4, 0};
+  t.grid = cdiv(M, 32 * t.TB) * (C / t.BN);
+  return t;
+}
 // bytes of the hidden workspace the pair needs for M tokens
 static inline size_t mlp_pair_hidden_bytes(int64_t M, int C) { return (size_t)((M + 31) / 32) * (size_t)(4 * C / 32) * 2048; }
 

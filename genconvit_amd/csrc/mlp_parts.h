@@ -29,6 +29,13 @@ __device__ __forceinline__ u32x4 halves_to_piece(const uint2 (&h)[2]) {
   return u32x4{x[0], y[0], x[1], y[1]};
 }
 
+// The persistent kernels (fused_mlp_res_kernel, xs_mlp_kernel) launch at most this many workgroups, one per CU.  The kernel
+// test entries gcv_k_fused_mlp*_planned pass a lower cap, so that a few thousand tokens run the passes per workgroup of a
+// large batch; the networks never do.
+constexpr int kMlpWgCap = 256;
+// workgroups of a persistent kernel with `units` workgroup-sized pieces of work
+static inline int mlp_persistent_wgs(int units, int wg_cap) { return units < wg_cap ? units : wg_cap; }
+
 // Optional epilogue of the LAST block of a stage (fused_mlp_res_kernel, xs_mlp_kernel): the stage boundary's LayerNorm2d +
 // 2x2 space-to-depth (timm ConvNeXt `downsample`: LayerNorm2d -> Conv2d(k=2, s=2)) applied to the output rows,
 // which nothing else needs: `out` is then the patchified (M/4, 4C) operand of the down-sampling GEMM and the (M, C) residual

@@ -401,7 +401,8 @@ __global__ void __launch_bounds__(512, 2) xs_mlp_kernel(const XsMlpArgs a, const
   XM_STAMP(6);
 }
 
-template <typename T> int launch_xs_mlp(const XsMlpArgs& a, int C, hipStream_t s);
+template <typename T> int launch_xs_mlp(const XsMlpArgs& a, int C, hipStream_t s, int wg_cap = kMlpWgCap);
+static inline int xs_mlp_passes(int M) { return cdiv(M, 256); }      // 256-token passes, dealt round-robin to the workgroups
 // W1 (4C, C) of T and W2 (C, 4C) of S (T or float) on the device -> the packed records
 template <typename T, typename S> int launch_pack_xs_mlp(const T* w1, const S* w2, T* out, int C, hipStream_t s);
 static inline bool xs_mlp_supported(int C) { return C == 192; }

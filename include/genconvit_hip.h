@@ -616,6 +616,19 @@ int gcv_k_dwconv7_ln2(int dtype, const void* x0, void* y0, int nimg0, int H0, in
  * out5 = {kind (0 tile, 1 tiny, 2 tiny-pair, 3 roll, 4 mfma, 5 pair), workgroups, threads per workgroup, dynamic LDS bytes,
  * rows per band (roll, mfma, pair; else 0)}; or the launcher's error.  No HIP call: works without a GPU. */
 int gcv_dw_plan(int dtype, int nimg, int H, int W, int C, int aligned, int* out5);
+/* Test entries: gcv_k_dwconv7_ln / gcv_k_dwconv7_ln2 on nimg images under the plan of a launch of plan_nimg images (<= 0: of
+ * nimg).  The kernel and the rows per band are those gcv_dw_plan reports for plan_nimg images, the grid covers nimg images:
+ * a few images run the launch geometry of a large batch.  The two-group entry decides on the planning counts whether the
+ * launch is merged (gcv_dw_plan2). */
+int gcv_k_dwconv7_ln_planned(int dtype, const void* x, const float* wdw, const float* bdw, const float* lnw,
+                             const float* lnb, void* y, int nimg, int H, int W, int C, float eps, int plan_nimg,
+                             gcv_stream s);
+int gcv_k_dwconv7_ln2_planned(int dtype, const void* x0, void* y0, int nimg0, int H0, int W0, const void* x1, void* y1,
+                              int nimg1, int H1, int W1, const float* wdw, const float* bdw, const float* lnw,
+                              const float* lnb, int C, float eps, int plan_nimg0, int plan_nimg1, gcv_stream s);
+/* Test query: out1[0] = 1 if gcv_k_dwconv7_ln2 runs these two 16-byte aligned groups as one merged launch, 0 if as two.
+ * No HIP call: works without a GPU. */
+int gcv_dw_plan2(int dtype, int nimg0, int H0, int W0, int nimg1, int H1, int W1, int C, int* out1);
 /* Test query: 1 if gcv_convnext_forward on a handle of backbone `arch` (GCV_CONVNEXT_TINY / _LARGE) runs resolution `res`,
  * 0 if it refuses it (the rule it applies itself).  No HIP call: works without a GPU. */
 int gcv_convnext_res_ok(int arch, int res);
@@ -693,6 +706,25 @@ int gcv_k_fused_mlp_lnp(int dtype, int C, const void* x, const void* w1, const f
                         const float* b2, const float* gamma, const void* resid, const float* ln_w, const float* ln_b,
                         float eps, int nseg, const int* tok0, const int* hw, const int* wd, const int* out0, void* out, int M,
                         gcv_stream s);
+/* Test entries: the two launches above with the persistent kernels (C = 192; C = 96 at M >= 65536) held to at most wg_cap
+ * workgroups, 1 ... 256; the networks run 256, one per CU.  A lower cap gives every workgroup more passes (C = 192) or
+ * every wave more tiles (C = 96): a few thousand tokens run the pass count of a large batch.  The other kernels ignore it. */
+int gcv_k_fused_mlp_planned(int dtype, int C, const void* x, const void* w1, const float* b1, const float* w2_f32,
+                            const float* b2, const float* gamma, const void* resid, void* out, int M, int wg_cap,
+                            gcv_stream s);
+int gcv_k_fused_mlp_lnp_planned(int dtype, int C, const void* x, const void* w1, const float* b1, const float* w2_f32,
+                                const float* b2, const float* gamma, const void* resid, const float* ln_w,
+                                const float* ln_b, float eps, int nseg, const int* tok0, const int* hw, const int* wd,
+                                const int* out0, void* out, int M, int wg_cap, gcv_stream s);
+/* Test query: the kernels and grids of the ConvNeXt MLP at C channels and M tokens, persistent kernels held to wg_cap
+ * workgroups (256: as the networks launch).  out8[0] = kind, the rest by kind:
+ *   0 two tile GEMMs (fp32; 16-bit at other widths than below): zeros, see gcv_gemm_plan
+ *   1 C = 96    {1 LDS-resident persistent kernel / 0 tile kernel, workgroups, 32-token wave tiles, most tiles per wave}
+ *   2 C = 192   {256-token passes, workgroups, most passes per workgroup}
+ *   3 C = 384   {256-token pw1 tiles, hidden ranges ns, 32-wide hidden chunks per workgroup, pw2 tile BN, its ring depth D,
+ *                its 32-token blocks TB, pw2 workgroups}
+ * No HIP call: works without a GPU. */
+int gcv_mlp_plan(int dtype, int C, int M, int wg_cap, int* out8);
 /* The same launch, timed: the weights are packed once, then `iters` launches of the MLP kernel(s) alone are bracketed by
  * HIP events on `s` (the call synchronises).  ms3[0] = average ms per MLP; for the C = 384 kernel pair ms3[1] / ms3[2] are
  * pw1+GELU / pw2+scale+residual timed separately, else 0.  Used by profiles/microbench.py; `out` may alias `resid`. */

@@ -31,7 +31,9 @@ Defects that do not apply to a family (every other entry of the catalogue applie
   GEMM bias/act    no gamma, no shortcut, no branch to scale; ReLU-for-LeakyReLU only where the activation is LeakyReLU;
                    activation-omitted only where there is one
   POOL4 / CONVT    no gamma, no shortcut; CONVT has no pool, POOL4's activation is ReLU
-  dw7x7 + LN       no gamma, no shortcut, no activation; its contraction is the 49 taps (one tap zeroed on one channel)
+  dw7x7 + LN       no gamma, no shortcut, no activation; its contraction is the 49 taps (one tap zeroed on one channel); the two
+                   band-seam defects (a band's first rows without the input rows above it, its last row from the row before)
+                   need a band kernel with more than one band per image
   fused MLP        no pool, no taps; LN-patchify row defects exist only behind gcv_k_fused_mlp_lnp, and the
                    previous-segment-geometry defect needs a second segment
   M = 1            no row before the last one: the row defects are left out at a single row
@@ -481,22 +483,27 @@ def conv_transpose2x2(n, H, cin, cout, act, dtype):
 DW_KINDS = ("tile", "tiny", "tiny_pair", "roll", "mfma", "pair")      # gcv_dw_plan's kind codes (include/genconvit_hip.h)
 
 
-def dw_kind(dtype, n, H, W, C, aligned=True):
-    """the kernel gcv_k_dwconv7_ln runs for this launch, asked of the library's own planner (host code, no GPU)"""
+def dw_plan(dtype, n, H, W, C, aligned=True):
+    """(kind, rows per band) of the kernel gcv_k_dwconv7_ln runs for this launch, asked of the library's own planner (host
+    code, no GPU); rows per band is 0 for the kinds without bands"""
     import ctypes
     from genconvit_amd import _lib
     out = (ctypes.c_int * 5)()
     _lib.check(_lib.load().gcv_dw_plan(_lib.dtype_code(dtype), n, H, W, C, int(aligned), out), "gcv_dw_plan")
-    return DW_KINDS[out[0]]
+    return DW_KINDS[out[0]], out[4]
 
 
-def dwconv7_ln(C, H, W, n, dtype, aligned=True):
+def dwconv7_ln(C, H, W, n, dtype, aligned=True, plan_nimg=0):
     """depthwise 7x7 pad 3 + bias + LayerNorm(C, eps 1e-6); x NCHW here (the test uploads NHWC), NHWC out.  The taps are
     uploaded in fp32.  The matrix-pipe kernel (csrc/dwconv_mfma.h, 16-bit storage) rounds them to the storage dtype, being
-    an MFMA operand; for a launch that gcv_dw_plan sends there, reference, model and defects round them too."""
+    an MFMA operand; for a launch that gcv_dw_plan sends there, reference, model and defects round them too.  plan_nimg > 0:
+    the launch is gcv_k_dwconv7_ln_planned's, n images under the plan (kernel, rows per band) of plan_nimg images.  With
+    more than one band per image the two band-seam defects join the catalogue, built from the plan's rows per band:
+    case.kind and case.band_rows say what was planned."""
     inp = {"x": q(rnd((n, C, H, W), 1, 2.0), dtype), "w": signed((C, 1, 7, 7), 2, 0.05, 0.25),
            "b": signed((C,), 3, 0.1, 0.3), "lw": rnd((C,), 4, 0.5) + 1.0, "lb": signed((C,), 5, 0.1, 0.3)}
-    taps_in_T = dw_kind(dtype, n, H, W, C, aligned) == "mfma"
+    kind, band_rows = dw_plan(dtype, plan_nimg if plan_nimg > 0 else n, H, W, C, aligned)
+    taps_in_T = kind == "mfma"
 
     cache = {}
 
@@ -523,6 +530,23 @@ def dwconv7_ln(C, H, W, n, dtype, aligned=True):
             y = _last_from_prev(y)
         return numutil.ln_ref(y, i["lw"].double(), i["lb"].double(), 1e-6).contiguous()
 
+    # band seams: band 1 of the last image, output rows r0 ... r1 - 1
+    r0, r1 = band_rows, min(2 * band_rows, H)
+
+    def band_head_without_rows_above(i):
+        """the first output rows of band 1 (those whose taps reach above it) computed as if the map began at the band"""
+        d = _d({k: (q(i[k], dtype) if (k == "w" and taps_in_T) else i[k]) for k in ("x", "w", "b")})
+        top = min(r0 + 3, r1)                               # output rows r0 ... top - 1 read input rows above r0
+        rows = F.conv2d(F.pad(d["x"][n - 1:, :, r0:top + 3], (3, 3, 3, max(0, top + 3 - H))), d["w"], d["b"], groups=C)
+        y = conv(i).clone()
+        y[n - 1, r0:top] = rows.permute(0, 2, 3, 1)[0, :top - r0]
+        return ref(i, y=y)
+
+    def band_last_row_from_row_before(i):
+        y = conv(i).clone()
+        y[n - 1, r1 - 1] = y[n - 1, r1 - 2]
+        return ref(i, y=y)
+
     def model(i):
         y = F.conv2d(i["x"], q(i["w"], dtype) if taps_in_T else i["w"], i["b"], padding=3, groups=C).permute(0, 2, 3, 1)
         y = F.layer_norm(y, (C,), i["lw"], i["lb"], 1e-6).double()
@@ -547,22 +571,66 @@ def dwconv7_ln(C, H, W, n, dtype, aligned=True):
             defects[f"{vec}_{name}"] = (lambda i, vec=vec, v=v: ref(_with(i, **{vec: v})))
     if n * H * W > 1:
         defects["last_row_from_row_before"] = lambda i: ref(i, last_from_prev=True)
-    return Case("dw_ln", dtype, inp, ref, model, defects, 3.0, what=f"dwconv_ln C={C} {H}x{W} n={n}")
+    if 0 < band_rows < H:                                   # a band kernel with a seam inside the image
+        defects["band_head_without_rows_above"] = band_head_without_rows_above
+        defects["band_last_row_from_row_before"] = band_last_row_from_row_before
+    case = Case("dw_ln", dtype, inp, ref, model, defects, 3.0,
+                what=f"dwconv_ln C={C} {H}x{W} n={n}" + (f" planned as {plan_nimg} images" if plan_nimg > 0 else ""))
+    case.kind, case.band_rows = kind, band_rows
+    return case
 
 
 # ----------------------------------------------------------------------------- fused ConvNeXt MLP
+MLP_KINDS = ("gemm", "fused96", "xs192", "pair384")      # gcv_mlp_plan's kind codes (include/genconvit_hip.h)
+
+
+def mlp_plan(dtype, C, M, wg_cap=256):
+    """gcv_mlp_plan: (kind, seven fields by kind) of the ConvNeXt MLP at M tokens, the persistent kernels held to wg_cap
+    workgroups (256: the networks' launch); host code, no GPU"""
+    import ctypes
+    from genconvit_amd import _lib
+    out = (ctypes.c_int * 8)()
+    _lib.check(_lib.load().gcv_mlp_plan(_lib.dtype_code(dtype), C, M, wg_cap, out), "gcv_mlp_plan")
+    return (MLP_KINDS[out[0]],) + tuple(out[1:])
+
+
 def xs_pw1_range(C, M):
-    """width of the hidden ranges the C = 384 pw1 kernel's workgroups own at M tokens (csrc/mlp_pair_impl.h,
-    xs_pw1_pick_split: 256-token tiles, whole pairs of 32-wide chunks per workgroup, at most 24 ranges)"""
-    ntile, nkc = -(-M // 256), 4 * C // 32
-    best, best_cost = 1, None
-    for ns in range(1, 25):
-        if nkc % ns or (nkc // ns) % 2:
-            continue
-        cost = ((ntile * ns + 255) // 256) * (nkc // ns + 3)
-        if best_cost is None or cost < best_cost:
-            best, best_cost = ns, cost
-    return 32 * (nkc // best)
+    """width of the hidden ranges the C = 384 pw1 kernel's workgroups own at M tokens: 32-wide chunks per workgroup as
+    gcv_mlp_plan reports them (csrc/mlp_pair.h, xs_pw1_pick_split)"""
+    plan = mlp_plan(F16, C, M)
+    assert plan[0] == "pair384", plan
+    return 32 * plan[3]
+
+
+# ---- launch geometry of the MLP kernels (tests/census.py; tests/test_host_cpu.py asserts that the networks reach exactly
+# the geometries these lists cover).  C = 384, keyed (hidden-range split ns, pw2 tile (BN, D, TB)): the token counts of
+# test_fused_mlp_layerscale_residual (PAIR384_M); for the splits ns = 12, 6, 4, 2 which those leave out, the smallest token
+# count with that split (PAIR384_SPLIT_M); and for the splits that the networks also run beside another pw2 tile, the
+# smallest token count with that pair (PAIR384_TILE_M).  Each is one token more than a whole number of 256-token tiles.
+PAIR384_M = [128, 1000, 6272, 40000, 60013]      # ns 24, 24, 8, 3, 1; pw2 tiles (192, 5, 4) x 3, (192, 4, 8), (384, 3, 8)
+PAIR384_SPLIT_M = [2561, 8193, 10753, 21761]     # ns 12, 6, 4, 2: 4, 8, 12 and 24 chunks per workgroup on the ring of six
+PAIR384_TILE_M = [16129, 45825, 81921, 87297]    # ns 4 + (192, 4, 8); ns 4, 3, 2 + the full-width (384, 3, 8)
+# The persistent kernels, (C, segments or token count, workgroup cap): xs_mlp_kernel (C = 192) and fused_mlp_res_kernel (C = 96,
+# from 65 536 tokens) plain and with the LN-patchify epilogue at one, two and three or more passes per workgroup / tiles per
+# wave.  gcv_k_fused_mlp*_planned holds the launch to `cap` workgroups, so that 2 352 and 69 000 tokens run the four and
+# five passes that a batch of 128 runs on 256.
+PERSISTENT = [
+    (192, 2352, 256), (192, 2352, 5), (192, 2352, 3),                                        # 10 passes: 1, 2, 4 per workgroup
+    (192, [(3, 28, 28)], 256), (192, [(3, 28, 28)], 5), (192, [(5, 28, 28), (5, 14, 14)], 6),   # 10, 10, 20 passes: 1, 2, 4
+    (96, 65536, 256), (96, 70013, 256), (96, 70013, 64),                                     # 2 048 / 2 188 wave tiles: 1, 2, 5
+    (96, [(64, 32, 32)], 256), (96, [(22, 56, 56)], 256), (96, [(21, 56, 56), (9, 28, 28), (3, 14, 14)], 64),   # 1, 2, 5
+]
+
+
+def persistent_key(dtype, C, shape, wg_cap):
+    """(kernel, epilogue, passes per workgroup or tiles per wave as 1 / 2 / 3-and-more) of a PERSISTENT entry"""
+    segs = shape if isinstance(shape, list) else None
+    M = sum(n * h * w for n, h, w in segs) if segs else shape
+    plan = mlp_plan(dtype, C, M, wg_cap)
+    if plan[0] == "xs192":
+        return ("xs192", "lnp" if segs else "plain", min(plan[3], 3))
+    assert plan[0] == "fused96" and plan[1] == 1, (C, M, plan)
+    return ("res96", "lnp" if segs else "plain", min(plan[4], 3))
 
 
 def lnp_index(segs):

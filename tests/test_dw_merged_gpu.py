@@ -5,14 +5,18 @@ launch runs the device code of its single launch under the same plan, so the com
 The map sizes are those of ConvNeXt-T's 224- + 112-pixel pass (the VAE's), stage by stage.  Stages 1 - 3 have a merged
 kernel; stage 0 (C = 96) and every pair outside the table take two launches inside gcv_k_dwconv7_ln2 and must match all the
 same.  Both groups live in one buffer, group 1 behind group 0 as in the network's token stream, with a sentinel image behind
-each group's output: a workgroup that took the other group's geometry or index would write there or leave zeros."""
+each group's output: a workgroup that took the other group's geometry or index would write there or leave zeros.
+
+Those image counts plan the short bands of small launches.  The bands of the VAE's real batches (14- and 7-row bands at B = 128)
+are reached with two images per group through gcv_k_dwconv7_ln2_planned / gcv_k_dwconv7_ln_planned, which take the plan of a
+larger image count: every pair of band geometries that pass reaches at any batch (tests/dwcases.py MERGED)."""
 import ctypes
 
 import pytest
 import torch
 
 from genconvit_amd import _lib
-from tests import kutil
+from tests import dwcases, kutil
 from tests.kutil import DTYPES, dev, ptr, rnd
 
 pytestmark = pytest.mark.gpu
@@ -37,8 +41,9 @@ def _params(C, seed):
     return wdw, rnd((C,), seed + 1, 0.2).to(dev()), (1.0 + rnd((C,), seed + 2, 0.3)).to(dev()), rnd((C,), seed + 3, 0.3).to(dev())
 
 
-def _merged_vs_single(dtype, C, geo0, geo1, seed=0):
-    """geo = (n, H, W).  Returns nothing; asserts the merged launch's outputs equal the two single launches' bit for bit."""
+def _merged_vs_single(dtype, C, geo0, geo1, seed=0, plan=None):
+    """geo = (n, H, W).  Returns nothing; asserts the merged launch's outputs equal the two single launches' bit for bit.
+    plan = (plan_nimg0, plan_nimg1): both sides through the *_planned entries, each group under the plan of that many images."""
     (n0, H0, W0), (n1, H1, W1) = geo0, geo1
     e0, e1 = n0 * H0 * W0 * C, n1 * H1 * W1 * C
     assert e0 % 8 == 0 and e1 % 8 == 0              # both groups 16-byte aligned inside the one buffer
@@ -51,7 +56,15 @@ def _merged_vs_single(dtype, C, geo0, geo1, seed=0):
         x0, x1, y0, y1 = x[:e0], x[e0:], y[:e0], y[e0 + pad0:]
         assert all(t.data_ptr() % 16 == 0 for t in (x0, x1, y0, y1))
         dt = _lib.dtype_code(dtype)
-        if merged:
+        if merged and plan:
+            kutil.call("gcv_k_dwconv7_ln2_planned", dt, ptr(x0), ptr(y0), n0, H0, W0, ptr(x1), ptr(y1), n1, H1, W1, ptr(wdw),
+                       ptr(b), ptr(lw), ptr(lb), C, 1e-6, plan[0], plan[1])
+        elif plan:
+            kutil.call("gcv_k_dwconv7_ln_planned", dt, ptr(x0), ptr(wdw), ptr(b), ptr(lw), ptr(lb), ptr(y0), n0, H0, W0, C, 1e-6,
+                       plan[0])
+            kutil.call("gcv_k_dwconv7_ln_planned", dt, ptr(x1), ptr(wdw), ptr(b), ptr(lw), ptr(lb), ptr(y1), n1, H1, W1, C, 1e-6,
+                       plan[1])
+        elif merged:
             kutil.call("gcv_k_dwconv7_ln2", dt, ptr(x0), ptr(y0), n0, H0, W0, ptr(x1), ptr(y1), n1, H1, W1, ptr(wdw), ptr(b),
                        ptr(lw), ptr(lb), C, 1e-6)
         else:
@@ -75,6 +88,20 @@ def test_two_group_launch_matches_two_launches(dt, n0, n1, C, S0, S1, kinds):
     dtype = DTYPES[dt]
     assert (_plan_kind(dtype, n0, S0, S0, C), _plan_kind(dtype, n1, S1, S1, C)) == kinds
     _merged_vs_single(dtype, C, (n0, S0, S0), (n1, S1, S1), seed=C + n0)
+
+
+@pytest.mark.parametrize("dt", ["f32", "f16", "bf16"])
+@pytest.mark.parametrize("C,H0,H1,plan0,plan1", dwcases.MERGED)
+def test_two_group_launch_at_every_pair_of_band_geometries(dt, C, H0, H1, plan0, plan1):
+    """Two images per group under the plans of the VAE's merged 224- + 112-pixel pass at the batch plan0 = plan1: every pair of
+    (kernel, H, rows per band) that pass reaches at B = 1 ... 512 (tests/dwcases.py MERGED, held against the census of the
+    networks' launches by tests/test_host_cpu.py), against two gcv_k_dwconv7_ln_planned launches under the same plans.
+    The single launches under those plans are compared with the float64 reference in tests/test_kernels_gpu.py."""
+    dtype = DTYPES[dt]
+    out = (ctypes.c_int * 1)()
+    _lib.check(_lib.load().gcv_dw_plan2(_lib.dtype_code(dtype), plan0, H0, H0, plan1, H1, H1, C, out), "gcv_dw_plan2")
+    assert out[0] == 1, "these plans do not merge"
+    _merged_vs_single(dtype, C, (2, H0, H0), (2, H1, H1), seed=C + plan0, plan=(plan0, plan1))
 
 
 @pytest.mark.parametrize("dt", ["f16", "bf16"])

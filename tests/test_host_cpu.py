@@ -177,6 +177,76 @@ def test_every_dw_kernel_has_a_gpu_parity_case():
         assert kinds == ({"roll", "pair"} if dt == "f32" else {"roll", "pair", "mfma"}), (dt, kinds)
 
 
+def test_every_launch_geometry_the_networks_reach_has_a_kernel_case():
+    """The pattern of the test above, applied to geometry.  tests/census.py walks, through the library's planners, every
+    depthwise and MLP launch of ED, VAE (both schedules) and gcv_convnext_forward at every accepted resolution on both
+    backbones at B = 1 ... the handle limit; the geometry keys it reaches must EQUAL the keys that the explicit case lists
+    cover (tests/dwcases.py GEOMETRY and MERGED, tests/kcases.py PAIR384_M + PAIR384_SPLIT_M + PAIR384_TILE_M and PERSISTENT).  A geometry
+    without a case fails; a case that stops reaching its geometry fails; and since every entry is the only one with its key
+    in some storage dtype, so does a list with one entry removed."""
+    from tests import census, dwcases, kcases
+    tiny, large = census.reached("tiny"), census.reached("large")
+    for dt, dtype in census.DTYPES.items():
+        # depthwise band kernels: (kind, C, NS, H, band_rows), each entry at the smallest image count that reaches its key
+        want = dict(large["dw"][dt])
+        for key, n in tiny["dw"][dt].items():
+            want[key] = min(n, want.get(key, n))
+        have = {}
+        for C, H, plan in dwcases.GEOMETRY:
+            key = census.dw_key(dt, plan, H, C)
+            assert key not in have, (dt, "two GEOMETRY entries with one key", key, have[key], plan)
+            have[key] = plan
+        assert have == want, (dt, sorted(set(have.items()) ^ set(want.items())))
+        assert set(dwcases.GEOMETRY_N3) <= set(dwcases.GEOMETRY)
+        n3 = {census.dw_key(dt, plan, H, C)[:3] for C, H, plan in dwcases.GEOMETRY_N3}
+        assert n3 == {k[:3] for k in want}, (dt, "three images once per band kernel", n3)
+        # what the GPU test builds for an entry is what the census keyed
+        for C, H, plan in dwcases.GEOMETRY:
+            assert kcases.dw_plan(dtype, plan, H, H, C) == (census.dw_key(dt, plan, H, C)[0], census.dw_key(dt, plan, H, C)[4])
+        # merged launches: the pair of keys; ConvNeXt-L has none
+        assert not large["dw2"][dt]
+        have2 = {}
+        for C, H0, H1, p0, p1 in dwcases.MERGED:
+            assert census.dw_merged(dt, p0, H0, p1, H1, C), (dt, C, H0, H1, p0, p1)
+            key = (census.dw_key(dt, p0, H0, C), census.dw_key(dt, p1, H1, C))
+            assert key not in have2, (dt, "two MERGED entries with one pair of keys", key)
+            have2[key] = (p0, p1)
+        assert have2 == tiny["dw2"][dt], (dt, sorted(set(have2.items()) ^ set(tiny["dw2"][dt].items())))
+        if dt == "f32":
+            assert not tiny["mlp"][dt] and not large["mlp"][dt]      # two tile GEMMs: tests/gemmcases.py
+            continue
+        reached = set(tiny["mlp"][dt]) | set(large["mlp"][dt])
+        # C = 384: (hidden-range split ns, pw2 tile)
+        new_m = kcases.PAIR384_SPLIT_M + kcases.PAIR384_TILE_M
+        plans = {M: kcases.mlp_plan(dtype, 384, M) for M in kcases.PAIR384_M + new_m}
+        key = lambda M: (plans[M][2], plans[M][4:7])
+        assert {k[1:] for k in reached if k[0] == "pair384"} == {key(M) for M in plans}, \
+            (dt, {k[1:] for k in reached if k[0] == "pair384"} ^ {key(M) for M in plans})
+        assert {p[2]: p[3] for p in plans.values()} == {ns: 48 // ns for ns in (1, 2, 3, 4, 6, 8, 12, 24)}
+        assert {plans[M][2] for M in kcases.PAIR384_M} == {1, 3, 8, 24}
+        assert [plans[M][2] for M in kcases.PAIR384_SPLIT_M] == [12, 6, 4, 2]
+        # each new case is the only one with its key, at the smallest token count that has it, one token into its last tile
+        old = {key(M) for M in kcases.PAIR384_M}
+        for M in new_m:
+            assert key(M) not in old and [m for m in new_m if key(m) == key(M)] == [M], (M, key(M))
+            first = next(m for m in range(1, M + 1, 256) if (lambda p: (p[2], p[4:7]))(kcases.mlp_plan(dtype, 384, m)) == key(M))
+            assert first == M, (M, first)
+            assert kcases.xs_pw1_range(384, M) == 32 * 48 // plans[M][2]
+        # persistent kernels: (kernel, epilogue, passes as 1 / 2 / 3 and more)
+        keys = [kcases.persistent_key(dtype, *entry) for entry in kcases.PERSISTENT]
+        assert len(set(keys)) == len(keys), (dt, "two PERSISTENT entries with one key", keys)
+        assert set(keys) == {k for k in reached if k[0] != "pair384"}, (dt, set(keys) ^ {k for k in reached if k[0] != "pair384"})
+        # the plan of a capped launch: the cap bounds the grid, the passes follow
+        assert kcases.mlp_plan(dtype, 192, 2352, 3)[1:4] == (10, 3, 4) and kcases.mlp_plan(dtype, 192, 2352)[1:4] == (10, 10, 1)
+        assert kcases.mlp_plan(dtype, 96, 70013, 64)[1:5] == (1, 64, 2188, 5) and kcases.mlp_plan(dtype, 96, 70013)[1:5] == (1, 256, 2188, 2)
+        assert kcases.mlp_plan(dtype, 96, 65535)[1:5] == (0, 512, 2048, 1)
+    import ctypes
+    from genconvit_amd import _lib
+    out = (ctypes.c_int * 8)()
+    assert _lib.load().gcv_mlp_plan(_lib.GCV_F16, 192, 2352, 0, out) != 0 and "workgroup cap" in _lib.last_error()
+    assert _lib.load().gcv_mlp_plan(_lib.GCV_F16, 192, 2352, 257, out) != 0
+
+
 def test_gemm_plan_table():
     """The GEMM family's launch, pinned: kernel (tile GEMM and its tile, LDS-DMA GEMM and its LDS row, direct conv), grid,
     threads and dynamic LDS bytes of every launch_gemm call of the ED and VAE networks on both backbones (both VAE schedules),

@@ -58,6 +58,11 @@ CASES = [
     ("dw-roll-384x2x7", kcases.dwconv7_ln, (384, 2, 7, 4), ALL),
     ("dw-pair-1536x5x7", kcases.dwconv7_ln, (1536, 5, 7, 3), ALL),
     ("dw-mfma-96x5x56x717", kcases.dwconv7_ln, (96, 5, 56, 717), H16),      # taps rounded to T, as that kernel does
+    # ... and one launch of several bands per image for each band kernel (two images under the plan of a larger launch, as
+    # tests/dwcases.py GEOMETRY runs them): the two band-seam defects join the catalogue
+    ("dw-roll-two-7-row-bands", lambda C, H, p, dt: kcases.dwconv7_ln(C, H, H, 2, dt, plan_nimg=p), (384, 14, 65), ALL),
+    ("dw-pair-2-row-bands", lambda C, H, p, dt: kcases.dwconv7_ln(C, H, H, 2, dt, plan_nimg=p), (1536, 7, 86), ALL),
+    ("dw-mfma-four-14-row-bands", lambda C, H, p, dt: kcases.dwconv7_ln(C, H, H, 2, dt, plan_nimg=p), (96, 56, 64), H16),
     # stem: stem_ln_mfma_kernel (aligned 16-bit operands, both widths and layouts), stem_ln_kernel (fp32; 16-bit when
     # misaligned).  The long-stream case has the defects of 3 x 9 x 9: they do not depend on the trip count
     ("stem-mfma-96-one-token", kcases.stem, (96, 1, 1, 1, "nchw"), H16),

@@ -269,11 +269,12 @@ def test_dwconv7x7_layernorm(dt, C, H, n):
     _dw_case(DTYPES[dt], C, H, H, n)
 
 
-def _dw_case(dtype, C, H, W, n, shift=0):
+def _dw_case(dtype, C, H, W, n, shift=0, plan_nimg=0):
     """gcv_k_dwconv7_ln on n maps of H x W x C against the float64 conv + LayerNorm of kcases.dwconv7_ln.  The output buffer
     is one image longer than the launch and pre-filled with a sentinel: nothing behind the last image — and, with `shift`
-    elements of offset from the allocation's start, nothing in front of the first — may be written."""
-    case = kcases.dwconv7_ln(C, H, W, n, dtype, aligned=shift == 0)
+    elements of offset from the allocation's start, nothing in front of the first — may be written.  plan_nimg > 0:
+    gcv_k_dwconv7_ln_planned, the n images under the kernel and the rows per band of a launch of plan_nimg images."""
+    case = kcases.dwconv7_ln(C, H, W, n, dtype, aligned=shift == 0, plan_nimg=plan_nimg)
     x, w, b, lw, lb = (case.inputs[k] for k in ("x", "w", "b", "lw", "lb"))
     img = H * W * C
     xbuf = torch.zeros((shift + n * img,), dtype=dtype, device=dev())
@@ -282,10 +283,31 @@ def _dw_case(dtype, C, H, W, n, shift=0):
     xd, out = xbuf[shift:], ybuf[shift:]
     assert xd.data_ptr() % 16 == (shift * xd.element_size()) % 16 and out.data_ptr() % 16 == xd.data_ptr() % 16
     wdw = w.reshape(C, 49).t().contiguous().to(dev())
-    kutil.call("gcv_k_dwconv7_ln", _lib.dtype_code(dtype), ptr(xd), ptr(wdw), ptr(D(b)), ptr(D(lw)), ptr(D(lb)), ptr(out),
-               n, H, W, C, 1e-6)
+    if plan_nimg > 0:
+        kutil.call("gcv_k_dwconv7_ln_planned", _lib.dtype_code(dtype), ptr(xd), ptr(wdw), ptr(D(b)), ptr(D(lw)), ptr(D(lb)),
+                   ptr(out), n, H, W, C, 1e-6, plan_nimg)
+    else:
+        kutil.call("gcv_k_dwconv7_ln", _lib.dtype_code(dtype), ptr(xd), ptr(wdw), ptr(D(b)), ptr(D(lw)), ptr(D(lb)), ptr(out),
+                   n, H, W, C, 1e-6)
     assert (ybuf[:shift].float() == 7.0).all() and (out[n * img:].float() == 7.0).all(), "written outside the n images"
     case.assert_close(out[:n * img].reshape(n, H, W, C))
+
+
+@pytest.mark.parametrize("dt", ALL)
+@pytest.mark.parametrize("C,H,plan_nimg", dwcases.GEOMETRY)
+def test_dwconv7x7_layernorm_at_every_band_geometry(dt, C, H, plan_nimg):
+    """Two images under the plan of plan_nimg: every (kernel, H, rows per band) that a batch of ConvNeXt-T or ConvNeXt-L
+    reaches in any network (tests/dwcases.py GEOMETRY; tests/test_host_cpu.py holds the list against the census of the
+    networks' launches).  The bands of a large launch are long: the Roll walk's ring wraps, Pair reuses its double-buffered
+    LayerNorm partials from row to row, Mfma runs whole-image bands."""
+    _dw_case(DTYPES[dt], C, H, H, 2, plan_nimg=plan_nimg)
+
+
+@pytest.mark.parametrize("dt", ALL)
+@pytest.mark.parametrize("C,H,plan_nimg", dwcases.GEOMETRY_N3)
+def test_dwconv7x7_layernorm_three_images_under_a_large_plan(dt, C, H, plan_nimg):
+    """... and three images once per band kernel: an odd image count under the same plans"""
+    _dw_case(DTYPES[dt], C, H, H, 3, plan_nimg=plan_nimg)
 
 
 @pytest.mark.parametrize("dt", ALL)
@@ -799,23 +821,49 @@ def test_mean_over_tokens_one_token_and_ragged_width(dt, n, L, C):
 @pytest.mark.parametrize("C,M", [(96, 256), (96, 1000), (192, 300), (192, 37),
                                  (96, 70013),       # >= 65536 tokens at C=96: the LDS-resident persistent kernel
                                  (192, 70013),      # C=192 x-stationary kernel: 274 passes on 256 workgroups, i.e. a second pass (ring wrap-around, x reload) in some
-                                 (384, 128), (384, 1000), (384, 6272),      # C=384 kernel pair, small launches: 128-token pw2 tiles, pw1 hidden range split up to 24 ways
-                                 (384, 40000),      # 157 tiles (hidden range split, 256x192 pw2 tiles)
-                                 (384, 60013)])     # ... 235 token tiles: unsplit pw1, full-width 256x384 pw2 tiles, ragged last block
+                                 # C=384 kernel pair (kcases.PAIR384_M): 128, 1000, 6272 are small launches, 128-token pw2 tiles,
+                                 # pw1 hidden range split up to 24 ways; 40000 is 157 tiles (hidden range split, 256x192 pw2
+                                 # tiles); 60013 is 235 token tiles: unsplit pw1, full-width 256x384 pw2 tiles, ragged last block
+                                 ] + [(384, M) for M in kcases.PAIR384_M])
 def test_fused_mlp_layerscale_residual(dt, C, M):
     """timm ConvNeXtBlock tail: fc1 -> exact GELU -> fc2 -> * gamma -> + shortcut, hidden kept on chip."""
     mlp_case(DTYPES[dt], C, M)
 
 
-def mlp_case(dtype, C, M, **kw):
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+@pytest.mark.parametrize("M", kcases.PAIR384_SPLIT_M + kcases.PAIR384_TILE_M)
+def test_fused_mlp_c384_at_every_hidden_range_split(dt, M):
+    """The C = 384 pw1 kernel at the splits the cases above leave out, ns = 12, 6, 4, 2: 4, 8, 12 and 24 hidden chunks per
+    workgroup on a ring of depth 6 (shorter than the ring, the first wrap, two and four wraps), each at the smallest token
+    count with that split, whose last 256-token tile holds one token.  The networks run them from ED at B = 8 on.  Then
+    ns = 4, 3 and 2 beside the pw2 tiles the networks also pair them with (kcases.PAIR384_TILE_M)."""
+    mlp_case(DTYPES[dt], 384, M)
+
+
+@pytest.mark.parametrize("dt", ["bf16", "f16"])
+@pytest.mark.parametrize("C,shape,wg_cap", kcases.PERSISTENT)
+def test_fused_mlp_persistent_kernels_at_every_pass_count(dt, C, shape, wg_cap):
+    """xs_mlp_kernel and fused_mlp_res_kernel, plain and with the LN-patchify epilogue, at one, two and four or five passes per
+    workgroup (tiles per wave): a workgroup cap below the networks' 256 gives a few thousand tokens the middle passes, with
+    a predecessor and a successor, that a batch of 128 runs (kcases.PERSISTENT, held against the census by
+    tests/test_host_cpu.py)."""
+    if isinstance(shape, list):
+        mlp_lnp_case(DTYPES[dt], C, shape, wg_cap=wg_cap)
+    else:
+        mlp_case(DTYPES[dt], C, shape, wg_cap=wg_cap)
+
+
+def mlp_case(dtype, C, M, wg_cap=0, **kw):
     """gcv_k_fused_mlp in place on the shortcut, against kcases.fused_mlp; the rows behind M carry a sentinel.  Also used
-    by tests/test_mlp_bias_init_gpu.py"""
+    by tests/test_mlp_bias_init_gpu.py.  wg_cap > 0: gcv_k_fused_mlp_planned, the persistent kernels on at most wg_cap
+    workgroups."""
     case = kcases.fused_mlp(C, M, dtype, **kw)
     i = case.inputs
     out = torch.full((M + 8, C), 7.0, dtype=dtype, device=dev())
     out[:M] = i["res"].to(dev(), dtype)
-    kutil.call("gcv_k_fused_mlp", _lib.dtype_code(dtype), C, ptr(D(i["x"], dtype)), ptr(D(i["w1"], dtype)), ptr(D(i["b1"])),
-               ptr(D(i["w2"])), ptr(D(i["b2"])), ptr(D(i["gamma"])), ptr(out), ptr(out), M)
+    planned = ("gcv_k_fused_mlp_planned", (wg_cap,)) if wg_cap > 0 else ("gcv_k_fused_mlp", ())
+    kutil.call(planned[0], _lib.dtype_code(dtype), C, ptr(D(i["x"], dtype)), ptr(D(i["w1"], dtype)), ptr(D(i["b1"])),
+               ptr(D(i["w2"])), ptr(D(i["b2"])), ptr(D(i["gamma"])), ptr(out), ptr(out), M, *planned[1])
     assert (out[M:].float() == 7.0).all(), "rows past M were written"
     case.assert_close(out[:M])
 
@@ -896,8 +944,9 @@ def test_fused_mlp_layernorm_patchify_epilogue(dt, C, segs):
     mlp_lnp_case(DTYPES[dt], C, segs)
 
 
-def mlp_lnp_case(dtype, C, segs, **kw):
-    """gcv_k_fused_mlp_lnp on the segments (images, H, W); also used by tests/test_mlp_bias_init_gpu.py"""
+def mlp_lnp_case(dtype, C, segs, wg_cap=0, **kw):
+    """gcv_k_fused_mlp_lnp on the segments (images, H, W); also used by tests/test_mlp_bias_init_gpu.py.  wg_cap > 0:
+    gcv_k_fused_mlp_lnp_planned, the persistent kernels on at most wg_cap workgroups."""
     M = sum(n * h * w for n, h, w in segs)
     case = kcases.fused_mlp(C, M, dtype, segs=segs, **kw)
     i = case.inputs
@@ -909,9 +958,10 @@ def mlp_lnp_case(dtype, C, segs, **kw):
     arr = lambda v: (ctypes.c_int * 4)(*(v + [0] * (4 - len(v))))
     a_tok0, a_hw, a_wd, a_out0 = arr(tok0), arr(hw), arr(wd), arr(out0)
     resd = D(i["res"], dtype)
-    kutil.call("gcv_k_fused_mlp_lnp", _lib.dtype_code(dtype), C, ptr(D(i["x"], dtype)), ptr(D(i["w1"], dtype)),
+    planned = ("gcv_k_fused_mlp_lnp_planned", (wg_cap,)) if wg_cap > 0 else ("gcv_k_fused_mlp_lnp", ())
+    kutil.call(planned[0], _lib.dtype_code(dtype), C, ptr(D(i["x"], dtype)), ptr(D(i["w1"], dtype)),
                ptr(D(i["b1"])), ptr(D(i["w2"])), ptr(D(i["b2"])), ptr(D(i["gamma"])), ptr(resd), ptr(D(i["lw"])),
-               ptr(D(i["lb"])), 1e-6, len(segs), a_tok0, a_hw, a_wd, a_out0, ptr(out), M)
+               ptr(D(i["lb"])), 1e-6, len(segs), a_tok0, a_hw, a_wd, a_out0, ptr(out), M, *planned[1])
     assert torch.equal(resd.cpu(), i["res"].to(dtype)), "the residual stream must not be written"
     assert (out[M // 4:].float() == 7.0).all(), "rows behind the last patch row were written"
     case.assert_close(out[:M // 4])
