@@ -79,6 +79,8 @@ SIGNATURES = {
                                 c_int, c_void_p, c_void_p]),
     "gcv_scan_annotate": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                                   c_void_p, c_void_p]),
+    "gcv_yuv420_to_rgb": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "gcv_rgb_to_yuv420": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gcv_track_match": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gcv_track_chain": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "gcv_frame_hist": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
@@ -868,14 +870,17 @@ def sig_link(sig, owner, tracks):
 CUT_REGIONS, CUT_BINS = (1, 2, 4, 8), 64
 
 
-def _out_buffer(what, out, shape, device):
-    """``out`` if it is a contiguous int32 tensor of ``shape`` on ``device``, a new one for None, else an error."""
+def _out_buffer(what, out, shape, device, dtype=None):
+    """``out`` if it is a contiguous tensor of ``dtype`` (int32 by default) and ``shape`` on ``device``, a new one for None,
+    else an error."""
     import torch
+    dtype = dtype or torch.int32
     if out is None:
-        return torch.empty(shape, dtype=torch.int32, device=device)
-    if not (torch.is_tensor(out) and out.dtype == torch.int32 and out.device == device and tuple(out.shape) == shape
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not (torch.is_tensor(out) and out.dtype == dtype and out.device == device and tuple(out.shape) == shape
             and out.is_contiguous()):
-        raise GenConViTHipError(f"{what}: out must be a contiguous int32 tensor of shape {shape} on {device}")
+        raise GenConViTHipError(f"{what}: out must be a contiguous {str(dtype).replace('torch.', '')} tensor of shape {shape} "
+                                f"on {device}")
     return out
 
 
@@ -1115,6 +1120,71 @@ def scan_annotate(frames_u8, frame_no, marks, timeline=None, strip=0, out=None):
                                 tl.data_ptr() if strip > 0 else None, lanes, t, strip, out.data_ptr(),
                                 current_stream_ptr(dev)), "gcv_scan_annotate")
     return out
+
+
+YUV_LAYOUTS, YUV_MATRICES = ("i420", "nv12"), ("bt601", "bt709")      # the C entries' codes are the positions
+
+
+def _check_yuv_names(what, layout, matrix):
+    """The C entries' (layout, matrix) codes; an unknown name is an error."""
+    if layout not in YUV_LAYOUTS:
+        raise GenConViTHipError(f"{what}: unknown layout {layout!r}; accepted values are 'i420' and 'nv12'")
+    if matrix not in YUV_MATRICES:
+        raise GenConViTHipError(f"{what}: unknown matrix {matrix!r}; accepted values are 'bt601' and 'bt709'")
+    return YUV_LAYOUTS.index(layout), YUV_MATRICES.index(matrix)
+
+
+def yuv420_geometry(what, shape):
+    """(F, H, W) of a (F, 3H/2, W) YUV 4:2:0 buffer; a shape that is none, or an odd H or W, is an error."""
+    if len(shape) != 3 or shape[1] < 3 or shape[1] % 3 or shape[2] < 2 or shape[2] % 2:
+        raise GenConViTHipError(f"{what}: a shape of {tuple(shape)}; YUV 4:2:0 frames are (F, 3H/2, W) with H and W even and "
+                                f"at least 2")
+    return int(shape[0]), int(shape[1]) * 2 // 3, int(shape[2])
+
+
+def yuv420_to_rgb(frames, layout="i420", matrix="bt709", full_range=False, out=None):
+    """YUV 4:2:0 frames to RGB (``gcv_yuv420_to_rgb``, include/genconvit_hip.h: the layouts and the arithmetic are stated
+    there).  ``frames``: (F, 3H/2, W) uint8 device tensor, one row of 3HW/2 bytes per frame as a decoder delivers it, H and W
+    even; a slice such as ``frames[1:]`` is used in place, whatever its alignment.  ``layout``: "i420" or "nv12"; ``matrix``:
+    "bt601" or "bt709"; ``full_range``: 0 ... 255 rather than 16 ... 235 / 240.  Returns (F,H,W,3) uint8 RGB on the device;
+    ``out``: write into this contiguous uint8 tensor of that shape on the same device instead of a new one.  F = 0 launches
+    nothing.  A host tensor, a wrong dtype, rank or shape, odd sizes and unknown names are errors."""
+    import torch
+    what = "yuv420_to_rgb"
+    if not (torch.is_tensor(frames) and frames.dtype == torch.uint8 and frames.dim() == 3):
+        raise GenConViTHipError(f"{what} expects a uint8 device tensor of shape (F, 3H/2, W)")
+    nf, h, w = yuv420_geometry(what, frames.shape)
+    lay, mat = _check_yuv_names(what, layout, matrix)
+    if not frames.is_cuda:                   # last, so that the checks above do not need a device
+        raise GenConViTHipError(f"{what} expects a uint8 device tensor of shape (F, 3H/2, W); there is no CPU path")
+    frames = frames.contiguous()
+    rgb = _out_buffer(what, out, (nf, h, w, 3), frames.device, torch.uint8)
+    lib = load()
+    if nf:
+        check(lib.gcv_yuv420_to_rgb(frames.data_ptr(), nf, h, w, lay, mat, 1 if full_range else 0, rgb.data_ptr(),
+                                    current_stream_ptr(frames.device)), "gcv_yuv420_to_rgb")
+    return rgb
+
+
+def rgb_to_yuv420(frames, layout="i420", matrix="bt709", full_range=False, out=None):
+    """RGB frames to YUV 4:2:0 (``gcv_rgb_to_yuv420``, include/genconvit_hip.h), the reverse of ``yuv420_to_rgb``: ``frames``
+    (F,H,W,3) uint8 device tensor, H and W even and at least 2, of any alignment; returns (F, 3H/2, W) uint8 on the device in
+    ``layout``, each chroma sample from the sum of its 2 x 2 block.  ``out``: write into this contiguous uint8 tensor of that
+    shape on the same device instead of a new one.  F = 0 launches nothing."""
+    import torch
+    what = "rgb_to_yuv420"
+    frames, (nf, h, w) = _check_frames(frames, f"{what} expects a uint8 device tensor of shape (F,H,W,3)", on_device=False)
+    if h < 2 or w < 2 or h % 2 or w % 2:
+        raise GenConViTHipError(f"{what}: frames of {h}x{w} pixels; H and W must be even and at least 2")
+    lay, mat = _check_yuv_names(what, layout, matrix)
+    if not frames.is_cuda:                   # last, so that the checks above do not need a device
+        raise GenConViTHipError(f"{what} expects a uint8 device tensor of shape (F,H,W,3); there is no CPU path")
+    yuv = _out_buffer(what, out, (nf, 3 * h // 2, w), frames.device, torch.uint8)
+    lib = load()
+    if nf:
+        check(lib.gcv_rgb_to_yuv420(frames.data_ptr(), nf, h, w, lay, mat, 1 if full_range else 0, yuv.data_ptr(),
+                                    current_stream_ptr(frames.device)), "gcv_rgb_to_yuv420")
+    return yuv
 
 
 def vote_segments(logits, batch, nets, offsets):

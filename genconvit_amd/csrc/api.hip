@@ -873,6 +873,18 @@ int gcv_scan_annotate(const void* frames_u8_nhwc, int nframes, int H, int W, con
                               strip, (unsigned char*)out_u8_nhwc, (hipStream_t)stream);
 }
 
+int gcv_yuv420_to_rgb(const void* yuv_u8, int nframes, int H, int W, int layout, int matrix, int full_range,
+                      void* rgb_u8_nhwc, gcv_stream stream) {
+  return launch_yuv420_to_rgb((const unsigned char*)yuv_u8, nframes, H, W, layout, matrix, full_range,
+                              (unsigned char*)rgb_u8_nhwc, (hipStream_t)stream);
+}
+
+int gcv_rgb_to_yuv420(const void* rgb_u8_nhwc, int nframes, int H, int W, int layout, int matrix, int full_range,
+                      void* yuv_u8, gcv_stream stream) {
+  return launch_rgb_to_yuv420((const unsigned char*)rgb_u8_nhwc, nframes, H, W, layout, matrix, full_range,
+                              (unsigned char*)yuv_u8, (hipStream_t)stream);
+}
+
 int gcv_track_match(const void* frames_u8_nhwc, int nframes, int H, int W, const int* jobs17, int n, int grid, int radius,
                     int* out4, gcv_stream s) {
   GCV_REQUIRE(n <= 0 || (frames_u8_nhwc && jobs17 && out4), "track match: null pointer");

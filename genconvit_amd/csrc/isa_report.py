@@ -28,6 +28,13 @@ Checks (run by the Makefile on every build):
     kernel's scratch (.private_segment_fixed_size) must stay within SCRATCH_BUDGET: 0 bytes unless listed, and the listed
     ones are the few dwords hipcc 7.2 spills outside the steady-state loops today.  Raising an entry is a decision, not a
     side effect.
+
+ 4. v_ashr_pk_u8_i32 / v_ashr_pk_i8_i32 (new on gfx950: shift two int32 right and pack them as saturated bytes).  hipcc
+    (ROCm 7.2) forms it from clip(a >> n, 0, 255) | clip(b >> n, 0, 255) << 8 and then ORs the result into a wider word as if
+    bits 16 ... 31 of the destination were zero.  On the MI355X they were not: yuv.hip's first form packed its RGB bytes
+    that way, and a channel that saturated came out with the byte behind its pair polluted (tests/test_yuv_gpu.py against
+    tests/yuvutil.py).  No kernel here needs the instruction, so any occurrence is an error; the way round it is to clip
+    before the shift (yuv.hip, yuv_clip14).
 """
 import re
 import subprocess
@@ -143,6 +150,11 @@ def check_file(path):
     text = open(path).read()
     for kname, body in kernels(text):
         short = re.sub(r'\(.*', '', demangle(kname))[:90]
+        # ---- check 4
+        for ln, t, _ in body:
+            if re.match(r'v_ashr_pk_[ui]8_i32\b', t):
+                findings.append(f"{path}:{ln}: {short}: `{t}` — the upper half of its result is not to be relied on; clip "
+                                f"before the shift (isa_report.py check 4)")
         # ---- check 1
         for i, (ln, t, _) in enumerate(body):
             m = re.match(r'buffer_store_dwordx[34]\s+(.*)', t)

@@ -90,6 +90,12 @@ int launch_cam_overlay(const unsigned char* frames, int nframes, int H, int W, c
 // annotate.hip: a scan's marks (outline, number tab) and its timeline strip drawn onto the frames, uint8 RGB in and out
 int launch_scan_annotate(const unsigned char* frames, int nframes, int H, int W, const int* frame_no, const int* marks8,
                          int n, const unsigned* timeline, int lanes, int T, int strip, unsigned char* out, hipStream_t s);
+// yuv.hip: decoder-native YUV 4:2:0 frames (layout 0 = i420, 1 = nv12; matrix 0 = bt601, 1 = bt709) to the uint8 RGB slab,
+// and an RGB slab back to YUV 4:2:0
+int launch_yuv420_to_rgb(const unsigned char* yuv, int nframes, int H, int W, int layout, int matrix, int full_range,
+                         unsigned char* rgb, hipStream_t s);
+int launch_rgb_to_yuv420(const unsigned char* rgb, int nframes, int H, int W, int layout, int matrix, int full_range,
+                         unsigned char* yuv, hipStream_t s);
 // follow.hip: block matching of a face between two detector frames, n jobs of 17 ints -> n rows (oy, ox, cost, cost0)
 int launch_track_match(const unsigned char* frames, int nframes, int H, int W, const int* jobs17, int n, int grid,
                        int radius, int* out4, hipStream_t s);

@@ -5,7 +5,8 @@ Same names and argument meaning (``load_genconvit``, ``preprocess_frame``, ``pre
 ``is_video``, ``set_result``, ``store_result``), plus what the reference lacks: evidence maps (``explain_*``) and the
 whole-video scan with per-track sliding-window verdicts (``scan_frames``, ``scan_video``; ``follow_tracks`` moves the
 boxes of frames the detector skipped onto the face, ``shot_cuts`` finds the hard cuts at which tracks end, ``shot_transitions`` the fades and dissolves whose frames stay out
-of them; ``render_scan`` / ``render_video`` draw the scan's result back onto the frames).  ``prediction.py`` star-imports this module and
+of them; ``render_scan`` / ``render_video`` draw the scan's result back onto the frames; ``YUV420`` / ``read_yuv420`` hand all of
+these a decoder's YUV 4:2:0 frames in place of RGB).  ``prediction.py`` star-imports this module and
 relies on ``torch``/``os``/``np`` coming along, so they stay module globals.  The heavy CPU-side
 dependencies (dlib, face_recognition, decord) are imported lazily inside the video / face
 functions so the model path imports on a box without them; cv2 is not needed any more (the crop +
@@ -187,10 +188,10 @@ def explain_frames(frames, model, boxes=None, locate=None, eps=None, target=None
         raise ValueError(f"unknown map {which!r}: accepted values are 'ed', 'vae' and 'mean'")
     fr = _as_frames("explain_frames", frames)
     if boxes is None:
-        boxes = (locate or face_locations)(frames)
+        boxes = (locate or face_locations)(fr.rgb(None, device).cpu().numpy() if isinstance(fr, YUV420) else frames)
     boxes = list(boxes)[:len(fr)]
     _lib._check_boxes("explain_frames", boxes, *fr.shape[:3])
-    fr = fr.to(device)
+    fr = _rgb_slab(fr, slice(None), device)
     if len(boxes) == 0:
         return (None, None), fr, []
     df = preprocess_frame(crop_faces(fr, boxes))
@@ -224,18 +225,89 @@ def window_ranges(length, window, stride):
     return [(s, s + window) for s in starts]
 
 
+class YUV420:
+    """Frames as a video decoder delivers them — YUV 4:2:0, 1.5 bytes a pixel — for everything here that takes RGB frames:
+    ``scan_frames``, ``follow_tracks``, ``extend_tracks``, ``shot_cuts``, ``shot_transitions``, ``face_quality``,
+    ``face_signatures``, ``explain_frames`` and ``render_scan`` accept a ``YUV420`` where they accept uint8 (F,H,W,3) RGB.
+    ``data``: uint8 (F, 3H/2, W), numpy or a tensor on either device, one row of 3HW/2 bytes per frame, H and W even;
+    ``layout``: "i420" (the Y plane, then U, then V, what ``-pix_fmt yuv420p -f rawvideo`` writes) or "nv12" (the Y plane,
+    then rows of interleaved U, V: a hardware decoder's surface); ``matrix``: "bt601" or "bt709"; ``full_range``: 0 ... 255
+    rather than Y 16 ... 235, C 16 ... 240.  Anything else is a ``GenConViTHipError`` here, before anything runs.
+    A stage asks for the frames of one of its groups and gets them as RGB on the device (``rgb``): host bytes are
+    uploaded as YUV, half of what RGB frames weigh, and one ``_lib.yuv420_to_rgb`` launch converts the group (include/
+    genconvit_hip.h states the integer arithmetic; each chroma sample serves its 2 x 2 block).  The groups are the ones
+    host RGB frames are cut into — also for data already on the device, whose RGB form never exists as a whole — so
+    every later launch sees the slab and the batch it would see for the same pixels given as RGB.
+    ``shape`` is the RGB shape (F, H, W, 3); ``len``, ``is_cuda`` and ``device`` describe ``data``."""
+
+    def __init__(self, data, layout="i420", matrix="bt709", full_range=False):
+        t = data if torch.is_tensor(data) else torch.as_tensor(np.ascontiguousarray(data))
+        if not (t.dtype == torch.uint8 and t.dim() == 3):
+            raise _lib.GenConViTHipError("YUV420: data must be uint8 of shape (F, 3H/2, W)")
+        nf, h, w = _lib.yuv420_geometry("YUV420", t.shape)
+        _lib._check_yuv_names("YUV420", layout, matrix)
+        self.data, self.layout, self.matrix, self.full_range = t.contiguous(), layout, matrix, bool(full_range)
+        self.shape = (nf, h, w, 3)
+
+    def __len__(self):
+        return self.shape[0]
+
+    @property
+    def is_cuda(self):
+        return self.data.is_cuda
+
+    @property
+    def device(self):
+        return self.data.device
+
+    @property
+    def colour(self):
+        return {"matrix": self.matrix, "full_range": self.full_range}
+
+    def rgb(self, index=None, dev=None):
+        """The frames ``index`` (None: all; a slice; a list of frame numbers) as a uint8 (n,H,W,3) RGB slab on the device:
+        their bytes go to ``dev`` (default: where they are if that is a GPU, else this module's ``device``) and one
+        ``_lib.yuv420_to_rgb`` converts them.  The slab is new with every call."""
+        d = self.data
+        if isinstance(index, slice):
+            d = d[index]
+        elif index is not None:
+            d = d.index_select(0, torch.as_tensor(index, dtype=torch.int64, device=d.device))
+        return _lib.yuv420_to_rgb(d.to(dev if dev is not None else d.device if d.is_cuda else device), self.layout, self.matrix,
+                                  self.full_range)
+
+
 def _as_frames(what, frames):
-    """``frames`` (numpy or a tensor on either device) as a tensor; anything but uint8 (F,H,W,3) is an error."""
+    """``frames`` (numpy or a tensor on either device) as a tensor; anything but uint8 (F,H,W,3) is an error.  A ``YUV420``
+    passes through: it has the shape, and ``_rgb_slab`` gets its pixels."""
+    if isinstance(frames, YUV420):
+        return frames
     fr = frames if torch.is_tensor(frames) else torch.as_tensor(np.ascontiguousarray(frames))
     if not (fr.dtype == torch.uint8 and fr.dim() == 4 and fr.shape[3] == 3):
         raise _lib.GenConViTHipError(f"{what}: frames must be uint8 of shape (F,H,W,3)")
     return fr
 
 
+def _resident(fr):
+    """Are the frames RGB on a GPU, to be used in place?  Host frames and every ``YUV420`` go group by group."""
+    return torch.is_tensor(fr) and fr.is_cuda
+
+
+def _rgb_slab(fr, index, dev, copy=False):
+    """The frames ``index`` (a slice or a sorted list of frame numbers) of ``fr`` as an RGB slab on ``dev``: the one place
+    where a stage's group of frames reaches the device, uploaded as they are, or as YUV and converted there.  ``copy``: the
+    slab is the caller's to draw on even when the frames are on ``dev`` already."""
+    if isinstance(fr, YUV420):
+        return fr.rgb(index, dev)
+    if isinstance(index, slice):
+        return fr[index].to(dev, copy=True) if copy else fr[index].to(dev)
+    return fr.index_select(0, torch.as_tensor(index, device=fr.device)).to(dev)
+
+
 def _upload(fr, used, dev):
     """What one group of a stage needs of ``fr``: the frames ``used`` (frame numbers, sorted) as a slab on ``dev``, and the map
     from frame number to slab row.  Which rows make a group is each stage's own business."""
-    return fr.index_select(0, torch.as_tensor(used, device=fr.device)).to(dev), {f: k for k, f in enumerate(used)}
+    return _rgb_slab(fr, used, dev), {f: k for k, f in enumerate(used)}
 
 
 def _is_whole(v):
@@ -355,7 +427,7 @@ def follow_tracks(frames, tracks, anchors, grid=64, radius=16, max_frames=128, d
     if not jobs:
         return out, follow
     res = np.zeros((len(jobs), 4), dtype=np.int64)
-    if fr.is_cuda:
+    if _resident(fr):
         res[:] = _lib.track_match(fr, [j[2] for j in jobs], grid=grid, radius=radius).cpu().numpy()
     else:
         groups, used = [], set()
@@ -469,7 +541,7 @@ def extend_tracks(frames, tracks, ends=None, grid=EXTEND_DEFAULTS["grid"], radiu
                 if tuple(r) == _lib.TRACK_CHAIN_NONE:
                     break
                 found[c].append(tuple(r))
-    if chains and fr.is_cuda:
+    if chains and _resident(fr):
         ids = [(c, 0, ch[3]) for c, ch in enumerate(chains)]
         take(ids, _lib.track_chain(fr, [row(*i) for i in ids], grid=grid, radius=radius).cpu().numpy())
     elif chains:
@@ -561,13 +633,13 @@ def _frame_stats(fr, regions, grid, max_frames, dev):
     histograms of ``_lib.frame_hist`` and the (F, G^2) cell sums of ``_lib.frame_cells``; ``regions`` or ``grid`` None leaves
     that one out.  Device frames are used in place; host frames are uploaded once each, in consecutive groups of at most
     ``max_frames``, and every group fills its rows of the two device buffers."""
-    if fr.is_cuda:
+    if _resident(fr):
         return (_lib.frame_hist(fr, regions) if regions else None), (_lib.frame_cells(fr, grid) if grid else None)
     nf, d = int(fr.shape[0]), dev or device
     hist = torch.empty((nf, regions * regions, _lib.CUT_BINS), dtype=torch.int32, device=d) if regions else None
     cells = torch.empty((nf, grid * grid), dtype=torch.int32, device=d) if grid else None
     for g in range(0, nf, max_frames):
-        slab = fr[g:g + max_frames].to(d)
+        slab = _rgb_slab(fr, slice(g, g + max_frames), d)
         if regions:
             _lib.frame_hist(slab, regions, out=hist[g:g + max_frames])
         if grid:
@@ -745,7 +817,7 @@ def face_quality(frames, boxes, grid=64, max_frames=128, dev=None):
     n = len(rows)
     raw = np.zeros((n, 8), dtype=np.int64)
     big = [i for i, b in enumerate(rows) if b[3] - b[1] >= grid and b[2] - b[4] >= grid]
-    if big and fr.is_cuda:
+    if big and _resident(fr):
         raw[big] = _lib.face_quality(fr, [rows[i] for i in big], grid=grid).cpu().numpy()
     elif big:
         for ids, slab, local in _box_groups(fr, rows, big, max_frames, dev or device):
@@ -831,7 +903,7 @@ def face_signatures(frames, boxes, max_frames=128, dev=None):
     if not big:
         return {"sig": torch.empty((0, _lib.SIG_BYTES), dtype=torch.uint8, device=to) if n == 0 else
                 torch.zeros((n, _lib.SIG_BYTES), dtype=torch.uint8, device=to), "measured": measured}
-    if fr.is_cuda:
+    if _resident(fr):
         parts, order = [_lib.face_signature(fr, [rows[i] for i in big])], list(big)
     else:
         parts, order = [], []
@@ -1082,7 +1154,11 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
                 transitions=None, transition_args=None, quality=None, quality_args=None, persons=None,
                 person_args=None, extend=None, extend_args=None):
     """When is a video fake, and whose face: every face of every frame is scored, linked into per-person tracks, and voted
-    over sliding windows of each track.  ``frames``: uint8 (F,H,W,3) RGB, numpy or a tensor on either device.  ``boxes``:
+    over sliding windows of each track.  ``frames``: uint8 (F,H,W,3) RGB, numpy or a tensor on either device, or a ``YUV420``
+    (decoder-native frames: every stage's groups are then uploaded as YUV, half the bytes, and converted on the device;
+    the result is the one the same pixels give as host RGB frames.  With ``boxes=None`` the detector still wants RGB on
+    the host: the frames ``[::detect_every]`` are converted on the device in groups of ``max_batch`` and downloaded, which
+    is the price of a CPU detector — callers with their own boxes pay nothing).  ``boxes``:
     rows (frame, top, right, bottom, left); by default the detector — ``locate``, else ``face_locations(..., keep_all=True)``
     — runs on ``frames[::detect_every]``, handed over as a numpy array on the host whatever ``frames`` is, and its frame
     indices are mapped back.  ALL faces are kept: the ``len(frames)`` cut is ``face_rec``'s contract, not this function's,
@@ -1191,7 +1267,13 @@ def scan_frames(frames, model, boxes=None, locate=None, detect_every=1, iou=0.3,
                         cut_threshold, cut_regions, transitions, transition_args, quality, quality_args, persons, person_args,
                         extend, extend_args)
     if boxes is None:
-        seen = (fr.cpu().numpy() if torch.is_tensor(frames) else np.asarray(frames))[::detect_every]
+        if isinstance(fr, YUV420):                          # the price of a CPU detector: see the docstring
+            pick = list(range(0, len(fr), detect_every))
+            dev = next(model.parameters()).device
+            seen = torch.cat([fr.rgb(pick[g:g + max_batch], dev).cpu() for g in range(0, len(pick), max_batch)]).numpy() \
+                if pick else np.empty((0, *fr.shape[1:]), dtype=np.uint8)
+        else:
+            seen = (fr.cpu().numpy() if torch.is_tensor(frames) else np.asarray(frames))[::detect_every]
         found = locate(seen) if locate is not None else face_locations(seen, keep_all=True)
         boxes = [(int(b[0]) * detect_every, *b[1:]) for b in found]
     boxes = [tuple(int(v) for v in b) for b in boxes]
@@ -1236,10 +1318,43 @@ def _read_frames(vid, select):
     return vr.get_batch(index).asnumpy(), index
 
 
+def read_yuv420(file_or_path, H, W, layout="i420", max_frames=None, **colour):
+    """A raw YUV 4:2:0 stream as a ``YUV420``: what ``-pix_fmt yuv420p|nv12 -f rawvideo`` writes, frames of 3HW/2 bytes back
+    to back with no header, so ``H``, ``W`` (even) and ``layout`` are the caller's to know.  ``file_or_path``: a path
+    (``numpy.fromfile``) or an open binary file object such as a decoder's pipe (``read`` until the end, or until
+    ``max_frames`` frames); ``colour``: ``matrix`` and ``full_range`` as ``YUV420`` takes them.  A stream that ends inside a
+    frame is a ``GenConViTHipError``; an empty one gives F = 0.  The frames stay on the host: the scan uploads them group
+    by group."""
+    if not (_is_whole(H) and _is_whole(W) and H >= 2 and W >= 2 and H % 2 == 0 and W % 2 == 0):
+        raise _lib.GenConViTHipError(f"read_yuv420: H {H} and W {W} must be even integers of at least 2")
+    if max_frames is not None and (not _is_whole(max_frames) or max_frames < 0):
+        raise _lib.GenConViTHipError(f"read_yuv420: max_frames {max_frames} must be None or an integer >= 0")
+    _lib._check_yuv_names("read_yuv420", layout, colour.get("matrix", "bt709"))
+    size = 3 * int(H) * int(W) // 2
+    want = -1 if max_frames is None else int(max_frames) * size
+    if isinstance(file_or_path, (str, bytes, os.PathLike)):
+        data = np.fromfile(file_or_path, dtype=np.uint8, count=want)
+    else:
+        parts, got = [], 0
+        while want < 0 or got < want:                       # a pipe may hand over less than was asked for
+            piece = file_or_path.read(-1 if want < 0 else want - got)
+            if not piece:
+                break
+            parts.append(piece)
+            got += len(piece)
+        data = np.frombuffer(b"".join(parts), dtype=np.uint8).copy()
+    if data.size % size:
+        raise _lib.GenConViTHipError(f"read_yuv420: the stream holds {data.size} bytes, {data.size // size} frames of "
+                                     f"{size} bytes ({H}x{W}) and a partial one of {data.size % size}")
+    return YUV420(data.reshape(-1, 3 * int(H) // 2, int(W)), layout, **colour)
+
+
 def scan_video(vid, model, every=1, max_frames=None, **kw):
     """``scan_frames`` on the frames ``range(0, len, every)[:max_frames]`` of the video file ``vid``; the result also
     holds ``frame_index``, the source frame number of each scanned frame (the frame numbers in ``tracks``, ``windows``
-    and ``segments`` count scanned frames: look them up there)."""
+    and ``segments`` count scanned frames: look them up there).  The file is decoded to RGB on the CPU by third-party
+    code (decord); the route without that conversion is ``scan_frames(read_yuv420(pipe, H, W), ...)`` on a decoder's raw
+    ``yuv420p`` / ``nv12`` output."""
     if every < 1:
         raise ValueError(f"scan_video: every {every} must be at least 1")
     frames, index = _read_frames(vid, lambda n: list(range(0, n, every))[:max_frames])
@@ -1324,9 +1439,11 @@ def _render_plan(what, fr, res, label, eps, lut, thick, strip, max_frames, max_b
 
 
 def render_scan(frames, res, model=None, evidence=True, label="track", eps=None, layer="s3", which="mean", alpha=0.5,
-                weighted=True, lut=None, thick=None, strip=None, max_frames=128, max_batch=128, sink=None):
+                weighted=True, lut=None, thick=None, strip=None, max_frames=128, max_batch=128, sink=None, out="rgb",
+                out_matrix="bt709", out_full_range=False):
     """The result of ``scan_frames`` drawn onto the frames it was run on, for the reviewer of a flagged video.  ``frames``:
-    the uint8 (F,H,W,3) RGB frames that were scanned, numpy or a tensor on either device (they are not changed); ``res``:
+    the uint8 (F,H,W,3) RGB frames that were scanned, numpy or a tensor on either device, or a ``YUV420`` (they are not
+    changed); ``res``:
     what ``scan_frames`` returned for them — ``boxes``, ``track_offsets``, ``frame_scores`` and ``segments`` are read, and
     ``persons`` for ``label="person"``.  Anything else, a crop row on a frame the video does not have, a ``label`` other than
     "track", "person" or None, and "person" without ``res["persons"]`` are a ValueError before anything runs.  Drawn, by
@@ -1358,10 +1475,24 @@ def render_scan(frames, res, model=None, evidence=True, label="track", eps=None,
     uint8 (m,H,W,3) device tensor (the caller encodes or stores it; the slab is not reused) and None is returned; otherwise
     the rendered frames come back as one uint8 (F,H,W,3) CPU tensor.  With no crop row the frames carry the timeline only
     (they are untouched when ``strip`` is 0) and ``model`` is not called.
+    ``out``: "rgb" (the default: all of the above), or "i420" / "nv12" for an encoder that wants YUV 4:2:0 — after
+    ``_lib.scan_annotate`` every group goes through one ``_lib.rgb_to_yuv420`` (include/genconvit_hip.h: integer arithmetic,
+    each chroma sample from the sum of its 2 x 2 block) and ``sink`` gets, or the call returns, uint8 (m, 3H/2, W): half
+    the bytes of the RGB frames on the way back.  The matrix and range are those of ``frames`` when it is a ``YUV420``,
+    else ``out_matrix`` ("bt601" or "bt709") and ``out_full_range``.  An unknown ``out`` or ``out_matrix`` and an odd H or W
+    with a YUV ``out`` are a ValueError before anything runs.
     Not shown: how accurate the scores are, and whether a Grad-CAM map is faithful to what the network used.  Encoding the
     frames into a video file is the caller's."""
     fr = _as_frames("render_scan", frames)
     nf, h, w = (int(v) for v in fr.shape[:3])
+    if out not in ("rgb",) + _lib.YUV_LAYOUTS:
+        raise ValueError(f"render_scan: unknown out {out!r}: accepted values are 'rgb', 'i420' and 'nv12'")
+    colour = fr.colour if isinstance(fr, YUV420) else {"matrix": out_matrix, "full_range": bool(out_full_range)}
+    if out != "rgb":
+        if colour["matrix"] not in _lib.YUV_MATRICES:
+            raise ValueError(f"render_scan: unknown out_matrix {out_matrix!r}: accepted values are 'bt601' and 'bt709'")
+        if h < 2 or w < 2 or h % 2 or w % 2:
+            raise ValueError(f"render_scan: out={out!r} needs frames of even height and width, not {h}x{w}")
     rows, marks, timeline, strip, rows_ev = _render_plan("render_scan", fr, res, label, eps, lut, thick, strip, max_frames,
                                                          max_batch, which)
     p = next(model.parameters()) if model is not None else None
@@ -1374,7 +1505,7 @@ def render_scan(frames, res, model=None, evidence=True, label="track", eps=None,
     with torch.no_grad():
         for g in range(0, nf, max_frames):
             m = min(max_frames, nf - g)
-            slab = fr[g:g + m].to(dev, copy=True)                   # one upload; drawn on in place
+            slab = _rgb_slab(fr, slice(g, g + m), dev, copy=True)   # one upload; drawn on in place
             ids = [i for i in rows_ev if g <= rows[i][0] < g + m]
             for s in range(0, len(ids), max_batch):
                 sub = ids[s:s + max_batch]
@@ -1387,13 +1518,19 @@ def render_scan(frames, res, model=None, evidence=True, label="track", eps=None,
                                  out=slab)
             here = [(mk[0] - g, *mk[1:]) for mk in marks if g <= mk[0] < g + m]
             _lib.scan_annotate(slab, list(range(g, g + m)), here, timeline if strip else None, strip, out=slab)
+            if out != "rgb":
+                slab = _lib.rgb_to_yuv420(slab, out, **colour)
             if sink is not None:
                 sink(g, slab)
             else:
                 done.append(slab.cpu())
     if sink is not None:
         return None
-    return torch.cat(done) if done else fr.cpu().clone()
+    if done:
+        return torch.cat(done)
+    if out == "rgb" and torch.is_tensor(fr):
+        return fr.cpu().clone()
+    return torch.empty((0, 3 * h // 2, w) if out != "rgb" else (0, h, w, 3), dtype=torch.uint8)
 
 
 def render_video(vid, model, every=1, max_frames=None, scan=None, **kw):
@@ -1401,7 +1538,8 @@ def render_video(vid, model, every=1, max_frames=None, scan=None, **kw):
     once: returns ``(res, rendered)``.  ``scan``: a dict of ``scan_frames``'s keyword arguments; ``kw``: ``render_scan``'s
     (its own ``max_frames`` keeps its default here).  ``res`` also holds ``frame_index``, as ``scan_video``'s does.  An
     ``eps`` is given to each of the two on its own.  Decoding is third-party CPU code (decord) and encoding the rendered
-    frames is the caller's."""
+    frames is the caller's.  This route moves RGB both ways; the YUV route is ``read_yuv420`` for the frames and
+    ``render_scan(..., out="i420" | "nv12")`` for the way back."""
     if every < 1:
         raise ValueError(f"render_video: every {every} must be at least 1")
     frames, index = _read_frames(vid, lambda n: list(range(0, n, every))[:max_frames])

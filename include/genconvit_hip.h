@@ -260,6 +260,50 @@ int gcv_cam_overlay(const void* frames_u8_nhwc, int nframes, int H, int W, const
 int gcv_scan_annotate(const void* frames_u8_nhwc, int nframes, int H, int W, const int* frame_no, const int* marks8, int n,
                       const unsigned* timeline, int lanes, int T, int strip, void* out_u8_nhwc, gcv_stream stream);
 
+/* The decoder's and the encoder's side of a scan: YUV 4:2:0 frames as H.264 / HEVC decoders produce them, 1.5 bytes a
+ * pixel, to the uint8 RGB frames every entry above reads (gcv_yuv420_to_rgb), and RGB frames back (gcv_rgb_to_yuv420).
+ * One launch each, every byte read once and written once.
+ *   yuv     nframes frames of 3 H W / 2 bytes each on the device, packed back to back (what a rawvideo pipe delivers):
+ *             layout 0, i420: the Y plane H x W, then U (H/2) x (W/2), then V (H/2) x (W/2), each contiguous
+ *             layout 1, nv12: the Y plane, then H/2 rows of W bytes U V U V ...
+ *           frame f starts at byte f 3 H W / 2; the pointer may have any alignment
+ *   rgb     (nframes,H,W,3) uint8 RGB on the device, any alignment
+ *   matrix  0: bt601, (Kr, Kb) = (0.299, 0.114);  1: bt709, (0.2126, 0.0722);  Kg = 1 - Kr - Kb
+ *   full_range  0: Y in 16 ... 235 and U, V in 16 ... 240 (limited);  otherwise 0 ... 255
+ * The two buffers differ in size and must not overlap: neither call works in place.
+ * Chroma siting: a chroma sample belongs to its 2 x 2 block of pixels — all four get it on the way in, it is the block's
+ * mean on the way out.  Arithmetic (fixed and all-integer, so that a CPU restatement is bit-equal: tests/yuvutil.py);
+ * int32, >> is an arithmetic shift, round(c 2^14) is round half up of the exact value:
+ *   in     y' = Y - oy, oy = 16 (limited) or 0;  u' = U - 128;  v' = V - 128;  ky = 255/219 or 1, kc = 255/224 or 1
+ *            R = clip((cy y' + crv v' + 8192) >> 14, 0, 255)             cy = round(ky 2^14), crv = round(kc 2 (1 - Kr) 2^14)
+ *            G = clip((cy y' + cgu u' + cgv v' + 8192) >> 14, 0, 255)    cgu = round(-kc 2 (1 - Kb) Kb / Kg 2^14),
+ *                                                                        cgv = round(-kc 2 (1 - Kr) Kr / Kg 2^14)
+ *            B = clip((cy y' + cbu u' + 8192) >> 14, 0, 255)             cbu = round(kc 2 (1 - Kb) 2^14)
+ *            (oy, cy, crv, cgu, cgv, cbu):  bt601 limited (16, 19077, 26149, -6419, -13320, 33050)
+ *                                           bt601 full    (0, 16384, 22970, -5638, -11700, 29032)
+ *                                           bt709 limited (16, 19077, 29372, -3494, -8731, 34610)
+ *                                           bt709 full    (0, 16384, 25802, -3069, -7670, 30402)
+ *   out    Y = oy + ((ar R + ag G + ab B + 8192) >> 14);  s = 219/255 or 1;  ar = round(Kr s 2^14), ab = round(Kb s 2^14),
+ *            ag = round(s 2^14) - ar - ab, so that white gives 235 / 255 exactly
+ *          with (Sr, Sg, Sb) the sums over the block's four pixels, 0 ... 1020, and t = 224/255 or 1:
+ *            U = clip(128 + ((ur Sr + ug Sg + ub Sb + 32768) >> 16), 0, 255)   ur = round(-Kr / (2 (1 - Kb)) t 2^14), ub = round(t 2^13)
+ *            V = clip(128 + ((vr Sr + vg Sg + vb Sb + 32768) >> 16), 0, 255)   vr = round(t 2^13), vb = round(-Kb / (2 (1 - Kr)) t 2^14)
+ *            ug = -ur - ub and vg = -vr - vb, so that grey gives 128 exactly
+ *            (oy, ar, ag, ab; ur, ug, ub; vr, vg, vb):
+ *              bt601 limited (16, 4207, 8260, 1604; -2428, -4768, 7196; 7196, -6026, -1170)
+ *              bt601 full    (0, 4899, 9617, 1868; -2765, -5427, 8192; 8192, -6860, -1332)
+ *              bt709 limited (16, 2991, 10064, 1016; -1649, -5547, 7196; 7196, -6536, -660)
+ *              bt709 full    (0, 3483, 11718, 1183; -1877, -6315, 8192; 8192, -7441, -751)
+ * Refused before anything is launched (gcv_last_error() says why): H or W odd or outside 2 ... 65536, a layout or matrix
+ * other than 0 and 1, nframes negative, nframes H W >= 2^31, a null pointer with nframes > 0.  nframes == 0 launches
+ * nothing.  The calls allocate, copy and synchronise nothing.
+ * Not done here: interpolated (co-sited) chroma, 4:2:2 / 4:4:4 / 10-bit formats, bt2020, bit-equality with any third-party
+ * converter. */
+int gcv_yuv420_to_rgb(const void* yuv_u8, int nframes, int H, int W, int layout, int matrix, int full_range,
+                      void* rgb_u8_nhwc, gcv_stream stream);
+int gcv_rgb_to_yuv420(const void* rgb_u8_nhwc, int nframes, int H, int W, int layout, int matrix, int full_range,
+                      void* yuv_u8, gcv_stream stream);
+
 /* Follow a face between two detector frames: integer block matching of n (track, skipped frame) jobs in one launch.
  * A whole-video scan runs its CPU face detector on every k-th frame; in a skipped frame the face is searched around the
  * interpolated ("prior") box, with the two detected faces around the gap as templates.
